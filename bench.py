@@ -19,8 +19,11 @@ have pending jobs on the rank, so fewer partitions per rank get the wider k_wide
         --master-port 29500 bench.py --gpus 8 --steps 3 --warmup 1
 
 Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel (k_wide; k_pipe / k_select when CNS_SELECT_KERNEL=pipe / legacy) with the ALGORITHMIC
-bytes of SURVEY.md §8(d) (N_p*S_node + S_job + S_out per decision) over its HIP-event duration;
-`cpu_baseline` times the CPU oracle (kind "port": a restatement of the reference algorithm on bit masks, pinned to the
+bytes of SURVEY.md §8(d) (N_p*S_node + S_job + S_out per decision) over its HIP-event duration.
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own: the SURVEY 8(d)
+bracket from host buffers (`incl_h2d_d2h`), the run-limit admission pass (`run_limits`, C4), the check of the N > 1 all-gather
+against one engine's run, and the CPU baseline.  --dump-outputs DIR writes the placements of the last timed step (dump_outputs()).
+In a --full run, `cpu_baseline` times the CPU oracle (kind "port": a restatement of the reference algorithm on bit masks, pinned to the
 reference's own code by tests/test_ref_pin.py) on ONE WHOLE PARTITION of the same queue (partitions never interact), single
 pinned thread like the reference, and diffs its placements against the engine's; `cpu_baseline.reference_build` times THE
 REFERENCE'S OWN CODE (oracle/_ref: slices of JobScheduler.{h,cpp} / PublicHeader.{h,cpp} compiled in the build container and
@@ -53,6 +56,45 @@ def _wide_shape(kernel: str) -> str:
     return f"single GPU, 1 + {waves // 4} workgroups per partition (k_wide, {waves} scanner waves)"
 
 
+DUMP_JOBS = 1 << 20      # per-job arrays: every job up to this many, else a seeded sample of this many
+DUMP_PLACES = 1 << 18    # per-placement arrays: a seeded sample of this many records
+DUMP_SEED = 0x43524E45
+
+
+def _dump_sample(n: int, k: int, seed: int) -> np.ndarray:
+    """Sorted indices of a fixed sample of k out of n (all of them when n <= k): a function of (n, k, seed) alone."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir: str, got, jobs) -> dict:
+    """The placements a caller of the timed path receives (cns_download), as float64 .npy files: job j's start_sec / reason
+    (every job, or a seeded sample: job_index), and a seeded sample of the placement records (place_index) with the
+    job owning each (place_job).  64-bit bit masks are split into their low and high 32-bit words (`_w0`, `_w1`) so that
+    float64 holds them exactly.  At most 3 x DUMP_JOBS + 16 x DUMP_PLACES float64 values: 56 MiB (< 64 MB).  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    J = jobs.num_jobs
+    places = jobs.total_places()
+    ji = _dump_sample(J, DUMP_JOBS, DUMP_SEED)
+    pi = _dump_sample(places, DUMP_PLACES, DUMP_SEED + 1)
+    offsets = np.concatenate([[0], np.cumsum(jobs.node_num.astype(np.int64))])   # cns_placement_soa: exclusive prefix sum of node_num
+    arrays = {"job_index": ji, "start_sec": got.start_sec[ji], "reason": got.reason[ji],
+              "place_index": pi, "place_job": np.searchsorted(offsets, pi, side="right") - 1}
+    for f in ("node_idx", "ntasks", "cpu_raw", "mem"):
+        arrays[f] = getattr(got, f)[pi]
+    for f in ("core_lo", "core_hi", "gres", "core_w2", "core_w3"):
+        w = getattr(got, f)[pi].astype(np.uint64)
+        arrays[f + "_w0"] = w & np.uint64(0xFFFFFFFF)
+        arrays[f + "_w1"] = w >> np.uint64(32)
+    shapes = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -63,8 +105,14 @@ def main():
     ap.add_argument("--nodes", type=int, default=None, help="override N (debug only)")
     ap.add_argument("--cpu-sample-jobs", type=int, default=0, help="CPU baseline on the first N jobs of the queue only (0 = whole queue; debug)")
     ap.add_argument("--cpu-partition", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements and checks beyond the headline: incl_h2d_d2h, run_limits, the all-gather check, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the placements of the last timed step to DIR/<name>.npy (float64; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # --config c5deep: BASELINE config 5's queue (1 M jobs with walltimes in 256 slots of 675 s) on a QUARTER of its nodes.  The frozen C5 (3.75 M
     # cores of demand on 4.19 M) never fills its cluster — every job starts now, nothing is ever packed into a window —; on 16 384 nodes 72 % of the
     # jobs are backfilled: the walltime-packing regime the configuration is named after (tests/golden/make_fullrun.py "c5deep": digest vs the oracle).
@@ -127,7 +175,7 @@ def main():
     # so it is timed separately and reported in "run_limits" next to the headline; single-GPU only (its order is the
     # global pending order, which spans the partition shards).
     limits = None
-    if world == 1 and args.config == "C4":
+    if args.full and world == 1 and args.config == "C4":
         limits = synth.make_limits(args.config, cluster, jobs)
         eng.set_run_limits(limits[0])
 
@@ -193,11 +241,16 @@ def main():
         dist.all_reduce(ordered, op=dist.ReduceOp.SUM)
     elapsed = float(el.item())
     total_jobs = int(ordered.item())
+    got = None
+    if rank == 0:     # the last timed step's placements (rank 0's shard at N > 1), before anything else runs on the engine
+        got = eng.download()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, got, my_jobs)
 
-    # N > 1 (or CNS_BENCH_FORCE_DIST=1): what the all-gather delivered is unpacked and merged on rank 0 and compared with
+    # --full, N > 1 (or CNS_BENCH_FORCE_DIST=1): what the all-gather delivered is unpacked and merged on rank 0 and compared with
     # ONE engine run over the whole queue on rank 0's GPU (untimed): the collective path is checked, not just exercised
     gather_check = None
-    if use_dist and rank == 0:
+    if args.full and use_dist and rank == 0:
         torch.cuda.synchronize()
         host = eng.download_gathered(pad * world) if gather_out is None else gather_out.cpu().numpy()
         shards = []
@@ -251,7 +304,6 @@ def main():
                                        "build; 2 x FETCH_SIZE (gfx950) + WRITE_SIZE, mean per launch of the dominant kernel (tools/gpu_bench.sh)"}
         except (OSError, KeyError):
             pass
-        got = eng.download()
         kernel = eng.last_kernel()
         # SURVEY 8(d) prices a configuration with time slots (C5: T = 256, Q = 675 s) at N_p * (16 * W + 8) + S_job + S_out bytes per decision,
         # W = ceil(L / Q) slots in the job's window; the engine's own count (cns_timing::algorithmic_bytes) is the T = 1 form N_p * S_node.
@@ -273,7 +325,7 @@ def main():
         # buffers — H2D of the job arrays, record packing, the kernels, D2H of the placements.  Median of 5 after the
         # warm-up above; reported beside `value` (which, per the bench contract, starts with the inputs resident in HBM).
         incl = None
-        if world == 1:
+        if args.full and world == 1:
             walls = []
             for _ in range(5):
                 torch.cuda.synchronize()
@@ -308,7 +360,7 @@ def main():
             "metric": "scheduling decisions/sec at 1M pending x 64k nodes",
             # `value`: inputs resident in HBM when the timed region starts (the bench contract: "if the boundary hands over host buffers, note the
             # PCIe-inclusive rate ... it is never `value`").  SURVEY 8(d)'s metric — the reference's own bracket incl. H2D of the job arrays and D2H of
-            # the placements — is `incl_h2d_d2h.decisions_per_s` (1 - 2 % below `value`); both are in every line.
+            # the placements — is `incl_h2d_d2h.decisions_per_s` (1 - 2 % below `value`); both are in every --full line.
             "value": value, "kernel_resident_decisions_per_s": value, "unit": "decisions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "int64", "data": "synthetic",
@@ -375,7 +427,7 @@ def main():
                 lim_line["cpu_port_ms"] = 1e3 * (time.perf_counter() - c0)
                 lim_line["identical_to_cpu_port"] = bool(np.array_equal(r_ref, lim_reason) and a_ref == lim_adm)
             line["run_limits"] = lim_line
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # CPU baseline on the SAME queue: partitions never interact, so one partition's whole shard (all of its
             # ~J/P jobs on its N/P nodes: cluster filling AND the loaded / backfill regime) is a bounded, unbiased sample
             # of the full queue's per-decision cost.  Single thread like the reference (JobScheduler.cpp:1322,6742),

@@ -85,3 +85,35 @@ def test_bench_names_the_shape_of_every_wide_build():
     assert bench._wide_shape("k_wide<2> x8").startswith("single GPU, 1 + 2 workgroups")
     assert bench._wide_shape("k_wide<2> x64 + k_select<37> on 1 of 8 partitions").startswith("single GPU, 1 + 16 workgroups")
     assert bench._wide_shape("k_wide") == "single GPU, k_wide"
+
+
+def test_bench_dump_outputs_is_exact_bounded_and_fixed(tmp_path):
+    """bench.py --dump-outputs: float64 files that hold the placements exactly (64-bit masks as two 32-bit words), the same sample
+    for the same queue, under 64 MB at the headline size."""
+    import numpy as np
+    import bench
+    from cranesched_amd import abi, synth
+    _, jobs, _ = synth.make_config("C4")
+    got = abi.Placements(jobs.num_jobs, jobs.total_places())
+    rng = np.random.default_rng(7)
+    for f in abi.Placements.FIELDS:
+        a = getattr(got, f)
+        a[:] = rng.integers(0, np.iinfo(a.dtype).max, a.shape, dtype=a.dtype, endpoint=True)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), got, jobs)
+    bench.dump_outputs(str(tmp_path / "b"), got, jobs)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n in shapes) and files == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64e6
+    ld = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / "b" / (n + ".npy"))) for n, a in ld.items())
+    ji, pi = ld["job_index"].astype(np.int64), ld["place_index"].astype(np.int64)
+    assert np.array_equal(ji, np.arange(jobs.num_jobs))
+    assert np.array_equal(ld["start_sec"], got.start_sec[ji].astype(np.float64)) and np.array_equal(ld["reason"], got.reason[ji])
+    assert len(pi) == bench.DUMP_PLACES and np.all(np.diff(pi) > 0) and pi[-1] < jobs.total_places()
+    off = np.concatenate([[0], np.cumsum(jobs.node_num.astype(np.int64))])
+    pj = ld["place_job"].astype(np.int64)
+    assert np.all((off[pj] <= pi) & (pi < off[pj + 1]))
+    assert np.array_equal(ld["node_idx"], got.node_idx[pi]) and np.array_equal(ld["mem"], got.mem[pi].astype(np.float64))
+    for f in ("core_lo", "core_hi", "gres", "core_w2", "core_w3"):
+        w = (ld[f + "_w1"].astype(np.uint64) << np.uint64(32)) | ld[f + "_w0"].astype(np.uint64)
+        assert np.array_equal(w, getattr(got, f)[pi]), f

@@ -3,12 +3,12 @@
 out=gpurun_out/$1; mkdir -p $out
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-timeout 600 python bench.py --gpus 1 --steps 5 --warmup 2 > $out/bench_n1.json 2> $out/bench_n1.err
+timeout 600 python bench.py --gpus 1 --steps 5 --warmup 2 --full > $out/bench_n1.json 2> $out/bench_n1.err
 echo "bench rc=$?"; tail -c 3000 $out/bench_n1.json
 cd /tmp
-timeout 300 rocprofv3 --kernel-trace --stats -d $R/$out/stats -o stats --output-format csv -- python $R/bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline > $R/$out/stats.log 2>&1
-timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $R/$out/pmc_fetch -o f --output-format csv -- python $R/bench.py --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline > $R/$out/pmc_fetch.log 2>&1
-timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $R/$out/pmc_write -o w --output-format csv -- python $R/bench.py --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline > $R/$out/pmc_write.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $R/$out/stats -o stats --output-format csv -- python $R/bench.py --gpus 1 --steps 3 --warmup 1 --full --no-cpu-baseline > $R/$out/stats.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $R/$out/pmc_fetch -o f --output-format csv -- python $R/bench.py --gpus 1 --steps 2 --warmup 1 --full --no-cpu-baseline > $R/$out/pmc_fetch.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $R/$out/pmc_write -o w --output-format csv -- python $R/bench.py --gpus 1 --steps 2 --warmup 1 --full --no-cpu-baseline > $R/$out/pmc_write.log 2>&1
 cd $R
 find $out -name "*kernel_stats.csv" | head -2 | xargs -I{} head -12 {}
 python3 - <<PY

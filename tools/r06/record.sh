@@ -4,7 +4,7 @@
 o=${1:-r06rec2}; out=gpurun_out/$o; mkdir -p $out
 bash tools/gpu_bench.sh $o > $out/script.log 2>&1
 for c in C5 c5deep C2 C3 C4r C4p64 C4p256; do
-  timeout 600 python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_$c.json 2> $out/bench_$c.err
+  timeout 600 python bench.py --config $c --steps 3 --warmup 1 --full --no-cpu-baseline > $out/bench_$c.json 2> $out/bench_$c.err
 done
 ( for t in 32 16; do timeout 300 cranesched_amd/host/test_host_adapter --e2e-bench 65536 8 1000000 deferred $t; done ) > $out/adapter_e2e.txt 2>&1
 timeout 900 python tools/r06/soak.py ${SOAK:-12} c4 c4v c5 2>&1 | grep -v amdgpu.ids > $out/soak.txt
