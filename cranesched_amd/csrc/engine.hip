@@ -36,6 +36,18 @@ using namespace cns;
 
 namespace {
 
+// Widest snapshots served.  A partition that shares no node and is wider than k_wide's widest tile (65 536 slots), and a group of
+// partitions sharing nodes that is wider than k_mem's ordinary row masks (143 360 slots), run on k_giant (launch_giant: the home
+// workgroup's sequential protocol plus helper workgroups that scan stripes of the slots); where the helpers' co-residency cannot be
+// proven, on k_mem — its 5-word masks up to 143 360 slots, the giant instantiation's 19-word masks above.  Above these limits:
+// CNS_PART_REFUSED_WIDTH for that partition / group only.
+constexpr u32 kGiantPartSlots = 262144;   // one partition that shares no node (and one reservation's virtual partition)
+constexpr u32 kGiantGroupSlots = 524288;  // a group of partitions that share nodes (ALL over 262 144 nodes + subsets that cover it once more)
+static_assert(kGiantPartSlots <= kGiantGroupSlots && kGiantGroupSlots <= w8::WideInfo::giant_mem_slots, "k_mem's giant masks hold the widest group");
+static_assert(w8::WideInfo::mem_slots >= w64::WideInfo::lanes * w64::WideInfo::npl_max, "k_wide's widest tile stays below k_mem's ordinary masks");
+// the widest partition / group a snapshot may hold (cns_set_nodes refuses the others with CNS_PART_REFUSED_WIDTH)
+inline u32 width_cap(bool group) { return group ? kGiantGroupSlots : kGiantPartSlots; }
+
 std::string g_create_error;
 
 struct DevBuf {
@@ -138,6 +150,7 @@ struct cns_engine {
   std::vector<uint8_t> pre_part;                // cycle with preemption: engine partition has a pending job whose qos may preempt
   DevBuf d_params2, d_pmap_a, d_pmap_b, d_wide_last;
   DevBuf d_params3, d_pmap_c, d_wide_mem;       // the serial-only launch of k_wide (groups wider than k_select's tile)
+  DevBuf d_giant;                               // ... its GiantCtl blocks when it runs with helper workgroups (k_giant)
   DevBuf d_flen, d_tag_off, d_tag_base;         // ... its compact map lengths, and the slot range of every member partition of a group
   std::vector<u32> tag_off, tag_base;
   // several devices (group_host.inc): this engine's rank in a communicator, the all-gathered results of every rank
@@ -147,6 +160,7 @@ struct cns_engine {
   double gather_ms = 0.0;
   u64 gather_bytes = 0;
   bool wide_off = false;                        // this run must not use k_wide (the retry after a k_wide protocol fault)
+  bool giant_off = false;                       // ... nor k_giant's helpers (the same retry: k_mem instead)
   u32 wide_retries = 0;                         // cycles that were re-run on k_pipe / k_select after a k_wide fault (lifetime of the handle)
   // MultiFactorPriority (priority_host.inc)
   DevBuf d_prio[27];
@@ -286,6 +300,7 @@ void fill_params(cns_engine* h, KParams& K, i64 now) {
   K.wide_ctl = h->d_wide.as<char>();
   K.general_only = h->pre_active ? 1u : 0u;
   K.serial_only = 0;
+  K.giant_ctl = nullptr; K.giant_nh = 0; K.pad_gnh = 0;
   K.pre = h->pre_active ? h->pre_params : PreParams{};
   K.gres = h->gres;
   if (h->shared) {
@@ -364,9 +379,13 @@ int launch_wide(cns_engine* h, const KParams& K, const LaunchCtx& L, std::string
 // k_wide's HOME workgroup alone, every job through the sequential protocol with its tester waves as memory scanners over the
 // committed HBM arrays (KParams::serial_only).  The narrowest build serves (its two scanner workgroups per partition leave at once);
 // no workgroup waits for another one, so no co-residency is needed.  Slow — every job reads every slot of its group — and exact.
+// Above W::mem_slots (143 360) the giant instantiation (19-word row masks, up to W::giant_mem_slots) serves the launch: same protocol,
+// more scratch per memory-scanner lane; the launches that fit the ordinary masks keep the ordinary kernel.
 int launch_mem(cns_engine* h, const KParams& K, const LaunchCtx& L, std::string* name) {
   using W = w8::WideInfo;
-  const void* fn = (const void*)w8::k_wide<1, false>;
+  if (L.max_np > W::giant_mem_slots) return 2;   // (cns_set_nodes refuses such groups: never reached)
+  const bool giant = L.max_np > W::mem_slots;
+  const void* fn = giant ? (const void*)w8::k_wide<1, false, w8::kWMemWordsGiant> : (const void*)w8::k_wide<1, false>;
   const unsigned groups = (L.nparts + 7u) / 8u;
   const unsigned grid = 8u * groups * W::group;
   const size_t need = (size_t)h->P * W::ctl_bytes;
@@ -385,7 +404,47 @@ int launch_mem(cns_engine* h, const KParams& K, const LaunchCtx& L, std::string*
   const KParams* dparams = L.dparams;
   void* args[2] = {(void*)&K2, (void*)&dparams};
   if (hipLaunchKernel(fn, dim3(grid), dim3(W::block), args, dyn, L.stream) != hipSuccess) return 1;
-  *name = "k_mem (k_wide<1> home workgroup, sequential protocol over the HBM arrays)";
+  *name = giant ? "k_mem giant (k_wide<1> home workgroup, sequential protocol over the HBM arrays, 19-word row masks)"
+               : "k_mem (k_wide<1> home workgroup, sequential protocol over the HBM arrays)";
+  return 0;
+}
+// k_giant (wide_kernel.inc, "k_giant"): the giant instantiation in serial-only mode plus `nh` helper workgroups per partition that
+// scan stripes of the job's slots; grid = nparts x (1 + nh), the home of partition i is block i.  The helpers and the home wait for
+// each other, so every workgroup must be resident at once: proven with the runtime's occupancy figure (one workgroup per CU: the
+// LDS pad of launch_mem) against the CUs left by the cycle's other launches.  Returns 0 (launched; *blocks: its workgroups), 1 (HIP
+// error), 3 (not launched: no proof of co-residency, or helpers turned off — the caller runs k_mem, which is exact and needs none).
+// 64 helper workgroups per launch at most (8 per XCD): C4's k_wide launch beside it keeps its 8 x 17 workgroups.
+constexpr u32 kGiantHelperBudget = 64;
+int launch_giant(cns_engine* h, const KParams& K, const LaunchCtx& L, std::string* name, u32* blocks) {
+  using W = w8::WideInfo;
+  if (h->giant_off || h->num_cus == 0 || L.max_np > W::giant_mem_slots) return 3;
+  const u32 nh = std::min<u32>(w8::kGiantHelpersMax, kGiantHelperBudget / std::max<u32>(L.nparts, 1));
+  if (nh < 4) return 3;
+  const void* fn = (const void*)w8::k_wide<1, false, w8::kWMemWordsGiant>;
+  const unsigned grid = L.nparts * (1u + nh);
+  size_t dyn = 0;
+  hipFuncAttributes fa;
+  if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.sharedSizeBytes < 84u * 1024u) {
+    dyn = 84u * 1024u - fa.sharedSizeBytes;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) { dyn = 0; (void)hipGetLastError(); }
+  }
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)W::block, dyn) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
+  if (per_cu < 1 || (u64)per_cu * h->num_cus < (u64)grid + L.other_blocks) return 3;
+  const size_t need = (size_t)h->P * W::ctl_bytes, gneed = (size_t)h->P * sizeof(w8::GiantCtl);
+  if (h->d_wide_mem.ensure(need) != hipSuccess || h->d_giant.ensure(gneed) != hipSuccess) return 1;
+  if (hipMemsetAsync(h->d_wide_mem.p, 0, need, L.stream) != hipSuccess || hipMemsetAsync(h->d_giant.p, 0, gneed, L.stream) != hipSuccess) return 1;
+  KParams K2 = K;
+  K2.wide_ctl = h->d_wide_mem.as<char>();
+  K2.serial_only = 1;
+  K2.giant_ctl = h->d_giant.as<char>();
+  K2.giant_nh = nh;
+  if (hipMemcpyAsync(const_cast<KParams*>(L.dparams), &K2, sizeof(KParams), hipMemcpyHostToDevice, L.stream) != hipSuccess) return 1;
+  const KParams* dparams = L.dparams;
+  void* args[2] = {(void*)&K2, (void*)&dparams};
+  if (hipLaunchKernel(fn, dim3(grid), dim3(W::block), args, dyn, L.stream) != hipSuccess) return 1;
+  *name = "k_giant (k_wide<1> home workgroup + " + std::to_string(nh) + " helper workgroups per partition, sequential protocol over the HBM arrays)";
+  *blocks = grid;
   return 0;
 }
 // Which selection kernel runs: k_pipe (decoupled test / commit pipeline) for partitions its tile covers, k_select
@@ -470,9 +529,9 @@ int finalize_layout(cns_engine* h, const std::vector<Res>* virt_total = nullptr)
   for (u32 q = h->S_real; q < S; ++q) h->slot_total[q] = (*virt_total)[q - h->S_real];
   for (u32 v = 0; v < h->V; ++v)
     for (u32 q = h->part_off[h->P_real + v]; q < h->part_off[h->P_real + v + 1]; ++q) h->slot_end[q] = h->resv_end[v];
-  // (per partition / group: checked in cns_set_nodes — a partition that shares no node may be as wide as k_wide's widest tile)
-  if (h->max_np > std::max<u32>(w8::WideInfo::mem_slots, w64::WideInfo::lanes * w64::WideInfo::npl_max))
-    return fail(h, CNS_ERR_UNSUPPORTED, "partition with more than " + std::to_string(std::max<u32>(w8::WideInfo::mem_slots, w64::WideInfo::lanes * w64::WideInfo::npl_max)) + " schedulable (partition, node) slots");
+  // (per partition / group: checked in cns_set_nodes, per reservation in cns_set_reservations — this is the backstop for k_mem's masks)
+  if (h->max_np > kGiantGroupSlots)
+    return fail(h, CNS_ERR_UNSUPPORTED, "partition with more than " + std::to_string(kGiantGroupSlots) + " schedulable (partition, node) slots");
   std::map<std::tuple<i64, u64, u64, u64, u64, u64, u64>, u32> tmap;
   std::vector<Res> type_total;
   std::vector<uint8_t> slot_type(std::max<u32>(S, 1), 0);
@@ -534,10 +593,13 @@ int finalize_layout(cns_engine* h, const std::vector<Res>* virt_total = nullptr)
   HIPCHK(h, h->d_dipt.ensure(S1 * sizeof(u32))); HIPCHK(h, h->d_dipcm.ensure(S1 * sizeof(u32))); HIPCHK(h, h->d_dipg.ensure(S1 * sizeof(u32)));
   if (h->shared) {
     HIPCHK(h, h->d_flen.ensure(S1 * sizeof(u32)));
-    std::vector<u32> tb = h->tag_base;
-    tb.resize(std::max<size_t>(h->P, 1), 0);   // (the virtual partitions of reservations share nothing: never read)
+    // the virtual partitions of reservations share nothing: one range over all of their slots (their jobs carry tag 0).  Read only by
+    // k_mem (a reservation wider than k_wide's tile); the other kernels take a partition without shared nodes whole.
+    std::vector<u32> tb = h->tag_base, to = h->tag_off;
+    tb.resize(std::max<size_t>(h->P, 1), 0);
+    for (u32 p = h->P_real; p < h->P; ++p) { tb[p] = (u32)to.size(); to.push_back(0); to.push_back(h->part_off[p + 1] - h->part_off[p]); }
     if (int rc = upload(h, h->d_tag_base, tb)) return rc;
-    if (int rc = upload(h, h->d_tag_off, h->tag_off)) return rc;
+    if (int rc = upload(h, h->d_tag_off, to)) return rc;
   }
   HIPCHK(h, h->d_first_resv.ensure(S1 * sizeof(i64)));
   HIPCHK(h, h->d_heap.ensure((size_t)(S + h->P + 1) * sizeof(HeapEnt)));
@@ -618,7 +680,7 @@ void cns_destroy(cns_handle* h) {
                     &h->d_slot_end, &h->d_slot_type, &h->d_rv_off, &h->d_rv_start, &h->d_rv_end, &h->d_rv_res,
                     &h->d_first_resv, &h->d_resv_se})
     b->release();
-  for (DevBuf* b : {&h->d_slot_block, &h->d_sib_off, &h->d_sib, &h->d_type_tag, &h->d_jtag, &h->d_params2, &h->d_pmap_a, &h->d_pmap_b, &h->d_wide_last, &h->d_params3, &h->d_pmap_c, &h->d_wide_mem, &h->d_flen, &h->d_tag_off, &h->d_tag_base}) b->release();
+  for (DevBuf* b : {&h->d_slot_block, &h->d_sib_off, &h->d_sib, &h->d_type_tag, &h->d_jtag, &h->d_params2, &h->d_pmap_a, &h->d_pmap_b, &h->d_wide_last, &h->d_params3, &h->d_pmap_c, &h->d_wide_mem, &h->d_giant, &h->d_flen, &h->d_tag_off, &h->d_tag_base}) b->release();
   for (PinBuf* b : {&h->h_place, &h->h_grouped, &h->h_reason, &h->h_jtag}) b->release();
   for (void* p : h->host_bufs) (void)hipHostFree(p);   // cns_host_alloc
   h->host_bufs.clear();
@@ -727,7 +789,7 @@ int cns_set_nodes(cns_handle* h, const cns_node_soa* nd) {
       for (u32 p : members[e]) if (part_bad[p] && !why) why = part_bad[p];
       u32 npe = 0;
       for (u32 p : members[e]) npe += (u32)plist[p].size();
-      const u32 cap = members[e].size() > 1 ? w8::WideInfo::mem_slots : std::max<u32>(kScan * (u32)CNS_NPL_MAX, w64::WideInfo::lanes * w64::WideInfo::npl_max);
+      const u32 cap = width_cap(members[e].size() > 1);
       if (!why && npe > cap) why = CNS_PART_REFUSED_WIDTH;
       if (!why) {
         auto mine = types;
@@ -777,8 +839,9 @@ int cns_set_nodes(cns_handle* h, const cns_node_soa* nd) {
   // share no node with another one run on it (groups run on k_select), and only while the device can hold its workgroups
   for (u32 e = 0; e < PE; ++e) {
     const u32 npe = part_off[e + 1] - part_off[e];
-    // (groups wider than k_select's tile run on k_wide's home workgroup alone, KParams::serial_only: launch_mem)
-    const u32 cap = members[e].size() > 1 ? w8::WideInfo::mem_slots : std::max<u32>(kScan * (u32)CNS_NPL_MAX, w64::WideInfo::lanes * w64::WideInfo::npl_max);
+    // (groups wider than k_select's tile, and partitions wider than k_wide's, run on k_wide's home workgroup alone,
+    // KParams::serial_only: launch_mem)
+    const u32 cap = width_cap(members[e].size() > 1);
     if (npe > cap)
       return fail(h, CNS_ERR_UNSUPPORTED, (members[e].size() > 1 ? "group of partitions sharing nodes with more than " : "partition with more than ") +
                                               std::to_string(cap) + " schedulable (partition, node) slots");
@@ -841,6 +904,7 @@ int cns_set_reservations(cns_handle* h, const cns_resv_soa* rv) {
     std::sort(al.begin(), al.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
     for (size_t i = 1; i < al.size(); ++i)
       if (al[i].first == al[i - 1].first) return fail(h, CNS_ERR_INVALID_ARG, "node listed twice in one reservation");
+    if (al.size() > kGiantPartSlots) return fail(h, CNS_ERR_UNSUPPORTED, "reservation over more than " + std::to_string(kGiantPartSlots) + " nodes");
     for (auto& [n, r] : al) {
       h->resv_node_slot[v][n] = (u32)h->slot_node.size();  // virtual node: its own NodeState (:6661-6664)
       h->slot_node.push_back(n);
@@ -1123,6 +1187,11 @@ static int run_resident_once(cns_handle* h, int64_t now, u32* fault_code) {
     // of the k_wide build (workgroups per partition), is sized by the busy partitions, not by the snapshot.
     // ... and a group of partitions that share nodes and is wider than k_select's register tile runs on k_wide's home workgroup
     // alone (launch_mem): the ordinary "ALL partition over the whole cluster" layout of a large site.
+    // CNS_SELECT_KERNEL=giant: every partition and group without preemption on k_giant (A/B runs against k_wide / k_select / k_mem);
+    // =mem: the shapes of k_giant on k_mem (19-word masks above 143 360 slots), helpers off
+    const char* ek = getenv("CNS_SELECT_KERNEL");
+    const bool force_giant = ek && !strcmp(ek, "giant"), force_mem = ek && !strcmp(ek, "mem");
+    bool giant_shape = false;   // a partition wider than k_wide's tile, or a group wider than k_mem's ordinary masks: k_giant
     std::vector<u32> pa, pb, pc;
     u32 npa = 0, npb = 0, npc = 0;
     for (u32 p = 0; p < h->P; ++p) {
@@ -1130,7 +1199,12 @@ static int run_resident_once(cns_handle* h, int64_t now, u32* fault_code) {
       const bool pre = h->pre_active && p < h->pre_part.size() && h->pre_part[p];
       const bool sel = (p < h->eng_members.size() && h->eng_members[p] > 1) || pre;
       const u32 np = h->part_off[p + 1] - h->part_off[p];
-      if (sel && np > kScan * (u32)CNS_NPL_MAX) {
+      // (a partition that shares no node and is wider than k_wide's widest tile: k_mem too — it needs no co-residency, and what the
+      // ordinary kernels hold stays on them)
+      const bool giant = !sel && np > w64::WideInfo::lanes * w64::WideInfo::npl_max;
+      giant_shape = giant_shape || giant || (sel && !pre && np > w8::WideInfo::mem_slots);
+      if (giant || (force_giant && !pre)) { pc.push_back(p); npc = std::max(npc, np); }
+      else if (sel && np > kScan * (u32)CNS_NPL_MAX) {
         if (pre) return fail(h, CNS_ERR_UNSUPPORTED, "preemption among the jobs of a partition (or group of partitions sharing nodes) with more than " +
                                                          std::to_string(kScan * (u32)CNS_NPL_MAX) + " (partition, node) slots");
         pc.push_back(p); npc = std::max(npc, np);
@@ -1138,6 +1212,7 @@ static int run_resident_once(cns_handle* h, int64_t now, u32* fault_code) {
       else { pa.push_back(p); npa = std::max(npa, np); }
     }
     std::string err, name_a, name_b, name_c;
+    u32 held_c = 0;
     if (!pc.empty()) {
       if (int rc = upload(h, h->d_pmap_c, pc)) return rc;
       HIPCHK(h, h->d_params3.ensure(sizeof(KParams)));
@@ -1147,10 +1222,13 @@ static int run_resident_once(cns_handle* h, int64_t now, u32* fault_code) {
       HIPCHK(h, hipEventRecord(h->ev2[0], h->stream));                  // tables + init kernels done: the second stream may start
       HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev2[0], 0));
       LaunchCtx LC{(u32)pc.size(), npc, h->stream2, h->d_params3.as<KParams>(), 0u};
-      if (launch_mem(h, KC, LC, &name_c)) return fail(h, CNS_ERR_HIP, "k_mem: control block allocation / upload / launch failed");
+      int rc = (giant_shape || force_giant) && !force_mem ? launch_giant(h, KC, LC, &name_c, &held_c) : 3;
+      if (rc == 3) { rc = launch_mem(h, KC, LC, &name_c); held_c = (u32)pc.size(); }
+      if (rc) return rc == 2 ? fail(h, CNS_ERR_UNSUPPORTED, "k_mem: a group wider than its giant row masks")
+                             : fail(h, CNS_ERR_HIP, "k_mem / k_giant: control block allocation / upload / launch failed");
       name_c += " on " + std::to_string(pc.size()) + " group(s) of up to " + std::to_string(npc) + " slots";
     }
-    const u32 held = (u32)pc.size();   // home workgroups of k_mem that hold a CU while the other launches run
+    const u32 held = held_c;   // workgroups of k_mem (its home workgroups) / k_giant that hold a CU while the other launches run
     if (pa.empty() && pb.empty()) {
       h->last_kernel = pc.empty() ? std::string("none (no pending job reaches an ordered loop)") : name_c;   // (never empty: callers parse it)
     } else if (pb.empty() || pa.empty()) {
@@ -1250,12 +1328,16 @@ int cns_run_resident(cns_handle* h, int64_t now) {
   // (CNS_WIDE_NO_RETRY=1: the fault fails the call — the GPU parity tests run that way, so that a k_wide that breaks is seen
   // and not papered over by the kernels behind it)
   const char* no_retry = getenv("CNS_WIDE_NO_RETRY");
-  if (rc == CNS_ERR_DEVICE_FAULT && code >= 20 && h->last_kernel.rfind("k_wide", 0) == 0 && !(no_retry && no_retry[0] == '1')) {
+  // (k_giant's helpers wait for the home and the home for them: a fault of that protocol, 43, is re-run the same way, on k_mem)
+  const bool protocol = h->last_kernel.rfind("k_wide", 0) == 0 || h->last_kernel.find("k_giant") != std::string::npos;
+  if (rc == CNS_ERR_DEVICE_FAULT && code >= 20 && protocol && !(no_retry && no_retry[0] == '1')) {
     const std::string first = h->err;
     h->wide_off = true;
+    h->giant_off = true;
     ++h->wide_retries;
     rc = run_resident_once(h, now, &code);
     h->wide_off = false;
+    h->giant_off = false;
     if (rc == CNS_OK) h->last_kernel += " (retry after: " + first + ")";
     else h->err = first + "; retry on " + h->last_kernel + ": " + h->err;
   }

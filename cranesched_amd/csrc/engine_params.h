@@ -219,6 +219,9 @@ struct KParams {
   const u32* sib_off;      // [S+1] the other slots of the same node (other partitions of the group) ...
   const u32* sib;          //       ... CSR
   const uint8_t* slot_tag; // [S] which partition of its group a slot belongs to (a job only sees the slots of its own partition)
+  // ---- k_giant (the serial-only mode of k_wide<1, false, kWMemWordsGiant> with helper workgroups, wide_kernel.inc) ------------
+  char* giant_ctl;         // [P] GiantCtl blocks (job word, one answer line per helper), zeroed before the launch
+  u32 giant_nh, pad_gnh;   // helper workgroups per partition (0: none — k_mem)
 };
 
 }  // namespace cns

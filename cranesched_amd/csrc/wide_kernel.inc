@@ -135,6 +135,8 @@ constexpr u32 kWNonePay = 0x3FFFFFFFu;         // payload "no node": code 0xFFFF
 constexpr u32 kWMs = (u32)kWTesters * 64u;     // memory-scanner lanes of a serial job
 constexpr u32 kWMemWords = 5;                  // ... each with up to 64 x kWMemWords rows: 448 x 320 = 143 360 slots (an ALL partition over 65 536 nodes
                                                // next to partitions that cover them once more = 131 072)
+constexpr u32 kWMemWordsGiant = 19;            // the giant instantiation of the serial-only mode (k_wide<1, false, kWMemWordsGiant>): 448 x 1 216 = 544 768
+                                               // slots >= 524 288 (an ALL partition over 262 144 nodes next to subsets that cover it once more)
 constexpr u32 kWSpinLimit = 1u << 22;          // polls of an exchange (>= ~0.5 us each): > 2 s without progress is a protocol bug
 constexpr u32 kWCmdSpinLimit = 1u << 23;       // polls for a command (the supervisor may be in a long serial job)
 constexpr u32 kWMaxParts = (32u / (u32)kWGroup) * 8u;   // (without extra homes; the host sizes KParams::wide_aux so that the launch still fits) every workgroup must be resident at once, and block b lands on XCD b % 8 (32 CUs, one workgroup each): 8 partitions at 17 workgroups, 24 at 9, 48 at 5, 80 at 3
@@ -575,19 +577,148 @@ __device__ __noinline__ void wide_test_task(const KParams* Pg, const WideHome sh
   TPROF_ADD(5, t8, t9);                                             // verdict + result into the slot
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// k_giant: the serial-only mode of the giant instantiation (k_wide<1, false, kWMemWordsGiant>) with HELPER workgroups
+// (KParams::giant_nh > 0, launch_giant).  A partition wider than k_wide's tile or a group wider than k_mem's ordinary masks
+// scans every slot of the job's partition per job; on the 448 memory-scanner lanes of the home alone that is ~1.9 ns per slot
+// (profiles/r07_giant_partitions.txt).  Here nh workgroups of 512 lanes each own a stripe of the job's slot range (lane gl of the
+// helpers: slots rb + gl, rb + gl + 512 nh, ...): per job they evaluate their rows exactly as the memory scanners do (eval_node,
+// own-partition tag, exclusive test) and answer with their stripe's lexicographic (cost key, slot) minimum of the start-now set
+// and of the res_total set.  The home reduces the answers: that is round 0 of the walk.  The walk goes on in the home alone: its
+// memory scanners build their row masks only when a job needs a second candidate (a failed exact test, node_num > 1, ntasks >
+// node_num) — the masks do not depend on round 0, so the walk is the one of k_mem, step for step.  Jobs with include / exclude
+// lists are scanned by the home itself.
+//   hand-off: home tester wave 1 -> helpers: the commits of earlier jobs (plain stores, drained) -> agent-scope release ->
+//   GiantCtl::job = seq << 32 | job; helpers: poll (wave 0, bounded) -> acquire -> plain loads of the arrays.  Helper -> home:
+//   its answer (agent-scope atomic stores) -> release -> tag = seq; home: poll the nh tags (bounded) -> atomic loads.
+// Workgroups land on any XCD: coherence is the agent scope's, not an L2's.  Every workgroup of the launch must be resident
+// (the host proves it with the occupancy figure, else k_mem runs); a home that waits for an answer longer than kGiantAnsSpin polls
+// raises device fault 43 and scans the job itself (exact; the host re-runs the cycle on k_mem).
+constexpr u32 kGiantHelpersMax = 64;           // helper workgroups per partition at most (one answer per lane of the home's tester wave 1)
+constexpr u32 kGiantExit = 0xFFFFFFFFu;        // GiantCtl::job >> 32: the home is done
+constexpr u32 kGiantAnsSpin = 1u << 22;        // home: polls for the helpers' answers to one job (> 1 s)
+constexpr u32 kGiantHelperSpin = 1u << 24;     // helper: polls for the next job (the home may scan a job with node lists alone meanwhile)
+struct GiantAns { u64 ac, tc; u32 ap, tp, tag, pad[9]; };   // one 64-byte line per helper
+struct GiantCtl { u64 job; u32 pad0[14]; GiantAns ans[kGiantHelpersMax]; };   // one per partition, zeroed before the launch
+static_assert(sizeof(GiantAns) == 64 && offsetof(GiantCtl, ans) == 64, "one line per word");
+
+// Slot p (relative to the partition) for the job: (a: start now, b: res_total fits); returns the cost key.  The body of the memory
+// scanners' row loop (mem_scan_serial), one slot at a time.
+__device__ __forceinline__ u64 giant_eval(const KParams& P, const FastJob& F, u64 tyok, u32 qbeg, u32 p, bool own_range, u32 jt, bool& a, bool& b) {
+  const u32 q = qbeg + p;
+  NodeSum ns;
+  ns.cost = 0; ns.code = p; ns.len = (P.serial_only && P.f_len) ? P.f_len[q] : hdr_of(P, q)->len; ns.type = P.slot_type[q];
+  ns.fcpu = P.f_cpu[q]; ns.fmem = P.f_mem[q]; ns.fcnt = P.f_cnt[q];
+  const u64 ck = cost_key(P.cost[q]);
+  const u32 tg = (P.slot_tag && !own_range) ? (u32)P.slot_tag[q] : jt;
+  eval_node(P, F.mv, F.flags, tyok, ns, b, a);
+  if (tg != jt) { b = false; a = false; }
+  if (F.flags & kJfExclusive) {
+    const Res tt = P.type_total[ns.type];
+    a = b && ns.fcpu >= clamp_cpu(tt.cpu) && ns.fmem >= mem_mib_ceil(tt.mem) && ns.fcnt == class_counts(tt.gres, P.gres);
+  }
+  return ck;
+}
+
+// Lexicographic (cost key, slot) minima of the start-now set (ac, ap) and the res_total set (tc, tp) over the slots
+// [rb + first, rb + rn) with stride `stride`, four slots per trip with every load in flight.
+__device__ __forceinline__ void giant_scan(const KParams& P, const FastJob& F, u64 tyok, u32 qbeg, u32 rb, u32 rn, bool own_range, u32 jt,
+                                           u32 first, u32 stride, u64& ac, u32& ap, u64& tc, u32& tp) {
+  ac = ~0ull; tc = ~0ull; ap = kNone; tp = kNone;
+  for (u32 o = first; o < rn; o += 4u * stride) {
+    bool a[4], b[4];
+    u64 ck[4];
+#pragma unroll
+    for (u32 u = 0; u < 4u; ++u) {
+      const u32 off = o + u * stride;
+      const bool in = off < rn;
+      ck[u] = giant_eval(P, F, tyok, qbeg, rb + (in ? off : 0u), own_range, jt, a[u], b[u]);
+      a[u] = a[u] && in; b[u] = b[u] && in;
+    }
+#pragma unroll
+    for (u32 u = 0; u < 4u; ++u) {   // (slots ascend and `<` is strict: the smallest slot among equal keys)
+      if (a[u] && ck[u] < ac) { ac = ck[u]; ap = rb + o + u * stride; }
+      if (b[u] && ck[u] < tc) { tc = ck[u]; tp = rb + o + u * stride; }
+    }
+  }
+}
+
+// The helper workgroup h of partition `part`: answers every job the home posts until the home's exit (or kGiantHelperSpin polls).
+__device__ __noinline__ void giant_helper(const KParams& P, u32 part, u32 qbeg, u32 nn, u64 jbeg, u32 h, u32 nh,
+                                          u64 (*s_wc)[kRed], u32 (*s_wp)[kRed], u64* s_tc, u32* s_tp, u32* s_cmd) {
+  GiantCtl* const gc = (GiantCtl*)(P.giant_ctl + (size_t)part * sizeof(GiantCtl));
+  const u32 tid = threadIdx.x, lane = tid & 63u, wave = uni32(tid >> 6);
+  const u32 stride = nh * (u32)kWBlock, gl = h * (u32)kWBlock + tid;
+  if (tid < (u32)kRed) { s_wc[0][tid] = ~0ull; s_wp[0][tid] = kNone; s_tc[tid] = ~0ull; s_tp[tid] = kNone; }
+  u32 seen = 0;
+  for (;;) {
+    if (wave == 0) {
+      u64 w = 0;
+      u32 sq = kGiantExit;
+      for (u32 spin = 0; spin < kGiantHelperSpin; ++spin) {
+        w = uni64(__hip_atomic_load(&gc->job, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if ((u32)(w >> 32) != seen) { sq = (u32)(w >> 32); break; }
+        __builtin_amdgcn_s_sleep(2);
+      }
+      if (lane == 0) { s_cmd[0] = sq; s_cmd[1] = (u32)w; }
+    }
+    __syncthreads();
+    const u32 sq = s_cmd[0], jl = s_cmd[1];
+    __syncthreads();
+    if (sq == kGiantExit) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const u32 raw = fetch_job(P, jbeg + jl);
+    const FastJob F = make_fast_job(P, raw);
+    const u64 tyok = jr64(raw, kJsTyok);
+    const bool own_range = P.serial_only && P.slot_tag && P.tag_off;
+    const u32 jt = (F.flags >> 8) & 0xFFu;
+    u32 rb = 0, rn = nn;
+    if (own_range) { const u32 tb = P.tag_base[part] + jt; rb = P.tag_off[tb]; rn = P.tag_off[tb + 1] - rb; }
+    u64 ac, tc;
+    u32 ap, tp;
+    giant_scan(P, F, tyok, qbeg, rb, rn, own_range, jt, gl, stride, ac, ap, tc, tp);
+    wave_argmin(ac, ap);
+    wave_argmin(tc, tp);
+    if (lane == 0) { s_wc[0][wave] = ac; s_wp[0][wave] = ap; s_tc[wave] = tc; s_tp[wave] = tp; }
+    __syncthreads();
+    if (wave == 0) {
+      u64 c1 = s_wc[0][lane & (kRed - 1)], c2 = s_tc[lane & (kRed - 1)];
+      u32 p1 = s_wp[0][lane & (kRed - 1)], p2 = s_tp[lane & (kRed - 1)];
+      reduce16(c1, p1);
+      reduce16(c2, p2);
+      if (lane == 0) {
+        GiantAns* const an = &gc->ans[h];
+        __hip_atomic_store(&an->ac, c1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&an->ap, p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&an->tc, c2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&an->tp, p2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __hip_atomic_store(&an->tag, sq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    seen = sq;
+  }
+}
+
 // kWinK: the instantiation that carries the window path ("A WINDOW OF JOBS PER EXCHANGE").  A kernel of its own because the path's mere
 // presence costs the single-job loops ~8 % (C4 280 against 258 ms: registers and code layout of one big function,
 // profiles/r05_ab_window_code_presence.txt); the engine launches it when a window may hold two jobs or more (KParams::wide_window).
-template <int NPL, bool kWinK = false>
+// MW: 64-bit words per memory-scanner lane in each row mask of the serial-only mode (kWMemWords everywhere but in the one instantiation
+// that serves groups wider than that: k_wide<1, false, kWMemWordsGiant>, launch_mem).
+template <int NPL, bool kWinK = false, u32 MW = kWMemWords>
 __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams* __restrict__ Pg) {
   const KParams& PG = *Pg;
+  constexpr bool kGiantMW = MW == kWMemWordsGiant;
+  const u32 gnh = kGiantMW ? P.giant_nh : 0u;  // k_giant: helper workgroups per partition (0: k_mem)
+  const u32 nlaunch = P.part_map ? P.launch_parts : P.num_parts;
   // block b runs on XCD b % 8 (observed; speed only): all workgroups of a partition share b % 8
   const u32 bslot = blockIdx.x >> 3;
   const u32 grp = (u32)kWGroup + (P.wide_aux < kWAuxMax ? P.wide_aux : kWAuxMax);   // workgroups per partition of THIS launch
-  const u32 pidx = (bslot / grp) * 8u + (blockIdx.x & 7u);   // position among the partitions of THIS launch
-  const u32 m = bslot % grp;                   // 0: home, 1..8: scanner workgroups, behind them: the extra home workgroups
-  const bool home = m == 0u || m > (u32)kWScanWgs;
-  const u32 hix = m > (u32)kWScanWgs ? m - (u32)kWScanWgs : 0u;   // which home (0: the one that talks to the scanners)
+  // (k_giant: the home of partition i is block i, its helper h block (h + 1) * nlaunch + i)
+  const u32 pidx = gnh ? blockIdx.x % nlaunch : (bslot / grp) * 8u + (blockIdx.x & 7u);   // position among the partitions of THIS launch
+  const u32 m = gnh ? blockIdx.x / nlaunch : bslot % grp;   // 0: home, 1..8: scanner workgroups, behind them: the extra home workgroups (k_giant: 1 + helper)
+  const bool home = m == 0u || (m > (u32)kWScanWgs && !gnh);
+  const u32 hix = (m > (u32)kWScanWgs && !gnh) ? m - (u32)kWScanWgs : 0u;   // which home (0: the one that talks to the scanners)
   if (pidx >= (P.part_map ? P.launch_parts : P.num_parts)) return;
   const u32 part = P.part_map ? uni32(P.part_map[pidx]) : pidx;   // (a cycle may be split over two launches: KParams::part_map)
   const u32 tid = threadIdx.x, lane = tid & 63u;
@@ -599,7 +730,7 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
   const u32 nn = uni32(P.part_off[part + 1]) - qbeg;
   const u64 jbeg = uni64(P.pj_off[part]), jend = uni64(P.pj_off[part + 1]);
   if (jbeg >= jend) return;
-  if (P.serial_only && m != 0) return;   // (the home workgroup does everything: see the supervisor)
+  if (P.serial_only && m != 0 && !gnh) return;   // (the home workgroup does everything: see the supervisor; k_giant: and its helpers)
   const bool resv_part = part >= P.num_real_parts;
   if (resv_part) {  // a reservation's scheduler exists only while the reservation is active (JobScheduler.cpp:6643,6754-6759)
     const i64 rs = P.resv_se[2 * (part - P.num_real_parts)], re = P.resv_se[2 * (part - P.num_real_parts) + 1];
@@ -684,6 +815,9 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
     }
   }
   __syncthreads();
+  if constexpr (kGiantMW) {
+    if (gnh && m != 0u) { giant_helper(P, part, qbeg, nn, jbeg, m - 1u, gnh, s_wc, s_wp, s_tc, s_tp, s_cmd); return; }
+  }
   if (!home && wave >= (u32)kWScanPerWg) {   // scanner workgroups: one wave per SIMD
 #if !defined(CNS_WIDE_NO_PREFETCH) && !defined(CNS_PROF)
     // One of the spare waves follows the DECISION ring and touches the node block of every selected node (header + the first entries:
@@ -927,6 +1061,8 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
         ++n_ser;
       }
       if (vld(&s_abort) && lane == 0) gst(&ctl->abort, 1u);
+      if (gnh && lane == 0)   // k_giant: the helpers leave
+        __hip_atomic_store(&((GiantCtl*)(P.giant_ctl + (size_t)part * sizeof(GiantCtl)))->job, (u64)kGiantExit << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (lane == 0) P.prof[(size_t)P.num_parts * 32 + (size_t)part * kWsSlots + kWsSerial] = n_ser;
       post_lcmd(kPcExit, 0);
       return;
@@ -1270,13 +1406,15 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
     psh.tp = (tw == 0 && hix == 0u) ? P.prof + (size_t)part * 32 : nullptr;
 #endif
     const u32 ml = tw * 64u + lane;
-    const u32 mrows = (nn + kWMs - 1u) / kWMs;   // rows of a memory-scanner lane: 37 for 16 384 nodes, 147 for 65 536
-    constexpr u32 kMW = kWMemWords;              // ... one bit per row in kMW 64-bit words (scratch: these masks are not on any fast path)
+    const u32 mrows = (nn + kWMs - 1u) / kWMs;   // rows of a memory-scanner lane: 37 for 16 384 nodes, 147 for 65 536, 1 171 for 524 288
+    constexpr u32 kMW = MW;                      // ... one bit per row in kMW 64-bit words (scratch: these masks are not on any fast path)
     struct MMask { u64 w[kMW]; };
     const u32 mwords = (mrows + 63u) >> 6;
     // (serial-only mode, shared nodes: a job scans only the slots of its OWN partition — a contiguous range [rb, rb + rn) of the
     // group, KParams::tag_off; else the whole partition: rb = 0, rn = nn.  Row r of lane ml is slot rb + r * kWMs + ml.)
     u32 rb = 0, rn = nn, jrows = mrows, jwords = mwords;
+    u32 gseq = 0;          // k_giant (tester wave 1): jobs posted to the helpers
+    bool gdead = false;    // ... a helper's answer did not come: device fault 43, every later job scanned by the home
     auto margmin = [&](const MMask& mask, const MMask* minus, u64& bc, u32& bp) {   // lexicographic (cost key, slot) over the lane's rows in `mask` (and not in `minus`)
       bc = ~0ull; bp = kNone;
       for (u32 w = 0; w < jwords; ++w) {
@@ -1314,6 +1452,12 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
       const u32 jt = (F.flags >> 8) & 0xFFu;
       u64 ac = ~0ull, tcs = ~0ull;
       u32 ap = kNone, tp = kNone;
+      // The bits of the mask word under way collect in registers and go to the scratch masks once per word (a trip's four rows never
+      // straddle a word: 64 % 4 == 0): a read-modify-write of scratch per row and mask kept every trip waiting on the last one.
+      const bool hjob = gnh != 0u && !(F.flags & (kJfIncl | kJfExcl));   // k_giant: round 0 comes from the helpers
+      bool built = !hjob;                                                // the row masks of this job exist
+      auto scan_rows = [&]() {
+      u64 wb = 0, wa = 0;
       for (u32 r0 = 0; r0 < jrows; r0 += 4u) {
         u32 vlen[4], vty[4], vtg[4], vfmem[4];
         int vfcpu[4];
@@ -1345,10 +1489,42 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
             const Res tt = P.type_total[ns.type];
             a = b && ns.fcpu >= clamp_cpu(tt.cpu) && ns.fmem >= mem_mib_ceil(tt.mem) && ns.fcnt == class_counts(tt.gres, P.gres);
           }
-          bmask.w[r >> 6] |= (u64)(b ? 1u : 0u) << (r & 63u);
-          amask.w[r >> 6] |= (u64)(a ? 1u : 0u) << (r & 63u);
+          wb |= (u64)(b ? 1u : 0u) << (r & 63u);
+          wa |= (u64)(a ? 1u : 0u) << (r & 63u);
           if (a && vck[u] < ac) { ac = vck[u]; ap = pr; }
           if (b && vck[u] < tcs) { tcs = vck[u]; tp = pr; }
+        }
+        if (((r0 + 4u) & 63u) == 0u || r0 + 4u >= jrows) { bmask.w[r0 >> 6] = wb; amask.w[r0 >> 6] = wa; wb = 0; wa = 0; }
+      }
+      };
+      if (!hjob) scan_rows();
+      if constexpr (kGiantMW) {
+        if (hjob && tw == 0u) {   // tester wave 1: post the job, collect the helpers' answers (lane i: helper i), reduce below
+          GiantCtl* const gc = (GiantCtl*)(P.giant_ctl + (size_t)part * sizeof(GiantCtl));
+          if (!gdead) {
+            ++gseq;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // (every commit of the earlier jobs is drained: S1, S0)
+            if (lane == 0) __hip_atomic_store(&gc->job, ((u64)gseq << 32) | jl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            bool ok = false;
+            for (u32 spin = 0; spin < kGiantAnsSpin; ++spin) {
+              const u32 t = lane < gnh ? __hip_atomic_load(&gc->ans[lane].tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : gseq;
+              if (!__any(t != gseq)) { ok = true; break; }
+              __builtin_amdgcn_s_sleep(1);
+            }
+            if (ok) {
+              __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+              if (lane < gnh) {
+                ac = __hip_atomic_load(&gc->ans[lane].ac, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ap = __hip_atomic_load(&gc->ans[lane].ap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                tcs = __hip_atomic_load(&gc->ans[lane].tc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                tp = __hip_atomic_load(&gc->ans[lane].tp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              }
+            } else {
+              if (lane == 0) set_fault(P, 43, jl, gseq, gnh);
+              gdead = true;
+            }
+          }
+          if (gdead) giant_scan(P, F, tyok, qbeg, rb, rn, own_range, jt, lane, 64u, ac, ap, tcs, tp);   // exact, one wave
         }
       }
       if (F.flags & (kJfIncl | kJfExcl)) {  // included / excluded node lists (rare)
@@ -1401,6 +1577,7 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
         }
         u64 c = ~0ull;
         u32 pc = kNone;
+        if (!built) { scan_rows(); built = true; }   // k_giant: the walk needs a second candidate
         margmin(phase_b ? bmask : amask, &used, c, pc);
         wave_argmin(c, pc);
         if (lane == 0) { s_wc[par][wave] = c; s_wp[par][wave] = pc; }
@@ -2692,6 +2869,9 @@ CNS_WNPL_LIST(CNS_WIDE_INSTANTIATE)
 template __global__ void k_wide<1, true>(const KParams, const KParams*);
 template __global__ void k_wide<2, true>(const KParams, const KParams*);
 #endif
+#if CNS_WIDE_SPW * CNS_WIDE_WGS == 8
+template __global__ void k_wide<1, false, kWMemWordsGiant>(const KParams, const KParams*);   // launch_mem above mem_slots
+#endif
 
 // Host side: what engine.hip needs to know about this build of the kernel (the file is included once per scanner-wave
 // count, each time inside its own namespace).
@@ -2701,6 +2881,7 @@ struct WideInfo {
   static constexpr u32 last_in_lds_rows = 4;    // ... which need the last-task table in LDS: tiles of up to 4 rows per lane
   static constexpr size_t ctl_bytes = sizeof(WideCtl);
   static constexpr u32 mem_slots = kWMs * 64u * kWMemWords;   // widest group the serial-only mode (KParams::serial_only) scans
+  static constexpr u32 giant_mem_slots = kWMs * 64u * kWMemWordsGiant;   // ... and its giant instantiation (the 8-wave build only)
   // the narrowest tile that holds `np` nodes per partition: the kernel and its name (nullptr: none)
   static const void* pick(u32 np, const char** name, bool windows = false) {
 #ifdef CNS_WIDE_WINDOWS
