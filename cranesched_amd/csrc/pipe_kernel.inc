@@ -164,8 +164,9 @@ __device__ __forceinline__ bool pipe_wait_verdicts(const KParams& P, const PipeS
 // Commit of one node of a task from the tester's registers: NodeState::UpdateResourceInNode (JobScheduler.h:340-459),
 // MinCpuTimeRatioFirst::UpdateCost (h:47-53), the HBM arrays the scanners reload from, and the placement record.
 template <bool kW = true>
-// (Pmem: the parameter block for the out-of-line routine of maps longer than 64 entries, G: the GRES layout — both P's own)
-__device__ __forceinline__ void pipe_commit_node(const KParams& P, const KParams& Pmem, const GresDev& G, const PipeShared& sh, NodeHdr* hd, const NodeHdr& h,
+// (Pmem: the parameter block for the out-of-line routine of maps longer than 64 entries, G: the GRES layout — both P's own;
+// abort: the LDS word that tells every wave of the workgroup to leave)
+__device__ __forceinline__ void pipe_commit_node(const KParams& P, const KParams& Pmem, const GresDev& G, u32* abort, NodeHdr* hd, const NodeHdr& h,
                                                  const TlEntry& e, u32 q, u64 cost0, const Res& alloc, i64 start, i64 L,
                                                  u32 orig, u64 rec, u32 lane) {
   const i64 end = start + L;   // job->end_time = start_time + time_limit, JobScheduler.cpp:6772
@@ -180,7 +181,7 @@ __device__ __forceinline__ void pipe_commit_node(const KParams& P, const KParams
       u64* const dbg = P.prof + (size_t)P.num_parts * 48 + 2040;
       dbg[0] = cost0; dbg[1] = cost_key(P.cost[q]); dbg[2] = ((u64)orig << 32) | h.node; dbg[3] = (u64)start; dbg[4] = (u64)alloc.cpu; dbg[5] = (u64)h.total.cpu; dbg[6] = (u64)L;
 #endif
-      set_fault(P, 22, orig, h.node, 0); vst(sh.abort, 1u);
+      set_fault(P, 22, orig, h.node, 0); vst(abort, 1u);
     }
     P.cost[q] = ncost;
     if (start == P.now) {
@@ -212,7 +213,7 @@ __device__ __noinline__ void pipe_tester_task(const KParams* Pg, const PipeShare
   const u32 maxlen = P.max_jobs_per_node;
   bool ok = true;
   i64 st = P.now;
-  int reason = 0;
+  int reason = CNS_REASON_NONE;
   NodeHdr* hd = nullptr; NodeHdr h; TlEntry e;
   Res alloc = res_zero();
   u32 q = 0;
@@ -228,26 +229,14 @@ __device__ __noinline__ void pipe_tester_task(const KParams* Pg, const PipeShare
     load_block<kW>(P, q, lane, hd, h, e);
     ok = h.len < maxlen;                                            // :6194 on the CURRENT map (the tile's length may be stale)
     if (ok && kind == kPkStart) {
-      // :6285 on the window minimum; it implies :6274 except for the core-id count of res_avail (see k_select)
-      const Res m = uni_res(narrow<kW>(h.len <= 64 ? window_min_regs(e, lane < h.len, h.avail0, F.E)
-                                                  : window_min(tl_of<kW>(P, hd), h.len, h.avail0, F.E, lane)));   // :6278-6283
-      ok = feasible(F.mv, m, alloc, G);
-      if (ok) {
-        const i64 req_int = F.mv.cpu / 256;
-        const u32 nc0 = cores_count(h.avail0);
-        if (req_int * 256 == F.mv.cpu && nc0 != 0 && nc0 < (u32)req_int) ok = false;           // :528-534 on res_avail
-      }
+      ok = fits_now(F.mv, block_window_min<kW>(P, hd, h, e, F.E, lane), h.avail0, alloc, G);
     } else if (ok) {
       // backfill on the first node in cost order whose res_total fits (:6335-6368, Backfill_ :6371-6376)
       if (!feasible(F.mv, h.total, alloc, G)) { pipe_fault(P, sh, 3, F.orig, h.node, 0); return; }
       alloc = uni_res(alloc);
-      st = h.len <= 64 ? next_fit_regs(e, h.len, alloc, F.L, P.now, lane) : next_fit_wave(tl_of<kW>(P, hd), h.len, &alloc, F.L, P.now);
+      st = block_next_fit<kW>(P, hd, h, e, alloc, F.L, P.now, lane);
       ok = st != kInf && st - P.now <= P.max_window;                // kAlgoMaxTimeWindow, JobScheduler.h:815
-      if (ok && st != P.now) {                                      // :6797-6831
-        const i64 first_resv = resv_part ? kInf : P.first_resv[q];
-        if (first_resv < P.now + F.L) reason = 3;                   // "Resource Reserved"
-        else reason = res_le(alloc, h.avail0) ? 1 /*Priority*/ : 2 /*Resource*/;
-      }
+      if (ok && st != P.now) reason = later_start_reason(!resv_part && P.first_resv[q] < P.now + F.L, !res_le(alloc, h.avail0));
     }
   } else {
     // node_num 2..8, ntasks == node_num: the nodes one after the other (the task is off the sequential chain)
@@ -260,14 +249,7 @@ __device__ __noinline__ void pipe_tester_task(const KParams* Pg, const PipeShare
       if (h.len >= maxlen) { ok = false; break; }
       Res a = res_zero();
       if (kind == kPkStart) {
-        const Res m = uni_res(narrow<kW>(h.len <= 64 ? window_min_regs(e, lane < h.len, h.avail0, F.E)
-                                                    : window_min(tl_of<kW>(P, hd), h.len, h.avail0, F.E, lane)));
-        ok = feasible(v1, m, a, G);
-        if (ok) {
-          const i64 req_int = v1.cpu / 256;
-          const u32 nc0 = cores_count(h.avail0);
-          if (req_int * 256 == v1.cpu && nc0 != 0 && nc0 < (u32)req_int) ok = false;
-        }
+        ok = fits_now(v1, block_window_min<kW>(P, hd, h, e, F.E, lane), h.avail0, a, G);
       } else {
         if (!feasible(v1, h.total, a, G)) { pipe_fault(P, sh, 3, F.orig, h.node, 2); return; }   // :6354-6356
         notle = notle || !res_le(a, h.avail0);
@@ -277,24 +259,12 @@ __device__ __noinline__ void pipe_tester_task(const KParams* Pg, const PipeShare
     }
     lds_fence();
     if (ok && kind == kPkBackfill) {
-      // EarliestStartSubsetSelector::CalcEarliestStartTime as the fixed point t <- max_i next_fit_i(t) (see k_select)
-      i64 t = P.now;
-      bool found = false;
-      for (u32 iter = 0; iter < (1u << 20); ++iter) {
-        i64 Tm = t;
-        for (u32 i = 0; i < k; ++i) {
-          load_block<kW>(P, qbeg + slot_of_code_t<kS>(vld(&T->code[i])), lane, hd, h, e);
-          const Res a = uni_res(narrow<kW>(ares[i]));
-          const i64 s = h.len <= 64 ? next_fit_regs(e, h.len, a, F.L, t, lane) : next_fit_wave(tl_of<kW>(P, hd), h.len, &ares[i], F.L, t);
-          Tm = s > Tm ? s : Tm;
-        }
-        if (Tm == kInf || Tm - P.now > P.max_window) break;
-        if (Tm == t) { found = true; break; }
-        t = Tm;
-      }
-      ok = found;
-      st = t;
-      if (ok && st != P.now) reason = reserved ? 3 : (notle ? 2 : 1);
+      st = earliest_start(P, k, [&](u32 i, i64 t) {
+        load_block<kW>(P, qbeg + slot_of_code_t<kS>(vld(&T->code[i])), lane, hd, h, e);
+        return block_next_fit<kW>(P, hd, h, e, ares[i], F.L, t, lane);
+      });
+      ok = st != kInf;
+      if (ok && st != P.now) reason = later_start_reason(reserved, notle);
     }
   }
 
@@ -312,7 +282,7 @@ __device__ __noinline__ void pipe_tester_task(const KParams* Pg, const PipeShare
 
   // ---- commit (every older task has a passing verdict: the selections up to here were right) ------------------
   if (k == 1) {
-    pipe_commit_node<kW>(P, *Pg, G, sh, hd, h, e, q, ((u64)vld((u32*)&T->cost0[0] + 1) << 32) | vld((u32*)&T->cost0[0]), alloc, st, F.L,
+    pipe_commit_node<kW>(P, *Pg, G, sh.abort, hd, h, e, q, ((u64)vld((u32*)&T->cost0[0] + 1) << 32) | vld((u32*)&T->cost0[0]), alloc, st, F.L,
                      F.orig, F.poff, lane);
   } else {
     for (u32 i = 0; i < k; ++i) {
@@ -321,7 +291,7 @@ __device__ __noinline__ void pipe_tester_task(const KParams* Pg, const PipeShare
       u32 rank = 0;  // placement records are listed by ascending node index
       for (u32 m = 0; m < k; ++m) rank += anode[m] < h.node ? 1u : 0u;
       const u64 c0 = ((u64)vld((u32*)&T->cost0[i] + 1) << 32) | vld((u32*)&T->cost0[i]);
-      pipe_commit_node<kW>(P, *Pg, G, sh, hd, h, e, qi, c0, uni_res(narrow<kW>(ares[i])), st, F.L, F.orig, F.poff + rank, lane);
+      pipe_commit_node<kW>(P, *Pg, G, sh.abort, hd, h, e, qi, c0, uni_res(narrow<kW>(ares[i])), st, F.L, F.orig, F.poff + rank, lane);
     }
   }
   if (lane == 0) { P.o_start[F.orig] = st; P.o_reason[F.orig] = (uint8_t)reason; }
@@ -347,7 +317,7 @@ __global__ __launch_bounds__(kPBlock) void k_pipe(const KParams P, const KParams
       for (u64 x = jbeg + tid; x < jend; x += kPBlock) {
         const u32 orig = P.jobrec[x * kJobRecDwords + kJrOrig];
         P.o_start[orig] = 0;
-        P.o_reason[orig] = 6;  // "Reservation Not Found"
+        P.o_reason[orig] = CNS_REASON_RESERVATION_NOT_FOUND;
       }
       return;
     }
@@ -592,7 +562,7 @@ __global__ __launch_bounds__(kPBlock) void k_pipe(const KParams P, const KParams
       reduce16(tc, tcode);
       par ^= 1;
       wc = uni64(wc); wcode = uni32(wcode); tc = uni64(tc); tcode = uni32(tcode);
-      par = worker_job_slow<kPScan>(PG, sh, &s_job, par, wc, wcode, tc, tcode, qbeg, gheap);
+      par = worker_job_slow<kPScan, false>(PG, sh, &s_job, par, wc, wcode, tc, tcode, qbeg, gheap);
       drain_stores();
       wg_barrier();  // S1
       PROF_T(sj1);
@@ -652,7 +622,7 @@ __global__ __launch_bounds__(kPBlock) void k_pipe(const KParams P, const KParams
           if (nfound != k) {
             // not even k nodes whose res_total fits: "Resource" (:6335-6343, :6768); nothing changes
             const u32 orig = rl32(raw, kJrOrig);
-            if (lane == 0) { P.o_start[orig] = 0; P.o_reason[orig] = 2; }
+            if (lane == 0) { P.o_start[orig] = 0; P.o_reason[orig] = CNS_REASON_RESOURCE; }
           } else {
             const u32 id = nposted + 1;
             PROF_T(f0);

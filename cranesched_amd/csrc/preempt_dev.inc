@@ -818,7 +818,7 @@ __device__ __noinline__ u32 pre_release(const KParams& P, const JobCtx& J, u32 q
         release_on(q, st, en, r);
         if (scheduled && lane == 0) Q.rec_gone[rec] = 1;
       }
-      if (lane == 0) P.o_reason[idx] = 7;                              // "Preempted", cpp:6783
+      if (lane == 0) P.o_reason[idx] = CNS_REASON_PREEMPTED;           // cpp:6783
     } else {
       const i64 en = Q.rj_end[idx];
       for (u32 x = Q.rj_off[idx]; x < Q.rj_off[idx + 1]; ++x) {

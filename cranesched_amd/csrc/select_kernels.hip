@@ -943,6 +943,69 @@ __device__ __forceinline__ i64 next_fit_regs(const TlEntry& e, u32 len, const Re
   return w == idx0 ? t0 : (i64)rl64((u64)e.t, w);
 }
 
+// ---- the rules of GetNodesAndTrySchedule_ that every tester and worker routine applies to a node -----------------------------
+// The block arguments (hd, h, e) are what load_block leaves: header scalarised, lane i <- entry i of the time map.
+
+// kW = false instantiations of the tester / commit functions of k_pipe and k_wide serve snapshots WITHOUT core ids above 127
+// (KParams::wide_cores == 0, chosen once per call by a scalar branch): every Res that enters them from memory has its upper
+// two core words replaced by the constant 0, so the compiler folds their arithmetic, their registers and their loads away —
+// those clusters run the code they ran before ABI 3 (the 4-word Res cost the testers of C4 +26 % per test otherwise).
+template <bool kW> __device__ __forceinline__ Res narrow(Res r) { if (!kW) { r.c2 = 0; r.c3 = 0; } return r; }
+
+// The window minimum of a loaded node block (:6278-6283), wave-uniform.
+template <bool kW = true>
+__device__ __forceinline__ Res block_window_min(const KParams& P, NodeHdr* hd, const NodeHdr& h, const TlEntry& e, i64 E, u32 lane) {
+  return uni_res(narrow<kW>(h.len <= 64 ? window_min_regs(e, lane < h.len, h.avail0, E)
+                                        : window_min(tl_of<kW>(P, hd), h.len, h.avail0, E, lane)));
+}
+
+// Can the node start the job now, given its window minimum m?  alloc: the allocation on m.
+// :6274 wants GetFeasibleResourceInNode(res_avail) to succeed, :6285 the same on the window minimum m.  m is res_avail folded
+// with Ckmin (:6278-6283): cpu and mem are minima, GRES slots and (when non-empty) core ids are subsets.  So success on m implies
+// the cpu, mem and GRES tests of :6274; the one test of :6274 that m does not imply is the core-id count of res_avail (:534) when
+// m's core set came out empty.
+__device__ __forceinline__ bool fits_now(const Req& mv, const Res& m, const Res& avail0, Res& alloc, const GresDev& G) {
+  if (!feasible(mv, m, alloc, G)) return false;                    // get_max_tasks(min_res) > 0, :6285
+  const i64 req_int = mv.cpu / 256;
+  const u32 nc0 = cores_count(avail0);
+  return !(req_int * 256 == mv.cpu && nc0 != 0 && nc0 < (u32)req_int);   // :528-534 on res_avail
+}
+
+// The earliest start >= t0 at which `alloc` fits the loaded node block for L seconds (kInf: none).  alloc may sit in LDS: the
+// register form takes a scalar copy, the general form reads it through its address (a copy would go through scratch).
+template <bool kW = true>
+__device__ __forceinline__ i64 block_next_fit(const KParams& P, NodeHdr* hd, const NodeHdr& h, const TlEntry& e, const Res& alloc,
+                                              i64 L, i64 t0, u32 lane) {
+  return h.len <= 64 ? next_fit_regs(e, h.len, uni_res(narrow<kW>(alloc)), L, t0, lane) : next_fit_wave(tl_of<kW>(P, hd), h.len, &alloc, L, t0);
+}
+
+// EarliestStartSubsetSelector::CalcEarliestStartTime over k nodes as the fixed point t <- max_i next_fit(i, t), from t = now;
+// next_fit(i, t) is node i's earliest fit at or after t.  Returns the start, or kInf when there is none inside kAlgoMaxTimeWindow.
+// Each step moves t to a later entry of one of the k time maps (at most kTlCap entries each), so no run takes more than
+// k * kTlCap steps; the bound only guards against a broken map (multi_backfill_par applies the same bound and termination test).
+template <class NextFit>
+__device__ __forceinline__ i64 earliest_start(const KParams& P, u32 k, NextFit next_fit) {
+  i64 t = P.now;
+  for (u32 iter = 0; iter < (1u << 22); ++iter) {
+    i64 Tm = t;
+    for (u32 i = 0; i < k; ++i) {
+      const i64 s = next_fit(i, t);
+      Tm = s > Tm ? s : Tm;
+    }
+    if (Tm == kInf || Tm - P.now > P.max_window) break;  // kAlgoMaxTimeWindow, JobScheduler.h:815
+    if (Tm == t) return t;
+    t = Tm;
+  }
+  return kInf;
+}
+
+// The reason of a start later than now (:6797-6831): "Resource Reserved" when a reservation begins on one of the nodes inside the
+// job's run (never for the jobs of a reservation: :6798, :6818), else "Resource" when the allocation exceeds res_avail on one of
+// them, else "Priority".
+__device__ __forceinline__ int later_start_reason(bool reserved, bool notle) {
+  return reserved ? CNS_REASON_RESOURCE_RESERVED : (notle ? CNS_REASON_RESOURCE : CNS_REASON_PRIORITY);
+}
+
 // Shared by the "start now" and "backfill" endings of the general path: H[0..k) holds the selected
 // nodes with their assigned task counts and allocations; commits them into the time maps and costs,
 // emits the placement records (sorted by node index) and the owner updates.
@@ -1244,8 +1307,8 @@ __device__ __forceinline__ bool post_dip(const KParams& P, const GresDev& G, int
 // Out-of-line worker path for everything that is not "node_num == 1, ntasks == 1, shared node":
 // multi-node jobs, ntasks > node_num (priority_queue emulation) and exclusive jobs.  Enters after the
 // round-0 barrier with the A and T winners, leaves after the job's last barrier; returns the LDS
-// double-buffer parity.
-template <u32 kS = kScan>
+// double-buffer parity.  kSelect: the caller is k_select (true) or k_pipe / k_wide (false); kS alone does not tell them apart.
+template <u32 kS, bool kSelect>
 __device__ __noinline__ int worker_job_slow(const KParams& Pm, const WorkerShared sh, const JobCtx* Jp, int par,
                                             u64 wc, u32 wcode, u64 tc, u32 tcode, u32 qbeg, HeapEnt* gheap) {
   const auto& P = kparams_scalar(&Pm);   // (Pm: the block's copy in HBM — what the out-of-line routines and the GRES tables are given)
@@ -1312,11 +1375,11 @@ __device__ __noinline__ int worker_job_slow(const KParams& Pm, const WorkerShare
       if (hsize == (int)J.k && (u32)hsum >= J.ntasks) {                   // :6294-6297
         if (!distribute_and_alloc(Pm, J, H, lane)) { if (lane == 0) set_fault(P, 2, orig, n, 2); }
         commit_selection<kS>(Pm, J, H, qbeg, P.now, lane, s_upd, s_nupd);      // start_time = now (:6326)
-        if (lane == 0) { P.o_start[orig] = P.now; P.o_reason[orig] = 0; }
+        if (lane == 0) { P.o_start[orig] = P.now; P.o_reason[orig] = CNS_REASON_NONE; }
         code = 2;
       }
     }
-    if constexpr (kS == kScan) {   // (k_select's scanners alone read the dip words: post_dip)
+    if constexpr (kSelect) {   // (k_select's scanners alone read the dip words: post_dip)
       if (!ok && !excl_job && len <= 64) {
         TlEntry e;
         e.t = kInf;
@@ -1400,7 +1463,7 @@ __device__ __noinline__ int worker_job_slow(const KParams& Pm, const WorkerShare
       // (only k_select runs cycles with preemption, and only its instantiation reaches g_pre_cache: the 100 KB of LDS are allocated
       // in k_select's kernels alone — a pointer through WorkerShared cost every kernel two more argument registers at each call of
       // an out-of-line worker routine, and k_select its spill-free allocation)
-      if constexpr (kS == kScan) nch = pre_try<kS>(Pm, J, H, qbeg, sh.part, &pf);
+      if constexpr (kSelect) nch = pre_try<kS>(Pm, J, H, qbeg, sh.part, &pf);
       else pf = 33;
       if (pf && lane == 0) set_fault(P, pf, orig, J.k, 0);
       if (nch >= 0) {
@@ -1442,29 +1505,18 @@ __device__ __noinline__ int worker_job_slow(const KParams& Pm, const WorkerShare
               ++nup;
             }
         }
-        if (lane == 0) { *s_nupd = (int)nup; P.o_start[orig] = P.now; P.o_reason[orig] = 0; }
+        if (lane == 0) { *s_nupd = (int)nup; P.o_start[orig] = P.now; P.o_reason[orig] = CNS_REASON_NONE; }
         code = 2;
         preempted = true;
       }
     }
-    // EarliestStartSubsetSelector::CalcEarliestStartTime as a fixed point over the k nodes
-    i64 t = P.now;
-    bool found = false;
-    for (u32 iter = 0; iter < (1u << 22) && !preempted; ++iter) {
-      i64 Tm = t;
-      for (u32 i = 0; i < J.k; ++i) {
-        const HeapEnt x = H[i];
-        NodeHdr* hd = hdr_of(P, qbeg + slot_of_code_t<kS>(x.p));
-        const i64 sx = next_fit_wave(tl_of(P, hd), hd->len, &H[i].res, J.L, t);
-        Tm = sx > Tm ? sx : Tm;
-      }
-      if (Tm == kInf || Tm - P.now > P.max_window) break;  // kAlgoMaxTimeWindow, JobScheduler.h:815
-      if (Tm == t) { found = true; break; }
-      t = Tm;
-    }
-    if (found) {
-      int reason = 0;
-      if (t != P.now) {  // JobScheduler.cpp:6797-6833
+    const i64 t = preempted ? kInf : earliest_start(P, J.k, [&](u32 i, i64 t0) {
+      NodeHdr* hd = hdr_of(P, qbeg + slot_of_code_t<kS>(H[i].p));
+      return next_fit_wave(tl_of(P, hd), hd->len, &H[i].res, J.L, t0);
+    });
+    if (t != kInf) {
+      int reason = CNS_REASON_NONE;
+      if (t != P.now) {
         bool notle = false, reserved = false;
         for (u32 i = lane; i < J.k; i += 64) {
           const HeapEnt x = H[i];
@@ -1473,25 +1525,20 @@ __device__ __noinline__ int worker_job_slow(const KParams& Pm, const WorkerShare
           if (P.first_resv[qx] < P.now + J.L) reserved = true;
         }
         const bool resv_part = sh.part >= P.num_real_parts;
-        reason = (!resv_part && __any(reserved)) ? 3 /*Resource Reserved*/ : (__any(notle) ? 2 /*Resource*/ : 1 /*Priority*/);
+        reason = later_start_reason(!resv_part && __any(reserved), __any(notle));
       }
       commit_selection<kS>(Pm, J, H, qbeg, t, lane, s_upd, s_nupd);
       if (lane == 0) { P.o_start[orig] = t; P.o_reason[orig] = (uint8_t)reason; }
       code = 2;
     }
   }
-  if (code == 0 && lane == 0) { P.o_start[orig] = 0; P.o_reason[orig] = 2; }  // "Resource", :6768
+  if (code == 0 && lane == 0) { P.o_start[orig] = 0; P.o_reason[orig] = CNS_REASON_RESOURCE; }  // :6768
   if (via_hbm) __threadfence_block();  // the owner updates went through HBM (g_upd)
   if (lane == 0) *sh.flag = code;
   wg_barrier();  // B3
   return par;
 }
 
-// kW = false instantiations of the tester / commit functions of k_pipe and k_wide serve snapshots WITHOUT core ids above 127
-// (KParams::wide_cores == 0, chosen once per call by a scalar branch): every Res that enters them from memory has its upper
-// two core words replaced by the constant 0, so the compiler folds their arithmetic, their registers and their loads away —
-// those clusters run the code they ran before ABI 3 (the 4-word Res cost the testers of C4 +26 % per test otherwise).
-template <bool kW> __device__ __forceinline__ Res narrow(Res r) { if (!kW) { r.c2 = 0; r.c3 = 0; } return r; }
 // Loads the node block of slot q the way the fast paths want it: header scalarised, lane i <- entry i.
 // kDrain = false: the caller has drained this wave's stores itself and has OTHER loads in flight that the block's loads may overlap
 // (k_wide's tester: the job record) — the initial s_waitcnt vmcnt(0) would serialise the two round trips.
@@ -1617,13 +1664,9 @@ __device__ __noinline__ int worker_job_multi(const KParams& P, const WorkerShare
     NodeHdr* hd; NodeHdr h; TlEntry e;
     load_block(P, q, lane, hd, h, e);
     int code = 0;
-    Res f, m;
-    bool ok = false;
-    if (feasible(J.min_view, h.avail0, f, P.gres)) {
-      m = uni_res(h.len <= 64 ? window_min_regs(e, lane < h.len, h.avail0, J.E)
-                              : window_min(tl_of(P, hd), h.len, h.avail0, J.E, lane));
-      ok = feasible(J.min_view, m, f, P.gres);
-    }
+    Res f;
+    const Res m = block_window_min(P, hd, h, e, J.E, lane);
+    const bool ok = fits_now(J.min_view, m, h.avail0, f, P.gres);
     if (ok) {
       Res alloc = f;
       if (J.tmin != 1 && !feasible(one_view, m, alloc, P.gres)) { if (lane == 0) set_fault(P, 2, orig, h.node, 3); }
@@ -1639,7 +1682,7 @@ __device__ __noinline__ int worker_job_multi(const KParams& P, const WorkerShare
         for (u32 i = 0; i < J.k; ++i) commit_pick(P, J, H[i], i, qbeg, P.now, lane, sh.upd, orig);
         emit_placements(P, J, H, lane);
         if (P.pre.enabled) pre_join_multi(P, J, H, qbeg, P.now + J.L);
-        if (lane == 0) { *sh.nupd = (int)J.k; P.o_start[orig] = P.now; P.o_reason[orig] = 0; }
+        if (lane == 0) { *sh.nupd = (int)J.k; P.o_start[orig] = P.now; P.o_reason[orig] = CNS_REASON_NONE; }
         code = 2;
       }
     }
@@ -1698,27 +1741,14 @@ __device__ __noinline__ int worker_job_multi(const KParams& P, const WorkerShare
     notle = __any(notle);
     reserved = __any(reserved) && sh.part < P.num_real_parts;   // (the partition, not the workgroup index: k_wide and split launches differ)
     __threadfence_block();
-    // EarliestStartSubsetSelector::CalcEarliestStartTime as a fixed point over the k nodes
-    i64 t = P.now;
-    bool found = false;
-    for (u32 iter = 0; iter < (1u << 20); ++iter) {
-      i64 Tm = t;
-      for (u32 i = 0; i < J.k; ++i) {
-        const HeapEnt x = H[i];
-        NodeHdr* hd; NodeHdr h; TlEntry e;
-        load_block(P, qbeg + slot_of_code(x.p), lane, hd, h, e);
-        i64 s;
-        if (h.len <= 64) s = next_fit_regs(e, h.len, x.res, J.L, t, lane);
-        else s = next_fit_wave(tl_of(P, hd), h.len, &x.res, J.L, t);
-        Tm = s > Tm ? s : Tm;
-      }
-      if (Tm == kInf || Tm - P.now > P.max_window) break;  // kAlgoMaxTimeWindow, JobScheduler.h:815
-      if (Tm == t) { found = true; break; }
-      t = Tm;
-    }
-    if (found) {
-      int reason = 0;
-      if (t != P.now) reason = reserved ? 3 /*Resource Reserved*/ : (notle ? 2 /*Resource*/ : 1 /*Priority*/);  // :6797-6831
+    const i64 t = earliest_start(P, J.k, [&](u32 i, i64 t0) {
+      const HeapEnt x = H[i];
+      NodeHdr* hd; NodeHdr h; TlEntry e;
+      load_block(P, qbeg + slot_of_code(x.p), lane, hd, h, e);
+      return block_next_fit(P, hd, h, e, x.res, J.L, t0, lane);
+    });
+    if (t != kInf) {
+      const int reason = t != P.now ? later_start_reason(reserved, notle) : CNS_REASON_NONE;
       for (u32 i = 0; i < J.k; ++i) commit_pick(P, J, H[i], i, qbeg, t, lane, sh.upd, orig);
       emit_placements(P, J, H, lane);
       if (P.pre.enabled) pre_join_multi(P, J, H, qbeg, t + J.L);
@@ -1726,7 +1756,7 @@ __device__ __noinline__ int worker_job_multi(const KParams& P, const WorkerShare
       code = 2;
     }
   }
-  if (code == 0 && lane == 0) { P.o_start[orig] = 0; P.o_reason[orig] = 2; }  // "Resource", :6768
+  if (code == 0 && lane == 0) { P.o_start[orig] = 0; P.o_reason[orig] = CNS_REASON_RESOURCE; }  // :6768
   if (lane == 0) *sh.flag = code;
   wg_barrier();  // B3
   return par;
@@ -1804,15 +1834,8 @@ __device__ __noinline__ bool multi_verify_commit(const KParams& P, const GresDev
     cost0 = H[i].cost;
     q = qbeg + slot_of_code(p);
     load_block(P, q, lane, hd, h, e);
-    // :6285 first; it implies :6274 except for the core-id count of res_avail (see the single-node fast path)
-    const Res m = uni_res(h.len <= 64 ? window_min_regs(e, lane < h.len, h.avail0, J.E)
-                                      : window_min(tl_of(P, hd), h.len, h.avail0, J.E, lane));    // :6278-6283
-    bool ok = feasible(J.min_view, m, f, G);  // tpn_min == 1: f is the 1-task allocation (:6285, :6312-6320)
-    if (ok) {
-      const i64 req_int = J.min_view.cpu / 256;
-      const u32 nc0 = cores_count(h.avail0);
-      if (req_int * 256 == J.min_view.cpu && nc0 != 0 && nc0 < (u32)req_int) ok = false;   // :528-534 on res_avail
-    }
+    const Res m = block_window_min(P, hd, h, e, J.E, lane);
+    const bool ok = fits_now(J.min_view, m, h.avail0, f, G);  // tpn_min == 1: f is the 1-task allocation (:6312-6320)
     if (lane == 0) { H[i].node = h.node; H[i].ntasks = ok ? 1 : 0; H[i].res = f; H[i].pad = P.sib_off ? (P.sib_off[q + 1] - P.sib_off[q]) << 8 : 0u; }
   }
   wg_barrier();  // M3: verdicts in
@@ -1866,9 +1889,9 @@ __device__ __noinline__ i64 multi_backfill_par(const KParams& P, const GresDev* 
   i64 t = P.now;
   bool found = false;
   int par2 = 0;
-  for (u32 iter = 0; iter < (1u << 20); ++iter) {
+  for (u32 iter = 0; iter < (1u << 22); ++iter) {   // (earliest_start's bound and termination test, one barrier per step)
     if (active) {
-      const i64 sx = h.len <= 64 ? next_fit_regs(e, h.len, alloc, J.L, t, lane) : next_fit_wave(tl_of(P, hd), h.len, &alloc, J.L, t);
+      const i64 sx = block_next_fit(P, hd, h, e, alloc, J.L, t, lane);
       if (lane == 0) nf[par2 * kMultiK + (int)i] = sx;
     }
     wg_barrier();
@@ -1897,7 +1920,7 @@ __device__ __noinline__ i64 multi_backfill_par(const KParams& P, const GresDev* 
   }
   if (found && threadIdx.x == 0) *nupd = (int)total;
   wg_barrier();  // commits + owner updates visible (or: nothing happened)
-  *reason_out = (found && t != P.now) ? (reserved ? 3 : (notle ? 2 : 1)) : 0;  // :6797-6831
+  *reason_out = (found && t != P.now) ? later_start_reason(reserved, notle) : CNS_REASON_NONE;
   return found ? t : kInf;
 }
 
@@ -1972,7 +1995,7 @@ __global__ __launch_bounds__(kBlock) void k_select(const KParams P, const KParam
       for (u64 x = jbeg + tid; x < jend; x += kBlock) {
         const u32 orig = P.jobrec[x * kJobRecDwords + kJrOrig];
         P.o_start[orig] = 0;
-        P.o_reason[orig] = 6;  // "Reservation Not Found"
+        P.o_reason[orig] = CNS_REASON_RESERVATION_NOT_FOUND;
       }
       return;
     }
@@ -2103,23 +2126,13 @@ __global__ __launch_bounds__(kBlock) void k_select(const KParams P, const KParam
           if (h.len > 64) { divert = true; break; }  // long time map: the general routines take over from here
           PROF_T(a1);
           PROF_ADD(1, a0, a1);  // node block load
-          Res f, m;
-          bool ok = false;
-          // :6274 wants GetFeasibleResourceInNode(res_avail) to succeed, :6285 the same on the window minimum m.
-          // m is res_avail folded with Ckmin (:6278-6283): cpu and mem are minima, GRES slots and (when non-empty)
-          // core ids are subsets.  So success on m implies the cpu, mem and GRES tests of :6274; the one test of
-          // :6274 that m does not imply is the core-id count of res_avail (:534) when m's core set came out empty.
+          Res f;
           PROF_T(a1w);
-          m = uni_res(window_min_regs(e, lane < h.len, h.avail0, F.E));   // :6278-6283
+          const Res m = uni_res(window_min_regs(e, lane < h.len, h.avail0, F.E));   // :6278-6283
           PROF_T(a1x);
           PROF_ADD(22, a1, a1w);   // phase A: (nothing left before the window-min)
           PROF_ADD(23, a1w, a1x);  // phase A: window-min
-          ok = feasible(F.mv, m, f, P.gres);                             // get_max_tasks(min_res) > 0, :6285
-          if (ok) {
-            const i64 req_int = F.mv.cpu / 256;
-            const u32 nc0 = cores_count(h.avail0);
-            if (req_int * 256 == F.mv.cpu && nc0 != 0 && nc0 < (u32)req_int) ok = false;   // :528-534 on res_avail
-          }
+          const bool ok = fits_now(F.mv, m, h.avail0, f, P.gres);
           PROF_T(a2);
           PROF_ADD(2, a1, a2);  // window-min + feasibility
           if (ok) {  // tpn_min == 1: the minimum view is the 1-task view, f is the allocation (:6312-6320)
@@ -2212,11 +2225,8 @@ __global__ __launch_bounds__(kBlock) void k_select(const KParams P, const KParam
               cn.code = tcode; cn.cost = tc; cn.len = h.len; cn.type = h.type;
               cn.fcpu = clamp_cpu(e0.cpu); cn.fmem = mem_mib_ceil(e0.mem); cn.fcnt = class_counts(e0.gres, P.gres);
               if (st != kInf && st - P.now <= P.max_window) {          // kAlgoMaxTimeWindow, JobScheduler.h:815
-                int reason = 0;
-                if (st != P.now) {  // :6797-6831
-                  if (!resv_part && first_resv < P.now + F.L) reason = 3;  // "Resource Reserved" (:6799-6806)
-                  else reason = res_le(alloc, h.avail0) ? 1 /*Priority*/ : 2 /*Resource*/;
-                }
+                const int reason = st != P.now ? later_start_reason(!resv_part && first_resv < P.now + F.L, !res_le(alloc, h.avail0))
+                                               : CNS_REASON_NONE;
                 PROF_T(b0c);
                 commit_single_regs(P, F.L, F.orig, F.poff, hd, h, e, q, tcode, cost_of_key_m(tc, wsmode),
                                    alloc, st, reason, lane, s_upd, &s_nupd, cn, PG, qbeg);
@@ -2226,7 +2236,7 @@ __global__ __launch_bounds__(kBlock) void k_select(const KParams P, const KParam
                 code = 2;
               }
             }
-            if (code == 0 && lane == 0) { P.o_start[F.orig] = 0; P.o_reason[F.orig] = 2; }  // "Resource", :6768
+            if (code == 0 && lane == 0) { P.o_start[F.orig] = 0; P.o_reason[F.orig] = CNS_REASON_RESOURCE; }  // :6768
             if (lane == 0) { s_flag = code; s_r0 = round0 ? 1 : 0; }
             PROF_T(b1);
             PROF_ADD(4, b0, b1);  // backfill + commit
@@ -2280,7 +2290,7 @@ __global__ __launch_bounds__(kBlock) void k_select(const KParams P, const KParam
           wg_barrier();  // M2
           if (n == F.k) {  // k start-now candidates exist (:6294-6297 if their exact tests pass)
             if (multi_verify_commit(PG, &s_gres, &s_job, s_heap, kWaves - 1, (u32)(kWaves - 1) < F.k, qbeg, s_upd, &s_nupd)) {
-              if (lane == 0) { P.o_start[F.orig] = P.now; P.o_reason[F.orig] = 0; }  // :6326
+              if (lane == 0) { P.o_start[F.orig] = P.now; P.o_reason[F.orig] = CNS_REASON_NONE; }  // :6326
               if (P.pre.enabled) pre_join_multi(PG, s_job, s_heap, qbeg, P.now + F.L);
               PROF_CNT(30);
             } else {
@@ -2303,14 +2313,14 @@ __global__ __launch_bounds__(kBlock) void k_select(const KParams P, const KParam
               PROF_CNT(31);
               if (lane == 0) {
                 if (st != kInf) { P.o_start[F.orig] = st; P.o_reason[F.orig] = (uint8_t)reason; }
-                else { P.o_start[F.orig] = 0; P.o_reason[F.orig] = 2; }  // "Resource", :6768
+                else { P.o_start[F.orig] = 0; P.o_reason[F.orig] = CNS_REASON_RESOURCE; }  // :6768
               }
               if (P.pre.enabled && st != kInf) pre_join_multi(PG, s_job, s_heap, qbeg, st + F.L);
             } else if (lane == 0) {
-              P.o_start[F.orig] = 0; P.o_reason[F.orig] = 2;  // not even k nodes fit res_total (:6335-6343)
+              P.o_start[F.orig] = 0; P.o_reason[F.orig] = CNS_REASON_RESOURCE;  // not even k nodes fit res_total (:6335-6343)
             }
           }
-          if (fallback) par = P.sib_off ? worker_job_slow(PG, sh, &s_job, par, wc, wcode, tc, tcode, qbeg, gheap)   // (sibling slots among the updates)
+          if (fallback) par = P.sib_off ? worker_job_slow<kScan, true>(PG, sh, &s_job, par, wc, wcode, tc, tcode, qbeg, gheap)   // (sibling slots among the updates)
                                         : worker_job_multi(PG, sh, &s_job, par, wc, wcode, tc, tcode, qbeg);
           PROF_T(p8);
           PROF_ADD(6, d0, p8);
@@ -2321,7 +2331,7 @@ __global__ __launch_bounds__(kBlock) void k_select(const KParams P, const KParam
           PROF_ADD(6, d0, p8);
           PROF_CNT(15);
         } else {
-          par = worker_job_slow(PG, sh, &s_job, par, wc, wcode, tc, tcode, qbeg, gheap);
+          par = worker_job_slow<kScan, true>(PG, sh, &s_job, par, wc, wcode, tc, tcode, qbeg, gheap);
           PROF_T(p9);
           PROF_ADD(5, d0, p9);
           PROF_CNT(13);

@@ -348,8 +348,6 @@ __device__ __noinline__ bool wide_retire_one(const KParams* Pg, const WideHome s
   // ---- commit: every older task has a passing verdict ------------------------------------------------------------
   const auto& P = kparams_scalar(Pg);   // (the block's copy in HBM, through scalar loads: select_kernels.hip)
   const GresDev& G = Pg->gres;
-  PipeShared psh;
-  psh.task = nullptr; psh.flush_job = &sh.w->flush_job; psh.abort = &sh.w->abort; psh.posted = &sh.w->posted; psh.tres = nullptr; psh.tnode = nullptr;
   const u32 k = vld(&T->kind_k) >> 8;
   const i64 st = (i64)(((u64)vld((u32*)&T->st + 1) << 32) | vld((u32*)&T->st));
   const i64 L = (i64)(((u64)vld((u32*)&T->L + 1) << 32) | vld((u32*)&T->L));
@@ -368,7 +366,7 @@ __device__ __noinline__ bool wide_retire_one(const KParams* Pg, const WideHome s
     u32 rank = 0;  // placement records are listed by ascending node index
     for (u32 mm = 0; mm < k; ++mm) rank += vld(&T->node[mm]) < h.node ? 1u : 0u;
     const u64 c0 = ((u64)vld((u32*)&T->cost0[i] + 1) << 32) | vld((u32*)&T->cost0[i]);
-    pipe_commit_node<kW>(P, *Pg, G, psh, hd, h, e, qi, c0, uni_res(narrow<kW>(T->alloc[i])), st, L, orig, poff + rank, lane);
+    pipe_commit_node<kW>(P, *Pg, G, &sh.w->abort, hd, h, e, qi, c0, uni_res(narrow<kW>(T->alloc[i])), st, L, orig, poff + rank, lane);
     TPROF_T(c4);
     TPROF_ADD(19, c3, c4);                         // map update + cost + scanner arrays + placement record (incl. the wait for the stores)
   }
@@ -428,14 +426,12 @@ __device__ __noinline__ void wide_test_task(const KParams* Pg, const WideHome sh
   h.len = 0;
   bool early = false;
   const bool multi = vld(&sh.w->homes) > 1u;   // several homes: a node's previous writer may sit on another CU — drop this CU's L1 behind every dependency wait
-#if !defined(CNS_WIDE_NO_TESTER_OVERLAP) && !defined(CNS_WIDE_NO_EARLY_BLOCK)
   if (k == 1 && P.wide_tester_opt != 0u) {
     if (!wide_wait_dep<kW>(P, Pg, sh, vld(&T->dep[0]), qbeg)) return;   // (LDS; a retirement it helps with drains its own stores)
     if (multi) l1_inv();
     load_block<kW, false>(P, qbeg + vld(&T->code[0]), lane, hd, h, e);
     early = true;
   }
-#endif
   const FastJob F = make_fast_job(P, raw);
   const u32 maxlen = P.max_jobs_per_node;
   TPROF_T(t1);
@@ -445,7 +441,7 @@ __device__ __noinline__ void wide_test_task(const KParams* Pg, const WideHome sh
   // start fails it, 4 no start inside the window on the res_total nodes (Backfill_ fails: the job gets "Resource")
   u32 cause = 0;
   i64 st = P.now;
-  int reason = 0;
+  int reason = CNS_REASON_NONE;
   if (k == 1) {
     Res alloc = res_zero();
     const u32 q = qbeg + vld(&T->code[0]);
@@ -457,15 +453,7 @@ __device__ __noinline__ void wide_test_task(const KParams* Pg, const WideHome sh
     ok = h.len < maxlen;                                            // :6194 on the CURRENT map (the tile's length may be stale)
     cause = ok ? 0u : 1u;
     if (ok && kind == kPkStart) {
-      // :6285 on the window minimum; it implies :6274 except for the core-id count of res_avail (see k_select)
-      const Res m = uni_res(narrow<kW>(h.len <= 64 ? window_min_regs(e, lane < h.len, h.avail0, F.E)
-                                                  : window_min(tl_of<kW>(P, hd), h.len, h.avail0, F.E, lane)));   // :6278-6283
-      ok = feasible(F.mv, m, alloc, G);
-      if (ok) {
-        const i64 req_int = F.mv.cpu / 256;
-        const u32 nc0 = cores_count(h.avail0);
-        if (req_int * 256 == F.mv.cpu && nc0 != 0 && nc0 < (u32)req_int) ok = false;           // :528-534 on res_avail
-      }
+      ok = fits_now(F.mv, block_window_min<kW>(P, hd, h, e, F.E, lane), h.avail0, alloc, G);
       if (!ok) { cause = 2; record_dip(P, G, q, e, h.len, F.mv, F.E, lane); }
       TPROF_T(t4);
       TPROF_ADD(4, t3, t4);                                         // window minimum + the exact test
@@ -473,35 +461,27 @@ __device__ __noinline__ void wide_test_task(const KParams* Pg, const WideHome sh
       // backfill on the first node in cost order whose res_total fits (:6335-6368, Backfill_ :6371-6376)
       if (!feasible(F.mv, h.total, alloc, G)) { wide_home_fault(P, sh, 3, F.orig, h.node, 0); return; }
       alloc = uni_res(alloc);
-      st = h.len <= 64 ? next_fit_regs(e, h.len, alloc, F.L, P.now, lane) : next_fit_wave(tl_of<kW>(P, hd), h.len, &alloc, F.L, P.now);
+      st = block_next_fit<kW>(P, hd, h, e, alloc, F.L, P.now, lane);
       ok = st != kInf && st - P.now <= P.max_window;                // kAlgoMaxTimeWindow, JobScheduler.h:815
       if (!ok) cause = 4;
-      if (ok && st != P.now) {                                      // :6797-6831
-        const i64 first_resv = resv_part ? kInf : P.first_resv[q];
-        if (first_resv < P.now + F.L) reason = 3;                   // "Resource Reserved"
-        else reason = res_le(alloc, h.avail0) ? 1 /*Priority*/ : 2 /*Resource*/;
-      }
+      if (ok && st != P.now) reason = later_start_reason(!resv_part && P.first_resv[q] < P.now + F.L, !res_le(alloc, h.avail0));
     }
     // ---- the task that is next to retire commits AT ONCE, from the registers of its test (round 5): every older task has been claimed
     // for its commit (retirement is in id order) and none contradicted its prediction — no verdict through the slot, no claim by another
     // wave, no second load of the node block (nobody else may touch the node: a younger task on it waits for this one).  (Waiting a few
     // hundred cycles for the predecessors' claims so that more tasks take this path was measured and does not pay: profiles/r05_ab_fuse_spin.txt)
-#if !defined(CNS_WIDE_NO_TESTER_OVERLAP) && !defined(CNS_WIDE_NO_FUSED_COMMIT)
     if (ok && P.wide_tester_opt != 0u && h.len <= 64 && vld(&sh.w->retired) + 1u == my && vld(&T->gid) <= vld(&sh.w->allow) && vld(&sh.w->flush_job) > ji) {
       u32 won = 0;
       if (lane == 0) won = atomicCAS(&sh.w->retired, my - 1u, my) == my - 1u ? 1u : 0u;
       if (uni32(won)) {
-        PipeShared psh;
-        psh.task = nullptr; psh.flush_job = &sh.w->flush_job; psh.abort = &sh.w->abort; psh.posted = &sh.w->posted; psh.tres = nullptr; psh.tnode = nullptr;
         const u64 c0 = ((u64)vld((u32*)&T->cost0[0] + 1) << 32) | vld((u32*)&T->cost0[0]);
-        pipe_commit_node<kW>(P, *Pg, G, psh, hd, h, e, q, c0, uni_res(alloc), st, F.L, F.orig, F.poff, lane);
+        pipe_commit_node<kW>(P, *Pg, G, &sh.w->abort, hd, h, e, q, c0, uni_res(alloc), st, F.L, F.orig, F.poff, lane);
         if (lane == 0) { P.o_start[F.orig] = st; P.o_reason[F.orig] = (uint8_t)reason; }
         drain_stores();   // later tasks on this node, and a tile reload, read what was just written
         if (lane == 0) { T->orig = F.orig; lds_fence(); vst(&T->state, kTsCommitted); }
         return;
       }
     }
-#endif
     if (ok && lane == 0) { T->alloc[0] = uni_res(alloc); T->node[0] = h.node; }
   } else {
     // node_num 2..8, ntasks == node_num: the nodes one after the other (the task is off the sequential chain)
@@ -520,14 +500,7 @@ __device__ __noinline__ void wide_test_task(const KParams* Pg, const WideHome sh
       if (h.len >= maxlen) { ok = false; cause = 1; break; }
       Res a = res_zero();
       if (kind == kPkStart) {
-        const Res m = uni_res(narrow<kW>(h.len <= 64 ? window_min_regs(e, lane < h.len, h.avail0, F.E)
-                                                    : window_min(tl_of<kW>(P, hd), h.len, h.avail0, F.E, lane)));
-        ok = feasible(v1, m, a, G);
-        if (ok) {
-          const i64 req_int = v1.cpu / 256;
-          const u32 nc0 = cores_count(h.avail0);
-          if (req_int * 256 == v1.cpu && nc0 != 0 && nc0 < (u32)req_int) ok = false;
-        }
+        ok = fits_now(v1, block_window_min<kW>(P, hd, h, e, F.E, lane), h.avail0, a, G);
         if (!ok) { cause = 3; record_dip(P, G, qi, e, h.len, v1, F.E, lane); }
       } else {
         if (!feasible(v1, h.total, a, G)) { wide_home_fault(P, sh, 3, F.orig, h.node, 2); return; }   // :6354-6356
@@ -538,25 +511,13 @@ __device__ __noinline__ void wide_test_task(const KParams* Pg, const WideHome sh
     }
     lds_fence();
     if (ok && kind == kPkBackfill) {
-      // EarliestStartSubsetSelector::CalcEarliestStartTime as the fixed point t <- max_i next_fit_i(t) (see k_select)
-      i64 t = P.now;
-      bool found = false;
-      for (u32 iter = 0; iter < (1u << 20); ++iter) {
-        i64 Tm = t;
-        for (u32 i = 0; i < k; ++i) {
-          load_block<kW>(P, qbeg + vld(&T->code[i]), lane, hd, h, e);
-          const Res a = uni_res(narrow<kW>(T->alloc[i]));
-          const i64 s = h.len <= 64 ? next_fit_regs(e, h.len, a, F.L, t, lane) : next_fit_wave(tl_of<kW>(P, hd), h.len, &T->alloc[i], F.L, t);
-          Tm = s > Tm ? s : Tm;
-        }
-        if (Tm == kInf || Tm - P.now > P.max_window) break;
-        if (Tm == t) { found = true; break; }
-        t = Tm;
-      }
-      ok = found;
+      st = earliest_start(P, k, [&](u32 i, i64 t) {
+        load_block<kW>(P, qbeg + vld(&T->code[i]), lane, hd, h, e);
+        return block_next_fit<kW>(P, hd, h, e, T->alloc[i], F.L, t, lane);
+      });
+      ok = st != kInf;
       if (!ok) cause = 4;
-      st = t;
-      if (ok && st != P.now) reason = reserved ? 3 : (notle ? 2 : 1);
+      if (ok && st != P.now) reason = later_start_reason(reserved, notle);
     }
   }
   // ---- verdict (+ the result the commit needs) ----------------------------------------------------------------
@@ -739,7 +700,7 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
         for (u64 x = jbeg + tid; x < jend; x += kWBlock) {
           const u32 orig = P.jobrec[x * kJobRecDwords + kJrOrig];
           P.o_start[orig] = 0;
-          P.o_reason[orig] = 6;  // "Reservation Not Found"
+          P.o_reason[orig] = CNS_REASON_RESERVATION_NOT_FOUND;
         }
       return;
     }
@@ -1045,7 +1006,7 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
       reduce16(tc, tcode);
       par ^= 1;
       wc = uni64(wc); wcode = uni32(wcode); tc = uni64(tc); tcode = uni32(tcode);
-      par = worker_job_slow<1024>(PG, sh, &s_job, par, wc, wcode, tc, tcode, qbeg, gheap);
+      par = worker_job_slow<1024, false>(PG, sh, &s_job, par, wc, wcode, tc, tcode, qbeg, gheap);
       drain_stores();
       wg_barrier();  // S1
       return !vld(&s_abort);
@@ -1180,7 +1141,7 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
               // not even k nodes whose res_total fits: "Resource" (:6335-6343, :6768); nothing changes
               if (hix == 0u) {
                 const u32 orig = uni32(P.jobrec[(jbeg + sup_pos) * kJobRecDwords + kJrOrig]);
-                if (lane == 0) { P.o_start[orig] = 0; P.o_reason[orig] = 2; }
+                if (lane == 0) { P.o_start[orig] = 0; P.o_reason[orig] = CNS_REASON_RESOURCE; }
               }
             } else if (own) {
               const u32 id = nposted + 1;
@@ -1335,7 +1296,7 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
             if (fcause == 4) {
               // Backfill_ fails on exactly these nodes in the reference too (no wave could start the job now: the tile
               // holds upper bounds; the res_total nodes and their costs are exact): "Resource", nothing changes (:6768)
-              if (lane == 0) { P.o_start[forig] = 0; P.o_reason[forig] = 2; }
+              if (lane == 0) { P.o_start[forig] = 0; P.o_reason[forig] = CNS_REASON_RESOURCE; }
               drain_stores();
               resume = fj + 1;
               excl_job = kNone;
