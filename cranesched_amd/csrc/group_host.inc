@@ -289,8 +289,11 @@ int cns_group_select(cns_group* g, int64_t now, const cns_job_soa* jb, cns_place
   const u64 J = jb->num_jobs;
   const auto t0 = std::chrono::steady_clock::now();
   // ---- deal the queue: job -> the device of its partition (of its reservation), order preserved ---------------------------------
-  if (!jb->partition || !jb->node_num || !jb->ntasks || !jb->ntasks_per_node_min || !jb->ntasks_per_node_max || !jb->time_limit_sec || !jb->node_mem ||
-      !jb->task_cpu_raw || !jb->task_mem || (jb->incl_offsets && !jb->incl_nodes && jb->incl_offsets[J] != 0) || (jb->excl_offsets && !jb->excl_nodes && jb->excl_offsets[J] != 0))
+  // (an empty queue may come with null job arrays — an adapter's never-filled vectors — as cns_select accepts them: every device then
+  // runs an empty shard, exactly as one engine runs an empty queue, and the result is all empty)
+  if (J && (!jb->partition || !jb->node_num || !jb->ntasks || !jb->ntasks_per_node_min || !jb->ntasks_per_node_max || !jb->time_limit_sec || !jb->node_mem ||
+            !jb->task_cpu_raw || !jb->task_mem || (jb->incl_offsets && !jb->incl_nodes && jb->incl_offsets[J] != 0) ||
+            (jb->excl_offsets && !jb->excl_nodes && jb->excl_offsets[J] != 0)))
     return gfail(g, CNS_ERR_INVALID_ARG, "cns_group_select: a required job array is missing (or node-list offsets without the lists)");
   for (auto& s : g->shard) s = cns_group::Shard{};
   std::vector<u32> jdev;

@@ -229,10 +229,11 @@ struct GpuNodeSelectionAlgo::Impl {
           auto rit = resv_idx.find(p.reservation);
           B.jresv[j] = rit == resv_idx.end() ? 0xFFFFFFFEu : rit->second;
         }
+        bool absent_name = false;   // (applied after the loop: the map's order must not let a known name overwrite the mark)
         for (const auto& [name, gc] : p.req_node_res_view.gres_map) {
           auto nit = name_id.find(name);
           uint64_t tot = gc.total;
-          if (nit == name_id.end()) { if (tot || !gc.specified.empty()) B.gtot[j * CNS_MAX_GRES_NAMES] = 255; continue; }  // name absent everywhere: never fits
+          if (nit == name_id.end()) { absent_name = absent_name || tot || !gc.specified.empty(); continue; }  // name absent everywhere: never fits
           B.gtot[j * CNS_MAX_GRES_NAMES + nit->second] = (uint8_t)std::min<uint64_t>(tot, 255);
           for (const auto& [type, cnt] : gc.specified) {
             int c = class_of(name, type);
@@ -240,6 +241,7 @@ struct GpuNodeSelectionAlgo::Impl {
             B.gspec[j * CNS_MAX_GRES_CLASSES + c] = (uint8_t)std::min<uint64_t>(cnt, 127);
           }
         }
+        if (absent_name) B.gtot[j * CNS_MAX_GRES_NAMES] = 255;
       }
       n_lists.fetch_add(lists, std::memory_order_relaxed);
       n_places.fetch_add(plc, std::memory_order_relaxed);
@@ -748,6 +750,74 @@ void GpuNodeSelectionAlgo::PendingCycleForBench(const std::vector<std::unique_pt
   mix(B.gtot.data(), B.gtot.size()); mix(B.gspec.data(), B.gspec.size()); mix(B.skip.data(), J);
   for (size_t j = 0; j < J; j += 997) { const auto& p = *ord[j]; mix(p.craned_ids[0].data(), p.craned_ids[0].size()); mix(&p.end_time, 8); }
   *checksum = hsh;
+}
+
+void GpuNodeSelectionAlgo::PackedArraysForTest(const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs,
+                                               const std::vector<std::unique_ptr<PdJobInScheduler>>& pending_jobs,
+                                               std::map<std::string, std::vector<uint64_t>>* out) {
+  Impl& I = *impl_;
+  out->clear();
+  auto put = [&](const char* name, const auto& v, size_t n) {
+    auto& d = (*out)[name];
+    d.resize(n);
+    for (size_t i = 0; i < n; ++i) d[i] = (uint64_t)v[i];
+  };
+  auto all = [&](const char* name, const auto& v) { put(name, v, v.size()); };
+  // cns_set_nodes
+  all("n_cpu", I.n_cpu); all("n_mem", I.n_mem); all("n_lo", I.n_lo); all("n_hi", I.n_hi); all("n_w2", I.n_w2); all("n_w3", I.n_w3);
+  all("n_gres", I.n_gres); all("n_sched", I.n_sched); all("n_unsup", I.n_unsup);
+  all("part_offsets", I.n_poff); all("part_nodes", I.n_pnodes);
+  const uint32_t C = I.layout.num_classes;
+  (*out)["layout_num_classes"] = {C};
+  put("layout_class_name", I.layout.class_name, C); put("layout_class_shift", I.layout.class_shift, C); put("layout_class_width", I.layout.class_width, C);
+  // cns_set_reservations
+  all("v_start", I.v_start); all("v_end", I.v_end); all("v_off", I.v_off); all("v_node", I.v_node); all("v_cpu", I.v_cpu); all("v_mem", I.v_mem);
+  all("v_lo", I.v_lo); all("v_hi", I.v_hi); all("v_w2", I.v_w2); all("v_w3", I.v_w3); all("v_g", I.v_g);
+  // cns_set_running
+  I.pack_running(running_jobs);
+  all("r_end", I.r_end); all("r_resv", I.r_resv); all("r_off", I.r_off); all("r_node", I.r_node); all("r_cpu", I.r_cpu); all("r_mem", I.r_mem);
+  all("r_lo", I.r_lo); all("r_hi", I.r_hi); all("r_w2", I.r_w2); all("r_w3", I.r_w3); all("r_g", I.r_g);
+  // cns_select
+  std::vector<PdJobInScheduler*> ord;
+  for (const auto& j : pending_jobs) ord.push_back(j.get());
+  Impl::PackedJobs B;
+  I.pack_pending(ord, B);
+  const size_t J = ord.size();
+  put("j_part", B.part, J); put("j_L", B.L, J); put("j_ncpu", B.ncpu, J); put("j_nmem", B.nmem, J); put("j_tcpu", B.tcpu, J);
+  put("j_tmem", B.tmem, J); put("j_k", B.k, J); put("j_nt", B.nt, J); put("j_tmin", B.tmin, J); put("j_tmax", B.tmax, J);
+  put("j_excl", B.excl, J); put("j_skip", B.skip, J); put("j_resv", B.jresv, J);
+  put("j_gtot", B.gtot, J * CNS_MAX_GRES_NAMES); put("j_gspec", B.gspec, J * CNS_MAX_GRES_CLASSES);
+  put("j_ioff", B.ioff, J + 1); put("j_eoff", B.eoff, J + 1);
+  put("j_inodes", B.inodes, B.ioff[J]); put("j_enodes", B.enodes, B.eoff[J]);
+}
+
+void GpuNodeSelectionAlgo::WriteBackForTest(const std::vector<std::unique_ptr<PdJobInScheduler>>& pending_jobs, const PlacementsForTest& p) {
+  Impl& I = *impl_;
+  std::vector<PdJobInScheduler*> ord;
+  for (const auto& j : pending_jobs) ord.push_back(j.get());
+  const size_t J = ord.size();
+  Impl::PlacementStore& S = I.last;   // what NodeSelect keeps of a cycle
+  S.start.assign(p.start_sec.begin(), p.start_sec.end()); S.reason.assign(p.reason.begin(), p.reason.end());
+  S.off.assign(p.place_offsets.begin(), p.place_offsets.end()); S.node.assign(p.node_idx.begin(), p.node_idx.end());
+  S.nt.assign(p.ntasks.begin(), p.ntasks.end()); S.cpu.assign(p.cpu_raw.begin(), p.cpu_raw.end()); S.mem.assign(p.mem.begin(), p.mem.end());
+  S.lo.assign(p.core_lo.begin(), p.core_lo.end()); S.hi.assign(p.core_hi.begin(), p.core_hi.end()); S.g.assign(p.gres.begin(), p.gres.end());
+  S.w2.assign(p.core_w2.begin(), p.core_w2.end()); S.w3.assign(p.core_w3.begin(), p.core_w3.end());
+  S.excl.resize(J); S.msw_node.resize(J); S.msw_task.resize(J);
+  for (size_t j = 0; j < J; ++j) {
+    S.excl[j] = ord[j]->exclusive;
+    S.msw_node[j] = ord[j]->req_node_res_view.memory_sw_bytes;
+    S.msw_task[j] = ord[j]->req_task_res_view.memory_sw_bytes;
+    if (!ord[j]->preempted_jobs.empty()) ord[j]->preempted_jobs.clear();
+  }
+  S.jobs = J;
+  I.last_ord.assign(ord.begin(), ord.end());
+  I.last_index.clear();
+  cns_placement_soa o{};
+  o.place_capacity = S.node.size();
+  o.start_sec = S.start.data(); o.reason = S.reason.data(); o.place_offsets = S.off.data(); o.node_idx = S.node.data(); o.ntasks = S.nt.data();
+  o.cpu_raw = S.cpu.data(); o.mem = S.mem.data(); o.core_lo = S.lo.data(); o.core_hi = S.hi.data(); o.gres = S.g.data();
+  o.core_w2 = S.w2.data(); o.core_w3 = S.w3.data();
+  I.write_back(ord, o);
 }
 
 size_t GpuNodeSelectionAlgo::PackRunningForBench(const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs,

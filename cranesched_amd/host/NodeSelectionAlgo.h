@@ -426,6 +426,26 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   // ... and the emission of PendingCycleForBench's synthetic placements (ms per call)
   double EmitWireForBench(size_t* records, size_t* bytes);
 
+  // ---- test hooks (no device): the two halves of the string <-> ABI translation, checked against an independent derivation ----------
+  // Copies of every array the adapter hands to cns_set_nodes ("n_*", "part_*", "layout_*"), cns_set_reservations ("v_*"),
+  // cns_set_running ("r_*", after packing `running_jobs`) and cns_select ("j_*", after packing `pending_jobs` in their order; no sorter,
+  // no license pre-pass), each as 64-bit words (signed values two's complement).  Needs SetClusterSnapshot first.
+  void PackedArraysForTest(const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs,
+                           const std::vector<std::unique_ptr<PdJobInScheduler>>& pending_jobs,
+                           std::map<std::string, std::vector<uint64_t>>* out);
+  // cns_placement_soa of a cycle over `pending_jobs` (in their order), as the caller gives it
+  struct PlacementsForTest {
+    std::vector<int64_t> start_sec;
+    std::vector<uint8_t> reason;
+    std::vector<uint64_t> place_offsets;   // [J + 1]
+    std::vector<uint32_t> node_idx, ntasks;
+    std::vector<int64_t> cpu_raw;
+    std::vector<uint64_t> mem, core_lo, core_hi, gres, core_w2, core_w3;
+  };
+  // The write-back of those placements into the jobs, under the current write-back mode, exactly as NodeSelect runs it; afterwards
+  // they are the last cycle's placements (MaterializeAllocation, the wire emission).
+  void WriteBackForTest(const std::vector<std::unique_ptr<PdJobInScheduler>>& pending_jobs, const PlacementsForTest& p);
+
   // ---- preemption (only when the snapshot had preempt_enabled) -------------------------------------------------------
   // m_preempting_set_ (JobScheduler.h:984) lives in the adapter across cycles; the running jobs newly put into it by the
   // last cycle are what the reference hands to EnqueuePreemptCancel (JobScheduler.cpp:6793), in that order.

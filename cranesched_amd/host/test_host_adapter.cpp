@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <set>
 #include <string>
 
 #include "NodeSelectionAlgo.h"
@@ -566,7 +567,379 @@ static int wire_dump(const char* path, int n, bool jobtod) {
   return 0;
 }
 
+// ---- string-level cases (tests/adapter_case.py): the adapter against the oracle, job by job ---------------------------------------------
+// A case is a whitespace-separated token stream ("-" = the empty string):
+//   now T
+//   nodes N            then N x  name alive drain RES
+//   partitions P       then P x  name n node_name x n
+//   resvs V            then V x  name start end m (node RES) x m
+//   running R          then R x  id qos qos_priority resv start end m (node RES) x m
+//   pending J          then J x  id partition resv time_limit node_num ntasks tmin tmax exclusive reason qos qos_priority priority
+//                                REQ(node) REQ(task) ni name x ni ne name x ne
+//   preempt E Q        then Q x  qos n qos x n
+// RES = cpu_raw mem mem_sw ncores id x ncores ngres (name type nslots slot x nslots) x ngres
+// REQ = cpu_raw mem mem_sw nnames (name total nspec (type count) x nspec) x nnames
+struct Case {
+  TimeSec now = 0;
+  ClusterSnapshot snap;
+  std::vector<std::unique_ptr<RnJobInScheduler>> running;
+  std::vector<std::unique_ptr<PdJobInScheduler>> pending;
+};
+
+struct Tok {
+  FILE* f;
+  bool ok = true;
+  std::string s() {
+    char buf[4096];
+    if (fscanf(f, "%4095s", buf) != 1) { ok = false; return ""; }
+    return strcmp(buf, "-") ? std::string(buf) : std::string();
+  }
+  uint64_t u() { const std::string t = s(); return ok ? strtoull(t.c_str(), nullptr, 10) : 0; }
+  int64_t i() { const std::string t = s(); return ok ? strtoll(t.c_str(), nullptr, 10) : 0; }
+  double d() { const std::string t = s(); return ok ? strtod(t.c_str(), nullptr) : 0.0; }
+  void expect(const char* kw) { if (s() != kw) ok = false; }
+};
+
+static ResourceInNodeV3 read_res(Tok& t) {
+  ResourceInNodeV3 r;
+  r.cpu_set.cpu_count = cpu_t::from_raw(t.i());
+  r.memory_bytes = t.u(); r.memory_sw_bytes = t.u();
+  for (uint64_t n = t.u(), c = 0; c < n && t.ok; ++c) r.cpu_set.core_ids.insert((uint32_t)t.u());
+  for (uint64_t n = t.u(), g = 0; g < n && t.ok; ++g) {
+    const std::string name = t.s(), type = t.s();
+    auto& slots = r.gres[name][type];
+    for (uint64_t k = t.u(), x = 0; x < k && t.ok; ++x) slots.insert(t.s());
+  }
+  return r;
+}
+static ResourceView read_req(Tok& t) {
+  ResourceView v;
+  v.cpu_count = cpu_t::from_raw(t.i());
+  v.memory_bytes = t.u(); v.memory_sw_bytes = t.u();
+  for (uint64_t n = t.u(), g = 0; g < n && t.ok; ++g) {
+    GresCount& gc = v.gres_map[t.s()];
+    gc.total = t.u();
+    for (uint64_t k = t.u(), x = 0; x < k && t.ok; ++x) { const std::string type = t.s(); gc.specified[type] = t.u(); }
+  }
+  return v;
+}
+
+static bool read_case(const char* path, Case& c) {
+  FILE* f = fopen(path, "r");
+  if (!f) return false;
+  Tok t{f};
+  t.expect("now"); c.now = t.i();
+  t.expect("nodes");
+  for (uint64_t n = t.u(), i = 0; i < n && t.ok; ++i) {
+    CranedMeta m;
+    m.craned_id = t.s(); m.alive = t.u() != 0; m.drain = t.u() != 0;
+    m.res_total = read_res(t);
+    c.snap.craned_metas.push_back(std::move(m));
+  }
+  t.expect("partitions");
+  for (uint64_t n = t.u(), i = 0; i < n && t.ok; ++i) {
+    std::pair<PartitionId, std::vector<CranedId>> p;
+    p.first = t.s();
+    for (uint64_t k = t.u(), x = 0; x < k && t.ok; ++x) p.second.push_back(t.s());
+    c.snap.partitions.push_back(std::move(p));
+  }
+  t.expect("resvs");
+  for (uint64_t n = t.u(), i = 0; i < n && t.ok; ++i) {
+    ResvMeta v;
+    v.name = t.s(); v.start_time = t.i(); v.end_time = t.i();
+    for (uint64_t k = t.u(), x = 0; x < k && t.ok; ++x) { const std::string cid = t.s(); v.res_total[cid] = read_res(t); }
+    c.snap.reservations.push_back(std::move(v));
+  }
+  t.expect("running");
+  for (uint64_t n = t.u(), i = 0; i < n && t.ok; ++i) {
+    auto r = std::make_unique<RnJobInScheduler>();
+    r->job_id = (job_id_t)t.u(); r->qos = t.s(); r->qos_priority = (uint32_t)t.u(); r->reservation = t.s();
+    r->start_time = t.i(); r->end_time = t.i();
+    for (uint64_t k = t.u(), x = 0; x < k && t.ok; ++x) { const std::string cid = t.s(); r->allocated_res[cid] = read_res(t); }
+    r->node_num = (uint32_t)r->allocated_res.size();
+    c.running.push_back(std::move(r));
+  }
+  t.expect("pending");
+  for (uint64_t n = t.u(), i = 0; i < n && t.ok; ++i) {
+    auto p = std::make_unique<PdJobInScheduler>();
+    p->job_id = (job_id_t)t.u(); p->partition_id = t.s(); p->reservation = t.s(); p->time_limit = t.i();
+    p->node_num = (uint32_t)t.u(); p->ntasks = (uint32_t)t.u(); p->ntasks_per_node_min = (uint32_t)t.u(); p->ntasks_per_node_max = (uint32_t)t.u();
+    p->exclusive = t.u() != 0; p->reason = t.s(); p->qos = t.s(); p->qos_priority = (uint32_t)t.u(); p->priority = t.d();
+    p->req_node_res_view = read_req(t);
+    p->req_task_res_view = read_req(t);
+    for (uint64_t k = t.u(), x = 0; x < k && t.ok; ++x) p->included_nodes.insert(t.s());
+    for (uint64_t k = t.u(), x = 0; x < k && t.ok; ++x) p->excluded_nodes.insert(t.s());
+    c.pending.push_back(std::move(p));
+  }
+  t.expect("preempt");
+  c.snap.preempt_enabled = t.u() != 0;
+  for (uint64_t n = t.u(), i = 0; i < n && t.ok; ++i) {
+    auto& lst = c.snap.qos_preempt[t.s()];
+    for (uint64_t k = t.u(), x = 0; x < k && t.ok; ++x) lst.push_back(t.s());
+  }
+  fclose(f);
+  return t.ok;
+}
+
+static std::string jstr(const std::string& s) {   // JSON string (names are plain tokens; quote and backslash escaped anyway)
+  std::string o = "\"";
+  for (char ch : s) { if (ch == '"' || ch == '\\') o.push_back('\\'); o.push_back(ch); }
+  return o + "\"";
+}
+// Every output field of PdJobInScheduler (JobScheduler.h:117-133), one JSON object per job, maps and sets in sorted order
+static void dump_jobs(FILE* o, const std::vector<std::unique_ptr<PdJobInScheduler>>& pending) {
+  for (const auto& p : pending) {
+    fprintf(o, "{\"job\": %u, \"reason\": %s, \"start\": %lld, \"end\": %lld, \"craned_ids\": [", p->job_id, jstr(p->reason).c_str(),
+            (long long)p->start_time, (long long)p->end_time);
+    for (size_t i = 0; i < p->craned_ids.size(); ++i) fprintf(o, "%s%s", i ? ", " : "", jstr(p->craned_ids[i]).c_str());
+    fprintf(o, "], \"task_num\": {");
+    std::map<std::string, uint32_t> tn(p->craned_id_to_task_num.begin(), p->craned_id_to_task_num.end());
+    bool first = true;
+    for (const auto& [cid, n] : tn) { fprintf(o, "%s%s: %u", first ? "" : ", ", jstr(cid).c_str(), n); first = false; }
+    fprintf(o, "}, \"alloc\": {");
+    std::map<std::string, const ResourceInNodeV3*> al;
+    for (const auto& [cid, r] : p->allocated_res) al[cid] = &r;
+    first = true;
+    for (const auto& [cid, r] : al) {
+      fprintf(o, "%s%s: {\"cpu\": %lld, \"mem\": %llu, \"msw\": %llu, \"cores\": [", first ? "" : ", ", jstr(cid).c_str(), (long long)r->cpu_set.cpu_count.raw,
+              (unsigned long long)r->memory_bytes, (unsigned long long)r->memory_sw_bytes);
+      first = false;
+      bool f2 = true;
+      for (uint32_t id : r->cpu_set.core_ids) { fprintf(o, "%s%u", f2 ? "" : ", ", id); f2 = false; }
+      fprintf(o, "], \"gres\": {");
+      std::map<std::string, std::map<std::string, const std::set<SlotId>*>> g;
+      for (const auto& [name, tm] : r->gres) for (const auto& [type, slots] : tm) g[name][type] = &slots;
+      f2 = true;
+      for (const auto& [name, tm] : g) {
+        fprintf(o, "%s%s: {", f2 ? "" : ", ", jstr(name).c_str());
+        f2 = false;
+        bool f3 = true;
+        for (const auto& [type, slots] : tm) {
+          fprintf(o, "%s%s: [", f3 ? "" : ", ", jstr(type).c_str());
+          f3 = false;
+          bool f4 = true;
+          for (const auto& s : *slots) { fprintf(o, "%s%s", f4 ? "" : ", ", jstr(s).c_str()); f4 = false; }
+          fprintf(o, "]");
+        }
+        fprintf(o, "}");
+      }
+      fprintf(o, "}}");
+    }
+    fprintf(o, "}, \"preempted\": [");
+    for (size_t i = 0; i < p->preempted_jobs.size(); ++i) {
+      const auto& pj = p->preempted_jobs[i];
+      if (std::holds_alternative<PdJobInScheduler*>(pj)) fprintf(o, "%s[\"P\", %u]", i ? ", " : "", std::get<PdJobInScheduler*>(pj)->job_id);
+      else fprintf(o, "%s[\"R\", %u]", i ? ", " : "", std::get<RnJobInScheduler*>(pj)->job_id);
+    }
+    fprintf(o, "]}\n");
+  }
+}
+static void dump_cycle(FILE* o, GpuNodeSelectionAlgo& algo, const std::vector<std::unique_ptr<PdJobInScheduler>>& pending) {
+  dump_jobs(o, pending);
+  fprintf(o, "{\"status\": %d, \"error\": %s, \"refused\": [", algo.LastStatus(), jstr(algo.LastError()).c_str());
+  for (size_t i = 0; i < algo.RefusedJobs().size(); ++i) fprintf(o, "%s%u", i ? ", " : "", algo.RefusedJobs()[i]->job_id);
+  fprintf(o, "], \"cancel\": [");
+  for (size_t i = 0; i < algo.LastPreemptCancel().size(); ++i) fprintf(o, "%s%u", i ? ", " : "", algo.LastPreemptCancel()[i]);
+  fprintf(o, "], \"preempting\": [");
+  bool first = true;
+  for (job_id_t id : algo.PreemptingSet()) { fprintf(o, "%s%u", first ? "" : ", ", id); first = false; }
+  fprintf(o, "]}\n");
+}
+
+// The objects of a cycle back as cns_placement_soa records (start, reason code, node_num records per job: the placed nodes in craned_ids
+// order, then CNS_NODE_NONE), through the snapshot's name -> dense index map and its GRES layout (classes in (name, type) order, a class
+// as wide as the union of its slot ids, bits in std::set<SlotId> order).  Raw little-endian arrays, one after the other: start_sec i64[J],
+// reason u8[J], place_offsets u64[J+1], node_idx u32[M], ntasks u32[M], cpu_raw i64[M], mem u64[M], core_lo u64[M], core_hi u64[M], gres u64[M].
+static bool write_soa(const char* path, const ClusterSnapshot& snap, const std::vector<std::unique_ptr<PdJobInScheduler>>& pending) {
+  std::unordered_map<CranedId, uint32_t> idx;
+  for (size_t n = 0; n < snap.craned_metas.size(); ++n) idx[snap.craned_metas[n].craned_id] = (uint32_t)n;
+  std::map<std::pair<std::string, std::string>, std::set<SlotId>> cls;
+  for (const auto& m : snap.craned_metas)
+    for (const auto& [name, tm] : m.res_total.gres)
+      for (const auto& [type, slots] : tm) cls[{name, type}].insert(slots.begin(), slots.end());
+  std::map<std::pair<std::string, std::string>, std::map<SlotId, uint32_t>> bit;
+  uint32_t shift = 0;
+  for (const auto& [key, slots] : cls) for (const auto& sl : slots) bit[key][sl] = shift++;
+  const std::map<std::string, uint8_t> code{{"", 0}, {"Priority", 1}, {"Resource", 2}, {"Resource Reserved", 3}, {"Partition Not Found", 4},
+                                            {"Reservation Not Found", 6}, {"Preempted", 7}, {"GpuEngineRefused", 8}};
+  const size_t J = pending.size();
+  std::vector<int64_t> start(J), cpu;
+  std::vector<uint8_t> reason(J);
+  std::vector<uint64_t> off(J + 1, 0), mem, lo, hi, g;
+  std::vector<uint32_t> node, nt;
+  for (size_t j = 0; j < J; ++j) {
+    const PdJobInScheduler& p = *pending[j];
+    start[j] = p.start_time;
+    auto c = code.find(p.reason);
+    reason[j] = c == code.end() ? 5 : c->second;   // a reason of the caller's own: CNS_REASON_SKIPPED
+    for (const auto& cid : p.craned_ids) {
+      const ResourceInNodeV3& r = p.allocated_res.at(cid);
+      uint64_t l = 0, h = 0, gm = 0;
+      for (uint32_t id : r.cpu_set.core_ids) (id < 64 ? l : h) |= 1ull << (id % 64);
+      for (const auto& [name, tm] : r.gres)
+        for (const auto& [type, slots] : tm)
+          for (const auto& sl : slots) gm |= 1ull << bit.at({name, type}).at(sl);
+      node.push_back(idx.at(cid)); nt.push_back(p.craned_id_to_task_num.at(cid)); cpu.push_back(r.cpu_set.cpu_count.raw); mem.push_back(r.memory_bytes);
+      lo.push_back(l); hi.push_back(h); g.push_back(gm);
+    }
+    for (size_t q = p.craned_ids.size(); q < p.node_num; ++q) {
+      node.push_back(CNS_NODE_NONE); nt.push_back(0); cpu.push_back(0); mem.push_back(0); lo.push_back(0); hi.push_back(0); g.push_back(0);
+    }
+    off[j + 1] = node.size();
+  }
+  FILE* o = fopen(path, "wb");
+  if (!o) return false;
+  auto put = [&](const auto& v) { if (!v.empty()) fwrite(v.data(), sizeof(v[0]), v.size(), o); };
+  put(start); put(reason); put(off); put(node); put(nt); put(cpu); put(mem); put(lo); put(hi); put(g);
+  return fclose(o) == 0;
+}
+
+static bool set_write_back_mode(GpuNodeSelectionAlgo& algo, const std::string& mode) {
+  if (mode == "lazy") return true;
+  if (mode == "full") { algo.SetFullWriteBack(true); return true; }
+  if (mode == "deferred") { algo.SetDeferredWriteBack(true); return true; }
+  return false;
+}
+
+// --case-pack IN OUT: the arrays the adapter would hand to the engine for the case, one "name v0 v1 ..." line each (no device needed)
+static int case_pack(const char* in, const char* outp) {
+  Case c;
+  if (!read_case(in, c)) { printf("cannot read case %s\n", in); return 2; }
+  GpuNodeSelectionAlgo algo(std::vector<int>{0});
+  algo.SetClusterSnapshot(c.snap);
+  std::map<std::string, std::vector<uint64_t>> arr;
+  algo.PackedArraysForTest(c.running, c.pending, &arr);
+  FILE* o = fopen(outp, "w");
+  if (!o) return 2;
+  for (const auto& [name, v] : arr) {
+    fprintf(o, "%s", name.c_str());
+    for (uint64_t x : v) fprintf(o, " %llu", (unsigned long long)x);
+    fprintf(o, "\n");
+  }
+  fclose(o);
+  printf("ok\n");
+  return 0;
+}
+
+// --case-write-back IN PLACEMENTS OUT [--write-back lazy|full|deferred]: the adapter's write-back of placements the caller gives
+// ("J", then per job "start reason k" and k records "node ntasks cpu mem lo hi gres w2 w3"); no device needed
+static int case_write_back(const char* in, const char* plc, const char* outp, const std::string& mode) {
+  Case c;
+  if (!read_case(in, c)) { printf("cannot read case %s\n", in); return 2; }
+  GpuNodeSelectionAlgo algo(std::vector<int>{0});
+  if (!set_write_back_mode(algo, mode)) { printf("bad --write-back %s\n", mode.c_str()); return 2; }
+  algo.SetClusterSnapshot(c.snap);
+  FILE* f = fopen(plc, "r");
+  if (!f) return 2;
+  GpuNodeSelectionAlgo::PlacementsForTest p;
+  unsigned long long J = 0;
+  if (fscanf(f, "%llu", &J) != 1 || J != c.pending.size()) { fclose(f); printf("placements do not match the case\n"); return 2; }
+  p.place_offsets.push_back(0);
+  for (unsigned long long j = 0; j < J; ++j) {
+    long long st; unsigned rs; unsigned long long k;
+    if (fscanf(f, "%lld %u %llu", &st, &rs, &k) != 3) { fclose(f); return 2; }
+    p.start_sec.push_back(st); p.reason.push_back((uint8_t)rs);
+    for (unsigned long long q = 0; q < k; ++q) {
+      unsigned nd, nt; long long cpu; unsigned long long mem, lo, hi, g, w2, w3;
+      if (fscanf(f, "%u %u %lld %llu %llu %llu %llu %llu %llu", &nd, &nt, &cpu, &mem, &lo, &hi, &g, &w2, &w3) != 9) { fclose(f); return 2; }
+      p.node_idx.push_back(nd); p.ntasks.push_back(nt); p.cpu_raw.push_back(cpu); p.mem.push_back(mem);
+      p.core_lo.push_back(lo); p.core_hi.push_back(hi); p.gres.push_back(g); p.core_w2.push_back(w2); p.core_w3.push_back(w3);
+    }
+    p.place_offsets.push_back(p.node_idx.size());
+  }
+  fclose(f);
+  algo.WriteBackForTest(c.pending, p);
+  if (mode == "deferred")
+    for (const auto& j : c.pending) if (j->reason.empty()) algo.MaterializeAllocation(*j);
+  FILE* o = fopen(outp, "w");
+  if (!o) return 2;
+  dump_jobs(o, c.pending);
+  fclose(o);
+  printf("ok\n");
+  return 0;
+}
+
+// --case-file IN OUT [--write-back lazy|full|deferred] [--devices 0,0] [--batch N] [--mirror] [--then IN2 OUT2]: NodeSelect on the
+// case as CraneCtld calls it; --mirror feeds the running jobs through MallocResourceFromNode / SetRunningJobInfo and calls
+// NodeSelect(now, pending).  --then: a second cycle on the same object — the snapshot is NOT set again, the nodes whose alive / drain
+// state differs in IN2 are flipped with SetCranedState, and IN2's running / pending jobs are used (on the mirror: the running jobs IN2
+// adds are fed to it, the ones it drops are freed).
+static int case_file(int argc, char** argv) {
+  const char* in = argv[2];
+  const char* outp = argv[3];
+  std::string mode = "lazy";
+  std::vector<int> devices{0};
+  uint64_t batch = 0;
+  bool mirror = false;
+  const char *in2 = nullptr, *out2 = nullptr, *soa = nullptr;
+  for (int a = 4; a < argc; ++a) {
+    if (!strcmp(argv[a], "--write-back") && a + 1 < argc) mode = argv[++a];
+    else if (!strcmp(argv[a], "--devices") && a + 1 < argc) devices = parse_devices(argv[++a]);
+    else if (!strcmp(argv[a], "--batch") && a + 1 < argc) batch = strtoull(argv[++a], nullptr, 10);
+    else if (!strcmp(argv[a], "--mirror")) mirror = true;
+    else if (!strcmp(argv[a], "--soa-out") && a + 1 < argc) soa = argv[++a];
+    else if (!strcmp(argv[a], "--then") && a + 2 < argc) { in2 = argv[a + 1]; out2 = argv[a + 2]; a += 2; }
+    else { printf("unknown argument %s\n", argv[a]); return 2; }
+  }
+  Case c;
+  if (!read_case(in, c)) { printf("cannot read case %s\n", in); return 2; }
+  GpuNodeSelectionAlgo algo(devices, batch);
+  if (!algo.Ok()) { printf("no engine: %s\n", algo.LastError().c_str()); return 3; }
+  if (!set_write_back_mode(algo, mode)) { printf("bad --write-back %s\n", mode.c_str()); return 2; }
+  algo.SetClusterSnapshot(c.snap);
+  if (!algo.Ok()) { printf("SetClusterSnapshot: %s\n", algo.LastError().c_str()); return 3; }
+  std::map<job_id_t, std::vector<CranedId>> mirrored;   // job -> the craneds it was fed to the mirror on
+  auto feed_mirror = [&](const Case& k) {
+    std::set<job_id_t> now_running;
+    for (const auto& r : k.running) {
+      now_running.insert(r->job_id);
+      if (mirrored.count(r->job_id)) continue;
+      auto& on = mirrored[r->job_id];
+      for (const auto& [cid, res] : r->allocated_res) { algo.MallocResourceFromNode(cid, r->job_id, r->allocated_res); on.push_back(cid); }
+      algo.SetRunningJobInfo(r->job_id, r->end_time, r->reservation);
+    }
+    for (auto it = mirrored.begin(); it != mirrored.end();) {   // jobs that ended since: freed on every craned they hold
+      if (now_running.count(it->first)) { ++it; continue; }
+      for (const auto& cid : it->second) algo.FreeResourceFromNode(cid, it->first);
+      it = mirrored.erase(it);
+    }
+  };
+  auto cycle = [&](const Case& k, const char* path) -> bool {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (mirror) { feed_mirror(k); algo.NodeSelect(k.now, k.pending); }
+    else algo.NodeSelect(k.now, k.running, k.pending);
+    if (mode == "deferred")
+      for (const auto& j : k.pending) if (j->reason.empty()) algo.MaterializeAllocation(*j);
+    const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    double pk = 0, en = 0, wb = 0;
+    algo.LastCycleMs(&pk, &en, &wb);
+    printf("cycle: %zu jobs x %zu nodes, NodeSelect wall %.1f ms (pack %.1f, engine %.1f, write-back %.1f)\n", k.pending.size(),
+           k.snap.craned_metas.size(), wall, pk, en, wb);
+    FILE* o = fopen(path, "w");
+    if (!o) return false;
+    dump_cycle(o, algo, k.pending);
+    fclose(o);
+    return true;
+  };
+  if (!cycle(c, outp)) return 2;
+  if (soa && !write_soa(soa, c.snap, c.pending)) return 2;
+  if (in2) {
+    Case c2;
+    if (!read_case(in2, c2) || c2.snap.craned_metas.size() != c.snap.craned_metas.size()) { printf("cannot read case %s\n", in2); return 2; }
+    for (size_t n = 0; n < c2.snap.craned_metas.size(); ++n) {
+      const CranedMeta &a = c.snap.craned_metas[n], &b = c2.snap.craned_metas[n];
+      if (a.alive != b.alive || a.drain != b.drain) algo.SetCranedState(b.craned_id, b.alive, b.drain);
+    }
+    if (!cycle(c2, out2)) return 2;
+  }
+  printf("ok\n");
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 3 && !strcmp(argv[1], "--case-file")) return case_file(argc, argv);
+  if (argc > 3 && !strcmp(argv[1], "--case-pack")) return case_pack(argv[2], argv[3]);
+  if (argc > 4 && !strcmp(argv[1], "--case-write-back")) return case_write_back(argv[2], argv[3], argv[4], argc > 6 && !strcmp(argv[5], "--write-back") ? argv[6] : "lazy");
   if (argc > 1 && !strcmp(argv[1], "--cycle-bench")) return cycle_bench(argc > 2 ? atoi(argv[2]) : 16384, argc > 3 ? atoi(argv[3]) : 200000, argc > 4 ? atoi(argv[4]) : 1);
   if (argc > 1 && !strcmp(argv[1], "--e2e-bench")) {   // ... [--devices 0,0] at the end: several engines (cns_group)
     std::vector<int> dev{0};

@@ -135,6 +135,37 @@ def test_group_with_reservations(classes):
         g.close()
 
 
+@pytest.mark.parametrize("devices", [[0], [0, 0]])
+def test_group_accepts_an_empty_queue_with_null_job_arrays(classes, devices):
+    """An empty queue whose job arrays were never filled (null pointers, num_jobs = 0) is what an adapter hands over on an empty first
+    cycle; cns_select accepts it (engine.hip guards with `J &&`), so cns_group_select must too: an all-empty result, also
+    as the first cycle after set_nodes and between two non-empty cycles."""
+    import ctypes as C
+    from cranesched_amd import abi
+    GpuNodeSelector, Group = classes
+    cluster, jobs, now = synth.make_config("C3", J=2000, N=512, P=1)
+    ref, _ = _single(GpuNodeSelector, cluster, jobs, now)
+    g = Group(devices)
+    try:
+        g.set_nodes(cluster)
+
+        def empty_cycle():
+            out = abi.Placements(0, 0)
+            out.place_offsets[0] = 77                 # must be written
+            cj, co = abi.CnsJobSoa(), out.to_c()      # num_jobs = 0, every job array NULL
+            rc = g._L.cns_group_select(g._g, C.c_int64(now), C.byref(cj), C.byref(co))
+            msg = g._L.cns_group_last_error(g._g)
+            assert rc == 0, (rc, msg.decode() if msg else "")
+            assert int(out.place_offsets[0]) == 0
+
+        empty_cycle()
+        assert g.node_select(now, jobs).diff(ref) is None
+        empty_cycle()
+        assert g.node_select(now, jobs).diff(ref) is None
+    finally:
+        g.close()
+
+
 @pytest.mark.parametrize("devices", [[0, 0], [0, 0, 0]])
 def test_group_applies_the_batch_limit_once(classes, devices):
     """ScheduledBatchSize cuts the ONE ordered queue (BasicPriority::GetOrderedJobPtrVec, JobScheduler.h:185-200): a group must not let every
