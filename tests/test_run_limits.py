@@ -193,11 +193,13 @@ def test_oracle_non_candidates_and_order():
     assert list(reason) == [255, 255, 255, 255] and adm == 0
 
 
-def random_limit_case(seed, J=600, N=96, tight=True):
-    """Random cluster / queue (tests.helpers) + a random account tree, QoS set, partition limits, initial usage."""
+def random_limit_case(seed, J=600, N=96, tight=True, case=None):
+    """Random cluster / queue (tests.helpers; `case`: a (cluster, jobs, now, running) of its own, e.g. tests.gres_wide) + a random account
+    tree, QoS set, partition limits with GRES limits on every name and class of the layout, initial usage."""
     rng = np.random.default_rng(seed + 7000)
-    cluster, jobs, now, _ = helpers.random_case(seed, N=N, J=J, P=2, running=0)
+    cluster, jobs, now, _ = helpers.random_case(seed, N=N, J=J, P=2, running=0) if case is None else case
     lay = cluster.gres
+    nn, nc = max(lay.class_name) + 1, len(lay.class_name)
     U, A, Q, Pn = 7, 6, 3, 2
     parent = [NONE, 0, 0, 1, 3, NONE][:A]           # two trees, depth up to 4 (a4 -> a3 -> a1 -> a0)
     ua_pairs = [(u, int(a)) for u in range(U) for a in rng.choice(A, rng.integers(1, 3), replace=False)]
@@ -207,8 +209,8 @@ def random_limit_case(seed, J=600, N=96, tight=True):
     def rtres(scale):
         if rng.random() < 0.3:
             return lm.unlimited_tres()
-        names = {int(n): int(rng.integers(1, 6 * scale)) for n in range(2) if rng.random() < 0.5}
-        classes = {int(g): int(rng.integers(1, 4 * scale)) for g in range(3) if rng.random() < 0.4}
+        names = {int(n): int(rng.integers(1, 6 * scale)) for n in range(nn) if rng.random() < 0.5}
+        classes = {int(g): int(rng.integers(1, 4 * scale)) for g in range(nc) if rng.random() < 0.4}
         return lm.tres(cpu=int(rng.integers(8, 64 * scale)) if rng.random() < 0.7 else None,
                        mem=int(rng.integers(32, 256 * scale)) * GIB if rng.random() < 0.5 else None, names=names, classes=classes)
 
@@ -232,7 +234,7 @@ def random_limit_case(seed, J=600, N=96, tight=True):
         u["mem"] = np.where(on, rng.integers(0, 16, n) * GIB, 0)
         u["wall_sec"] = np.where(on, rng.integers(0, 5000, n), 0)
         u["jobs_count"] = np.where(on, rng.integers(0, 3, n), 0)
-        for g in range(3):
+        for g in range(nc):
             c = np.where(on & (rng.random(n) < 0.3), rng.integers(0, 3, n), 0)
             u["class_count"][:, g] = c
             u["name_total"][:, lay.class_name[g]] += c.astype(np.uint64)
