@@ -21,6 +21,7 @@
 #include "../../include/crane_gpu/node_select.h"
 #include "../../include/crane_gpu/preempt.h"
 #include "../../include/crane_gpu/priority.h"
+#include "../../include/crane_gpu_probe/probe.h"
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
 #include <limits>
@@ -30,6 +31,7 @@
 #include "priority_kernels.hip"
 #include "limits_kernels.hip"
 #include "steps_kernels.hip"
+#include "probe_kernel.inc"    // k_probe: what-if probes against the final state of a cycle (include/crane_gpu_probe/probe.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 
 using namespace cns;
@@ -141,6 +143,16 @@ struct cns_engine {
   const u64* place_off = nullptr;               // [J + 1] first placement record per job (in h_place)
   struct ResOff { size_t start, cpu, mem, clo, chi, gres, node, ntasks, reason, c2, c3, total; } ro{};
   bool wide_cores = false;   // a node of the snapshot has a core id above 127: the results carry the core_w2 / core_w3 planes
+  // what-if probes against the final state of the last cycle (probe_host.inc): table, results and scratch in buffers of their own
+  DevBuf d_pb[28];
+  ResOff pro{};
+  u64 pJ = 0, pJg = 0, pplaces = 0;             // probes of the last cns_probe_upload, those that reach a walk, their placement records
+  u32 pkmax = 1;                                // ... and their widest node_num
+  std::vector<u64> probe_place_off;             // [pJ + 1]
+  bool have_probes = false, probes_answered = false;
+  bool pre_call = false;                        // inside cns_select_preempt with preemption enabled
+  bool run_preempt = false;                     // the last successful cycle was such a call (probes are not served behind it)
+  double probe_ms = 0.0;
   cns_timing timing{};
   std::string last_kernel;
   i64 last_now = 0;
@@ -690,6 +702,7 @@ void cns_destroy(cns_handle* h) {
   for (DevBuf& b : h->d_limpar) b.release();
   for (DevBuf& b : h->d_step) b.release();
   for (DevBuf& b : h->d_pre) b.release();
+  for (DevBuf& b : h->d_pb) b.release();
   h->d_gather.release();
   if (h->comm) (void)ncclCommDestroy((ncclComm_t)h->comm);
   for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
@@ -1147,6 +1160,7 @@ enum { B_QPOFF, B_QP, B_PJQOS, B_PJQP, B_PJPRIO, B_PJREC0, B_PJK, B_PJEND, B_RNJ
 // One pass of the cycle on the device.  *fault_code: the device fault it ended with (0: none).
 static int run_resident_once(cns_handle* h, int64_t now, u32* fault_code) {
   *fault_code = 0;
+  h->have_probes = h->probes_answered = false;   // (probes are routed against the snapshot of the cycle they follow)
   HIPCHK(h, hipSetDevice(h->device));
   KParams K;
   fill_params(h, K, now);
@@ -1310,6 +1324,7 @@ static int run_resident_once(cns_handle* h, int64_t now, u32* fault_code) {
                                              std::to_string(fault[3]) + " (" + h->last_kernel + ")");
   }
   h->have_run = true;
+  h->run_preempt = h->pre_call;
   return CNS_OK;
 }
 
@@ -1442,6 +1457,8 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
   }
   if (!jobs || !out || !pout) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: null argument");
   if (!h->have_nodes) return fail(h, CNS_ERR_STATE, "cns_select_preempt before cns_set_nodes");
+  struct PreCall { cns_engine* h; ~PreCall() { h->pre_call = false; } } pre_call{h};   // (run_resident_once notes it: cns_probe refuses such a state)
+  h->pre_call = true;
   const u64 J = jobs->num_jobs;
   const u32 R = h->R;
   if (J && (!pre->pd_qos || !pre->pd_qos_priority || !pre->pd_priority)) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: missing pending-job array");
@@ -1713,6 +1730,7 @@ int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity
 #include "priority_host.inc"
 #include "limits_host.inc"
 #include "steps_host.inc"
+#include "probe_host.inc"
 
 }  // extern "C"
 

@@ -41,6 +41,8 @@ PRIORITY_ABI_SYMBOLS = ("cns_priority_order", "cns_priority_timing")
 STEPS_ABI_SYMBOLS = ("cns_schedule_steps",)
 # ... and include/crane_gpu/preempt.h
 PREEMPT_ABI_SYMBOLS = ("cns_select_preempt",)
+# ... and include/crane_gpu_probe/probe.h
+PROBE_ABI_SYMBOLS = ("cns_probe", "cns_probe_upload", "cns_probe_run_resident", "cns_probe_download")
 LIMITS_ABI_SYMBOLS = ("cns_set_run_limits", "cns_apply_run_limits", "cns_upload_limit_jobs", "cns_run_limits_resident",
                       "cns_download_limits", "cns_get_limit_timing", "cns_get_usage")
 
@@ -323,6 +325,41 @@ class GpuNodeSelector:
         co = out.to_c()
         self._check(self._L.cns_download(self._h, C.byref(co)))
         return out
+
+    # -- what-if probes against the final state of the last cycle (include/crane_gpu_probe/probe.h) ------------------------
+    def probe(self, probes: abi.Jobs) -> abi.Placements:
+        """When and where would each of `probes` run if it were submitted now?  Per probe what the cycle would have written for it
+        behind the last job its ordered loop took, at the cycle's `now`; nothing is committed.  After a successful node_select /
+        run_resident only (EngineError CNS_ERR_STATE otherwise; CNS_ERR_UNSUPPORTED after a cycle with preemption)."""
+        out = abi.Placements(probes.num_jobs, probes.total_places())
+        cj, co = probes.to_c(), out.to_c()
+        ms = C.c_double(0)
+        self._check(self._L.cns_probe(self._h, C.byref(cj), C.byref(co), C.byref(ms)))
+        self._probe_ms = ms.value
+        return out
+
+    # split form: probes resident in HBM before the timed region (tools/probe_bench.py)
+    def probe_upload(self, probes: abi.Jobs):
+        cj = probes.to_c()
+        self._check(self._L.cns_probe_upload(self._h, C.byref(cj)))
+        self._probes = probes
+
+    def probe_run_resident(self) -> float:
+        """Answers the uploaded probes (again); -> HIP-event time of k_probe in ms."""
+        ms = C.c_double(0)
+        self._check(self._L.cns_probe_run_resident(self._h, C.byref(ms)))
+        self._probe_ms = ms.value
+        return ms.value
+
+    def probe_download(self) -> abi.Placements:
+        out = abi.Placements(self._probes.num_jobs, self._probes.total_places())
+        co = out.to_c()
+        self._check(self._L.cns_probe_download(self._h, C.byref(co)))
+        return out
+
+    def probe_timing(self) -> dict:
+        """HIP-event time of the last k_probe launch of this object."""
+        return {"kernel_ms": getattr(self, "_probe_ms", 0.0)}
 
     def device_results(self):
         p, n = C.c_void_p(), C.c_uint64()

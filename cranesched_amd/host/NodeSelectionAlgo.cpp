@@ -17,6 +17,7 @@
 #include "../../include/crane_gpu/priority.h"
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
+#include "../../include/crane_gpu_probe/probe.h"
 
 namespace crane {
 
@@ -1239,6 +1240,53 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
   const auto tp3 = std::chrono::steady_clock::now();
   I.t_engine_ms = std::chrono::duration<double, std::milli>(tp2 - tp1).count();
   I.t_write_ms = std::chrono::duration<double, std::milli>(tp3 - tp2).count();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// What-if probes (include/crane_gpu_probe/probe.h)
+// ---------------------------------------------------------------------------------------------------------
+void GpuNodeSelectionAlgo::ProbeStart(const std::vector<PdJobInScheduler*>& jobs) {
+  Impl& I = *impl_;
+  auto fail_all = [&](int st, const std::string& msg) {
+    status_ = st; error_ = msg;
+    for (PdJobInScheduler* j : jobs) if (j->reason.empty()) j->reason = "GpuEngineError";
+  };
+  if (I.grp) return fail_all(CNS_ERR_UNSUPPORTED, "ProbeStart on an algorithm object over several devices: probe the device that owns the partition (cns_group_handle)");
+  if (!I.h) return fail_all(status_ ? status_ : CNS_ERR_NO_DEVICE, error_);
+  if (!I.have_snapshot) return fail_all(CNS_ERR_STATE, "ProbeStart before SetClusterSnapshot");
+  const size_t Q = jobs.size();
+  if (Q == 0) { status_ = 0; error_.clear(); return; }
+  // the packer of the cycle, into a table of the probes' own (the cycle's packed table and placements stay: MaterializeAllocation,
+  // the wire emission)
+  Impl::PackedJobs B(nullptr);
+  I.pack_pending(jobs, B);
+  uint64_t places = 0;
+  for (const PdJobInScheduler* j : jobs) places += j->node_num;
+  cns_job_soa js{};
+  js.num_jobs = Q;
+  js.partition = B.part.data(); js.time_limit_sec = B.L.data(); js.node_cpu_raw = B.ncpu.data(); js.node_mem = B.nmem.data();
+  js.task_cpu_raw = B.tcpu.data(); js.task_mem = B.tmem.data(); js.node_num = B.k.data(); js.ntasks = B.nt.data();
+  js.ntasks_per_node_min = B.tmin.data(); js.ntasks_per_node_max = B.tmax.data(); js.exclusive = B.excl.data();
+  js.gres_total = B.gtot.data(); js.gres_spec = B.gspec.data(); js.incl_offsets = B.ioff.data(); js.incl_nodes = B.inodes.data();
+  js.excl_offsets = B.eoff.data(); js.excl_nodes = B.enodes.data(); js.skip = B.skip.data(); js.reservation = B.jresv.data();
+  std::vector<int64_t> start(Q + 1, 0), cpu(places + 1, 0);
+  std::vector<uint8_t> reason(Q + 1, 0);
+  std::vector<uint64_t> off(Q + 1, 0), mem(places + 1, 0), lo(places + 1, 0), hi(places + 1, 0), g(places + 1, 0), w2(places + 1, 0), w3(places + 1, 0);
+  std::vector<uint32_t> node(places + 1, CNS_NODE_NONE), nt(places + 1, 0);
+  cns_placement_soa out{};
+  out.place_capacity = places;
+  out.start_sec = start.data(); out.reason = reason.data(); out.place_offsets = off.data();
+  out.node_idx = node.data(); out.ntasks = nt.data(); out.cpu_raw = cpu.data(); out.mem = mem.data();
+  out.core_lo = lo.data(); out.core_hi = hi.data(); out.gres = g.data(); out.core_w2 = w2.data(); out.core_w3 = w3.data();
+  const int st = cns_probe(I.h, &js, &out, nullptr);
+  if (st != 0) return fail_all(st, cns_last_error(I.h));
+  status_ = 0;
+  error_.clear();
+  // always the full write-back, whatever mode the cycle runs in: a probe's answer IS its node list and allocation
+  const bool lazy = I.lazy_write_back, deferred = I.deferred_write_back;
+  I.lazy_write_back = false; I.deferred_write_back = false;
+  I.write_back(jobs, out);
+  I.lazy_write_back = lazy; I.deferred_write_back = deferred;
 }
 
 // ---------------------------------------------------------------------------------------------------------

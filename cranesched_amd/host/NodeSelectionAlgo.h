@@ -342,6 +342,18 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   void NodeSelect(const TimeSec& now, const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs,
                   const std::vector<std::unique_ptr<PdJobInScheduler>>& pending_jobs) override;
 
+  // ---- what-if probes (include/crane_gpu_probe/probe.h; the reference has no such call) -------------------------------------
+  // "When and where would THIS job run if it were submitted now?" for every job of `jobs`, independently of each other, against the
+  // final state of the last NodeSelect: per job exactly what that cycle would have written for it behind the last job its ordered
+  // loop took — and nothing is committed, the cycle's own results (MaterializeAllocation, the wire emission, RefusedJobs) stay.
+  // The jobs are packed by the packer of the cycle (same name tables, same GRES class order, unknown include names as in NodeSelect;
+  // no sorter, no license pre-pass: probes are questions, not the queue).  Written into the objects handed in, and nowhere else:
+  // reason, start_time, end_time, craned_ids, craned_id_to_task_num, allocated_res — always in full, whatever write-back mode the
+  // cycle runs in; a job that comes with a reason keeps it and is not asked.  On an engine error (no cycle yet, a cycle with
+  // preemption, no device) the jobs without a reason get "GpuEngineError" and Ok() / LastStatus() / LastError() say why; nothing is
+  // thrown.  One device only: an algorithm object built over several devices refuses with CNS_ERR_UNSUPPORTED.
+  void ProbeStart(const std::vector<PdJobInScheduler*>& jobs);
+
   // ---- event-fed mirror of the running allocations -------------------------------------------------
   // Instead of re-deriving the running jobs' allocations from the vector NodeSelect is handed every cycle, the adapter
   // can be told what the meta container is told: the same calls, at the same places (JobScheduler.cpp:1590-1612 for the

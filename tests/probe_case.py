@@ -1,0 +1,177 @@
+"""The yardstick of the what-if probes (include/crane_gpu_probe/probe.h).
+
+By definition the answer for probe q is what NodeSelect writes for q when q is appended behind the last job the ordered loop of the
+cycle took.  `expected` computes exactly that, one oracle cycle per probe: `ordered jobs + [probe]` with batch size 0, result of the
+last job.  backend "oracle" is the restated oracle, "ref" the reference's own compiled NodeSelect (oracle/_ref) — the expected value
+never comes from the engine."""
+from __future__ import annotations
+
+import numpy as np
+
+from cranesched_amd import abi
+from oracle import pyoracle
+
+_DEFAULT = {"node_cpu_raw": 0, "exclusive": 0, "skip": 0, "reservation": abi.RESV_NONE}
+_PLAIN = ("partition", "time_limit_sec", "node_mem", "task_cpu_raw", "task_mem", "node_num", "ntasks", "ntasks_per_node_min",
+          "ntasks_per_node_max", "node_cpu_raw", "exclusive", "skip", "reservation")
+
+
+def take(jobs: abi.Jobs, idx) -> abi.Jobs:
+    """The jobs `idx` (any order, repeats allowed) as a job table of their own, CSR lists included."""
+    idx = np.asarray(idx, np.int64)
+    kw = {}
+    for f in _PLAIN + ("gres_total", "gres_spec"):
+        v = getattr(jobs, f)
+        kw[f] = None if v is None else v[idx].copy()
+    for off, lst in (("incl_offsets", "incl_nodes"), ("excl_offsets", "excl_nodes")):
+        o = getattr(jobs, off)
+        if o is None:
+            kw[off] = kw[lst] = None
+            continue
+        nodes = getattr(jobs, lst)
+        parts = [nodes[int(o[i]):int(o[i + 1])] for i in idx]
+        kw[off] = np.cumsum([0] + [len(p) for p in parts]).astype(np.uint64)
+        flat = np.concatenate(parts).astype(np.uint32) if parts else np.zeros(0, np.uint32)
+        kw[lst] = flat if len(flat) else np.zeros(1, np.uint32)
+    return abi.Jobs(**kw)
+
+
+def concat(a: abi.Jobs, b: abi.Jobs) -> abi.Jobs:
+    """a followed by b (abi.Jobs has no concatenation: the optional arrays and the CSR lists are filled in where one side lacks them)."""
+    ja, jb = a.num_jobs, b.num_jobs
+    kw = {}
+    for f in _PLAIN:
+        va, vb = getattr(a, f), getattr(b, f)
+        if va is None and vb is None:
+            kw[f] = None
+            continue
+        dt = (va if va is not None else vb).dtype
+        va = np.full(ja, _DEFAULT[f], dt) if va is None else va
+        vb = np.full(jb, _DEFAULT[f], dt) if vb is None else vb
+        kw[f] = np.concatenate([va, vb])
+    for f, w in (("gres_total", abi.MAX_GRES_NAMES), ("gres_spec", abi.MAX_GRES_CLASSES)):
+        va, vb = getattr(a, f), getattr(b, f)
+        if va is None and vb is None:
+            kw[f] = None
+            continue
+        va = np.zeros((ja, w), np.uint8) if va is None else va
+        vb = np.zeros((jb, w), np.uint8) if vb is None else vb
+        kw[f] = np.concatenate([va, vb])
+    for off, lst in (("incl_offsets", "incl_nodes"), ("excl_offsets", "excl_nodes")):
+        oa, ob = getattr(a, off), getattr(b, off)
+        if oa is None and ob is None:
+            kw[off] = kw[lst] = None
+            continue
+        oa = np.zeros(ja + 1, np.uint64) if oa is None else oa
+        ob = np.zeros(jb + 1, np.uint64) if ob is None else ob
+        na = getattr(a, lst)[:int(oa[-1])] if getattr(a, off) is not None else np.zeros(0, np.uint32)
+        nb = getattr(b, lst)[:int(ob[-1])] if getattr(b, off) is not None else np.zeros(0, np.uint32)
+        kw[off] = np.concatenate([oa, ob[1:] + oa[-1]]).astype(np.uint64)
+        flat = np.concatenate([na, nb]).astype(np.uint32)
+        kw[lst] = flat if len(flat) else np.zeros(1, np.uint32)
+    return abi.Jobs(**kw)
+
+
+def ordered(jobs: abi.Jobs, batch: int = 0) -> abi.Jobs:
+    """The jobs the ordered loop takes: all of them, or the first `batch` (BasicPriority, JobScheduler.h:185-200)."""
+    if not batch or batch >= jobs.num_jobs:
+        return jobs
+    return take(jobs, np.arange(batch))
+
+
+def expected(cluster, jobs, probes, now, running=None, reservations=None, batch=0, backend="oracle", **cfg) -> abi.Placements:
+    """Per probe i: one cycle over `ordered jobs + [probe i]` with batch size 0; what it wrote for the last job.  -> the probes' Placements."""
+    base = ordered(jobs, batch)
+    Q = probes.num_jobs
+    out = abi.Placements(Q, probes.total_places())
+    off = np.concatenate([[0], np.cumsum(probes.node_num.astype(np.uint64))]).astype(np.uint64)
+    out.place_offsets[:Q + 1] = off
+    for i in range(Q):
+        q = concat(base, take(probes, [i]))
+        run = pyoracle.select(cluster, q, now, running=running, reservations=reservations, scheduled_batch_size=0, backend=backend, **cfg)
+        pl = run.placements
+        last = q.num_jobs - 1
+        out.start_sec[i] = pl.start_sec[last]
+        out.reason[i] = pl.reason[last]
+        a, b = int(pl.place_offsets[last]), int(pl.place_offsets[last + 1])
+        o = int(off[i])
+        for f in ("node_idx", "ntasks", "cpu_raw", "mem", "core_lo", "core_hi", "gres", "core_w2", "core_w3"):
+            getattr(out, f)[o:o + (b - a)] = getattr(pl, f)[a:b]
+        run.close()
+    return out
+
+
+def outcome_mix(exp: abi.Placements, probes: abi.Jobs, now: int) -> dict:
+    """What the oracle answered, counted: the coverage condition of the GPU tests is asserted on THESE numbers."""
+    Q = probes.num_jobs
+    r, s = exp.reason[:Q], exp.start_sec[:Q]
+    return {"probes": Q,
+            "now": int(((r == abi.REASON_NONE) & (s == now)).sum()),
+            "later": int((s > now).sum()),
+            "resource_no_start": int(((r == abi.REASON_RESOURCE) & (s == 0)).sum()),
+            "reserved": int((r == abi.REASON_RESOURCE_RESERVED).sum()),
+            "multi_node": int((probes.node_num[:Q] > 1).sum()),
+            "partition_not_found": int((r == abi.REASON_PARTITION_NOT_FOUND).sum()),
+            "skipped": int((r == abi.REASON_SKIPPED).sum())}
+
+
+def add_mix(a: dict, b: dict) -> dict:
+    return {k: a.get(k, 0) + v for k, v in b.items()}
+
+
+def check_mix(m: dict):
+    """The coverage condition over the random_case scenarios (asserted on the oracle's answers)."""
+    Q = m["probes"]
+    assert m["now"] * 4 >= Q, m
+    assert m["later"] * 4 >= Q, m
+    assert m["resource_no_start"] >= 3, m
+    assert m["multi_node"] * 10 >= Q, m
+    assert m["partition_not_found"] >= 1 and m["skipped"] >= 1, m
+
+
+# ---- the scenarios both probe test files use ------------------------------------------------------------------------------------
+RANDOM_SEEDS = (0, 1, 2, 3, 4, 5)
+Q_RANDOM = 40
+
+
+def random_scenario(seed, **kw):
+    """helpers.random_case(seed) and, as probes, the jobs of random_case(1000 + seed, J=40): partitions, node kinds and GRES layout are
+    the same for every seed, so the probes fit the cluster.  -> cluster, jobs, probes, now, running"""
+    from tests import helpers
+    c, j, now, run = helpers.random_case(seed, **kw)
+    pk = {k: v for k, v in kw.items() if k in ("general", "lists", "exclusive", "frac", "P", "N")}
+    p = helpers.random_case(1000 + seed, J=Q_RANDOM, **pk)[1]
+    return c, j, p, now, run
+
+
+def resv_scenario(seed=0, Q=Q_RANDOM):
+    """test_reservations.random_resv_case and probes from its generator with another seed (a quarter of them into reservations)."""
+    from tests.test_reservations import random_resv_case
+    c, j, now, run, rv = random_resv_case(seed)
+    p = take(random_resv_case(100 + seed)[1], np.arange(Q))
+    return c, j, p, now, run, rv
+
+
+def overlap_scenario(seed=1, Q=Q_RANDOM, layout="all+subsets"):
+    """test_overlap.overlap_case (partitions that share nodes) and probes from its generator with another seed."""
+    from tests.test_overlap import overlap_case
+    c, j, now, run = overlap_case(seed, layout=layout)
+    p = take(overlap_case(100 + seed, layout=layout)[1], np.arange(Q))
+    return c, j, p, now, run
+
+
+def reserved_kat():
+    """Hand-made: one 8-core node with a reservation of 6 cores that begins in 1000 s; a 4-core probe of 3600 s cannot run in front of
+    it (its window reaches the reservation) and starts when the reservation ends, 'Resource Reserved' (JobScheduler.cpp:6799-6806).
+    -> cluster, jobs, probes, now, running, reservations, (start, reason) of the probe"""
+    from cranesched_amd import synth
+    now = synth.NOW
+    G = 1 << 30
+    c = abi.Cluster(np.array([8 * 256], np.int64), np.array([32 * G], np.uint64), np.array([0xFF], np.uint64), np.array([0], np.uint64),
+                    np.array([0], np.uint64), np.array([0, 1], np.uint32), np.array([0], np.uint32))
+    rv = abi.Reservations([now + 1000], [now + 5000], [0, 1], [0], [6 * 256], [8 * G], [0x3F], [0], [0])
+
+    def job(cpus, L):
+        return abi.Jobs(partition=[0], time_limit_sec=[L], node_mem=[0], task_cpu_raw=[cpus * 256], task_mem=[G], node_num=[1], ntasks=[1],
+                        ntasks_per_node_min=[1], ntasks_per_node_max=[1])
+    return c, job(2, 600), job(4, 3600), now, None, rv, (now + 5000, abi.REASON_RESOURCE_RESERVED)
