@@ -5,6 +5,7 @@
 // known answers of tests/kat.py (scenarios A, B and F).
 //   test_host_adapter            -> needs an MI355X, exit 0 on success
 //   test_host_adapter --no-gpu   -> checks the loud "no device" behaviour instead
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -936,7 +937,77 @@ static int case_file(int argc, char** argv) {
   return 0;
 }
 
+// --prio-file FILE: GpuMultiFactorPriority::GetOrderedJobPtrVec as CraneCtld calls it, cycle after cycle on ONE sorter and on the SAME
+// PdJobInScheduler objects (tests/test_gpu_prio_adapter.py writes the case and compares every cycle with the oracle).  Token stream:
+//   config max_age w_age w_fair w_size w_part w_qos favor_small
+//   cycles C           then C x:
+//     cycle NOW LIMIT
+//     remove K         then K x  id                    (pending jobs that left the queue since the last cycle)
+//     append M         then M x  id account submit qos_priority partition_priority node_num cpu_raw mem
+//     running R        then R x  account node_num nres start qos_priority partition_priority cpu_raw mem
+// A running job gets an allocated_res of `nres` craneds; node_num 0 is what the reference leaves there (JobScheduler.h:70).
+// Per cycle it prints "cycle c", "ordered n id x n", then per pending job in queue order "job id priority-bits-hex reason".
+static int prio_file(const char* path) {
+  FILE* f = fopen(path, "r");
+  if (!f) { printf("cannot read %s\n", path); return 2; }
+  Tok t{f};
+  PriorityConfig pc;
+  t.expect("config");
+  pc.MaxAge = t.u(); pc.WeightAge = (uint32_t)t.u(); pc.WeightFairShare = (uint32_t)t.u(); pc.WeightJobSize = (uint32_t)t.u();
+  pc.WeightPartition = (uint32_t)t.u(); pc.WeightQoS = (uint32_t)t.u(); pc.FavorSmall = t.u() != 0;
+  GpuMultiFactorPriority sorter(pc, 0);
+  if (!sorter.Ok()) { printf("no engine: %s\n", sorter.LastError().c_str()); return 3; }
+  std::vector<std::unique_ptr<PdJobInScheduler>> pending;
+  t.expect("cycles");
+  const uint64_t cycles = t.u();
+  for (uint64_t c = 0; c < cycles && t.ok; ++c) {
+    t.expect("cycle");
+    const TimeSec now = t.i();
+    const uint64_t limit = t.u();
+    t.expect("remove");
+    std::set<job_id_t> gone;
+    for (uint64_t n = t.u(), i = 0; i < n && t.ok; ++i) gone.insert((job_id_t)t.u());
+    pending.erase(std::remove_if(pending.begin(), pending.end(), [&](const auto& j) { return gone.count(j->job_id) != 0; }), pending.end());
+    t.expect("append");
+    for (uint64_t n = t.u(), i = 0; i < n && t.ok; ++i) {
+      auto p = std::make_unique<PdJobInScheduler>();
+      p->job_id = (job_id_t)t.u(); p->account = t.s(); p->submit_time = t.i(); p->qos_priority = (uint32_t)t.u();
+      p->partition_priority = (uint32_t)t.u(); p->node_num = (uint32_t)t.u();
+      p->req_total_res_view.cpu_count = cpu_t::from_raw(t.i()); p->req_total_res_view.memory_bytes = t.u();
+      pending.push_back(std::move(p));
+    }
+    t.expect("running");
+    std::vector<std::unique_ptr<RnJobInScheduler>> running;
+    for (uint64_t n = t.u(), i = 0; i < n && t.ok; ++i) {
+      auto r = std::make_unique<RnJobInScheduler>();
+      r->job_id = (job_id_t)(1000000 + i); r->account = t.s(); r->node_num = (uint32_t)t.u();
+      for (uint64_t k = t.u(), x = 0; x < k && t.ok; ++x) r->allocated_res["cn" + std::to_string(x)] = ResourceInNodeV3{};
+      r->start_time = t.i(); r->end_time = now + 3600; r->qos_priority = (uint32_t)t.u(); r->partition_priority = (uint32_t)t.u();
+      r->allocated_res_view.cpu_count = cpu_t::from_raw(t.i()); r->allocated_res_view.memory_bytes = t.u();
+      running.push_back(std::move(r));
+    }
+    if (!t.ok) break;
+    for (auto& j : pending) j->reason.clear();
+    std::vector<PdJobInScheduler*> ordered;
+    sorter.GetOrderedJobPtrVec(now, pending, running, (size_t)limit, ordered);
+    if (!sorter.Ok()) { printf("GetOrderedJobPtrVec: %s\n", sorter.LastError().c_str()); fclose(f); return 3; }
+    printf("cycle %llu\nordered %zu", (unsigned long long)c, ordered.size());
+    for (const PdJobInScheduler* j : ordered) printf(" %llu", (unsigned long long)j->job_id);
+    printf("\n");
+    for (const auto& j : pending) {
+      uint64_t bits;
+      memcpy(&bits, &j->priority, 8);
+      printf("job %llu %016llx %s\n", (unsigned long long)j->job_id, (unsigned long long)bits, j->reason.empty() ? "-" : j->reason.c_str());
+    }
+  }
+  fclose(f);
+  if (!t.ok) { printf("malformed case %s\n", path); return 2; }
+  printf("ok\n");
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 2 && !strcmp(argv[1], "--prio-file")) return prio_file(argv[2]);
   if (argc > 3 && !strcmp(argv[1], "--case-file")) return case_file(argc, argv);
   if (argc > 3 && !strcmp(argv[1], "--case-pack")) return case_pack(argv[2], argv[3]);
   if (argc > 4 && !strcmp(argv[1], "--case-write-back")) return case_write_back(argv[2], argv[3], argv[4], argc > 6 && !strcmp(argv[5], "--write-back") ? argv[6] : "lazy");

@@ -56,6 +56,10 @@ typedef struct cns_prio_pending_soa {
   const uint64_t* total_mem;          /* [J] req_total_res_view memory bytes                       */
   const uint32_t* account;            /* [J] dense account id < num_accounts                       */
   const double* cached_priority;      /* [J] priority kept from an earlier cycle; 0.0 = compute (cpp:7616); NULL = all 0.0 */
+  /* Any other value is kept verbatim and sorted as a double: negative values, +-inf, denormals and DBL_MAX have their
+   * place in the order (-0.0 == 0.0: computed).  NaN is UNSPECIFIED: the reference's comparator `a->priority > b->priority`
+   * (cpp:7621-7623) is no strict weak order over a range that holds a NaN, so its std::ranges::sort has no defined result to
+   * match; the call stays memory-safe and returns a permutation, but which one is not part of this contract. */
 } cns_prio_pending_soa;
 
 /* Running jobs, vector order (the fp64 service values are accumulated in this order, cpp:7716-7746). */
