@@ -33,6 +33,7 @@
 #include "steps_kernels.hip"
 #include "probe_kernel.inc"    // k_probe: what-if probes against the final state of a cycle (include/crane_gpu_probe/probe.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
+#include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
 
 using namespace cns;
 
@@ -171,8 +172,7 @@ struct cns_engine {
   DevBuf d_gather;
   double gather_ms = 0.0;
   u64 gather_bytes = 0;
-  bool wide_off = false;                        // this run must not use k_wide (the retry after a k_wide protocol fault)
-  bool giant_off = false;                       // ... nor k_giant's helpers (the same retry: k_mem instead)
+  bool pass_waits = false;                      // a kernel the last pass launched has workgroups that wait for each other (k_wide, k_giant)
   u32 wide_retries = 0;                         // cycles that were re-run on k_pipe / k_select after a k_wide fault (lifetime of the handle)
   // MultiFactorPriority (priority_host.inc)
   DevBuf d_prio[27];
@@ -241,7 +241,26 @@ int build_gres(cns_engine* h, const cns_gres_layout& g) {
   return 0;
 }
 
-void fill_params(cns_engine* h, KParams& K, i64 now) {
+// The A/B and test knobs of a run, read from the environment once per cns_run_resident: both passes of a retry see the same values,
+// and there is no other getenv on the selection path.  Numbers: -1 = unset.
+struct RunKnobs {
+  cns_plan::Switch sw = cns_plan::Switch::Unset;   // CNS_SELECT_KERNEL (plan_host.inc: parse_kernel_switch)
+  bool no_retry = false;                           // CNS_WIDE_NO_RETRY=1
+  i64 inject_stall = -1, window = -1, tester_opt = -1, batch_post = -1, aux = -1;   // CNS_WIDE_INJECT_STALL, _WINDOW, _TESTER_OPT, _BATCH_POST, _AUX
+  static RunKnobs read() {
+    auto num = [](const char* name) { const char* e = getenv(name); return e ? (i64)(u32)strtoul(e, nullptr, 10) : (i64)-1; };
+    RunKnobs k;
+    k.sw = cns_plan::parse_kernel_switch(getenv("CNS_SELECT_KERNEL"));
+    const char* nr = getenv("CNS_WIDE_NO_RETRY");
+    k.no_retry = nr && nr[0] == '1';
+    k.inject_stall = num("CNS_WIDE_INJECT_STALL"); k.window = num("CNS_WIDE_WINDOW"); k.tester_opt = num("CNS_WIDE_TESTER_OPT");
+    k.batch_post = num("CNS_WIDE_BATCH_POST"); k.aux = num("CNS_WIDE_AUX");
+    return k;
+  }
+};
+
+// (the probes fill a block without knobs: no selection kernel runs there)
+void fill_params(cns_engine* h, KParams& K, i64 now, const RunKnobs& kn = RunKnobs{}) {
   memset(&K, 0, sizeof K);
   K.num_nodes = h->N; K.num_parts = h->P; K.num_slots = h->S; K.num_types = h->T;
   K.tl_cap = kTlCap;
@@ -249,7 +268,7 @@ void fill_params(cns_engine* h, KParams& K, i64 now) {
   K.max_jobs_per_node = h->cfg.max_job_num_per_node;
   K.now = now;
   K.max_window = h->cfg.max_time_window_sec;
-  if (const char* inj = getenv("CNS_WIDE_INJECT_STALL")) K.wide_inject_stall = (u32)strtoul(inj, nullptr, 10) + 1u;
+  if (kn.inject_stall >= 0) K.wide_inject_stall = (u32)kn.inject_stall + 1u;
   // jobs per pool exchange of k_wide's 64-wave build at most (wide_kernel.inc, "A WINDOW OF JOBS PER EXCHANGE"); 0 / 1: one job per exchange, as in
   // rounds 2-4 — and the kernel WITHOUT the window path is launched (k_wide<NPL, false>: the path's presence costs the single-job loops 8 %).
   // Unless CNS_WIDE_WINDOW says otherwise the QUEUE decides: windows for a queue that is (almost) all one-node jobs without GRES and node lists
@@ -257,13 +276,11 @@ void fill_params(cns_engine* h, KParams& K, i64 now) {
   // whose GRES backfills and multi-node jobs would close every window after two or three jobs (258 against 273 ms):
   // profiles/r05_ab_window_code_presence.txt, DESIGN.md 5.8.
   K.wide_window = (h->jobs_ordered != 0 && h->window_shaped * 100 >= h->jobs_ordered * 95) ? w64::kWJ : 0u;
-  if (const char* ww = getenv("CNS_WIDE_WINDOW")) { const u32 v = (u32)strtoul(ww, nullptr, 10); K.wide_window = v < w64::kWJ ? v : w64::kWJ; }
+  if (kn.window >= 0) K.wide_window = std::min<u32>((u32)kn.window, w64::kWJ);
   if (K.wide_inject_stall) K.wide_window = 0;
-  K.wide_tester_opt = 1;
-  if (const char* to = getenv("CNS_WIDE_TESTER_OPT")) K.wide_tester_opt = (u32)strtoul(to, nullptr, 10);
-  K.wide_aux = 0;   // (sized per launch: launch_wide)
-  K.wide_batch_post = 1;
-  if (const char* bp = getenv("CNS_WIDE_BATCH_POST")) K.wide_batch_post = (u32)strtoul(bp, nullptr, 10);
+  K.wide_tester_opt = kn.tester_opt >= 0 ? (u32)kn.tester_opt : 1u;
+  K.wide_aux = 0;   // (sized per launch: the plan's candidate)
+  K.wide_batch_post = kn.batch_post >= 0 ? (u32)kn.batch_post : 1u;
   K.part_off = h->d_part_off.as<u32>();
   K.slot_node = h->d_slot_node.as<u32>();
   K.slot_total = h->d_slot_total.as<Res>();
@@ -321,214 +338,170 @@ void fill_params(cns_engine* h, KParams& K, i64 now) {
   }
 }
 
-// One launch of a cycle: the partitions it serves (all of them, or the part_map of K), its stream and its copy of the
-// parameter block in HBM (the out-of-line routines read that one).
-struct LaunchCtx {
-  u32 nparts;            // partitions of this launch
-  u32 max_np;            // widest of them (slots)
-  hipStream_t stream;
-  const KParams* dparams;
-  u32 other_blocks;      // workgroups of the cycle's other launch (they hold CUs while k_wide needs all of its own resident)
-};
-template <int NPL>
-void launch_select(cns_engine* h, const KParams& K, const LaunchCtx& L) {
-  hipLaunchKernelGGL((k_select<NPL>), dim3(L.nparts), dim3(kBlock), 0, L.stream, K, L.dparams);
-}
-template <int NPL>
-void launch_pipe(cns_engine* h, const KParams& K, const LaunchCtx& L) {
-  hipLaunchKernelGGL((k_pipe<NPL>), dim3(L.nparts), dim3(kPBlock), 0, L.stream, K, L.dparams);
-}
-// k_wide: 1 + 8 (or 1 + 16) workgroups per partition; the workgroups of a partition share blockIdx % 8 (= the XCD, observed).
-// A pad of dynamic LDS keeps it at one workgroup per CU (one scanner wave per SIMD is the point of the kernel).
-template <class W>
-int launch_wide(cns_engine* h, const KParams& K, const LaunchCtx& L, std::string* name) {
-  const u32 np = L.max_np;
-  const char* kname = "";
-  const void* fn = W::pick(np, &kname, K.wide_window >= 2u);
-  if (!fn) return 2;
-  const unsigned groups = (L.nparts + 7u) / 8u;
-  // Extra home workgroups per partition (wide_kernel.inc, "MORE THAN ONE HOME WORKGROUP PER PARTITION"): as many as the build allows, as long as
-  // every workgroup of the launch still gets a CU of "its" XCD (32 each, `groups` partitions per XCD) and of the device (other launches of the
-  // cycle hold theirs); none for tiles whose last-task table is not in LDS.  ONE extra home is the default: with two homes the scanners pace every
-  // configuration measured (C5 184.6 -> 146.6 ms, C2 139.4 -> 114.2; a third and a fourth home: 146.3 / 114.2 — profiles/r06_ab_home_workgroups.txt).
-  // CNS_WIDE_AUX=<n> sets the number (0: rounds 2-5's single home; up to the build's maximum: the parity tests run them all).
-  unsigned aux = np > W::lanes * W::last_in_lds_rows ? 0u : (W::aux_max < 1u ? W::aux_max : 1u);
-  if (const char* ea = getenv("CNS_WIDE_AUX")) { const unsigned v = (unsigned)strtoul(ea, nullptr, 10); aux = np > W::lanes * W::last_in_lds_rows ? 0u : (v < W::aux_max ? v : W::aux_max); }
-  while (aux > 0 && (groups * (W::group + aux) > 32u || (u64)8u * groups * (W::group + aux) + L.other_blocks > h->num_cus)) --aux;
-  const unsigned grid = 8u * groups * (W::group + aux);
-  const size_t need = (size_t)h->P * W::ctl_bytes;
-  if (h->d_wide.ensure(need) != hipSuccess) return 1;
-  if (hipMemsetAsync(h->d_wide.p, 0, need, L.stream) != hipSuccess) return 1;
-  KParams K2 = K;
-  K2.wide_ctl = h->d_wide.as<char>();
-  K2.wide_aux = aux;
-  if (np > W::lanes * 4u) {   // 8 / 16 rows per lane: the home workgroup's last-task table does not fit the LDS
-    const size_t lb = (size_t)h->P * W::lanes * W::npl_max * sizeof(u32);
-    if (h->d_wide_last.ensure(lb) != hipSuccess) return 1;
-    if (hipMemsetAsync(h->d_wide_last.p, 0, lb, L.stream) != hipSuccess) return 1;
-    K2.wide_last = h->d_wide_last.as<u32>();
-  }
-  if (hipMemcpyAsync(&const_cast<KParams*>(L.dparams)->wide_ctl, &K2.wide_ctl, sizeof(char*), hipMemcpyHostToDevice, L.stream) != hipSuccess) return 1;
-  size_t dyn = 0;
-  hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.sharedSizeBytes < 84u * 1024u) {
-    dyn = 84u * 1024u - fa.sharedSizeBytes;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) { dyn = 0; (void)hipGetLastError(); }
-  }
-  // The workgroups of this launch spin on each other: ALL of them must be resident at once.  Proof, not assumption: the
-  // runtime's own occupancy figure for this kernel at this block size and LDS footprint, times the device's CUs, must
-  // cover the grid — else the launch is refused here and the cycle runs on k_pipe / k_select, which need no co-residency.
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)W::block, dyn) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
-  if (per_cu < 1 || (u64)per_cu * h->num_cus < (u64)grid + L.other_blocks) return 2;
-  const KParams* dparams = L.dparams;
-  void* args[2] = {(void*)&K2, (void*)&dparams};
-  if (hipLaunchKernel(fn, dim3(grid), dim3(W::block), args, dyn, L.stream) != hipSuccess) return 1;
-  *name = std::string(kname) + " x" + std::to_string(W::waves);   // (x64: cns::w64::k_wide in a profile, x32: cns::w32::k_wide, ...)
-  return 0;
-}
-// Groups of partitions that share nodes and are wider than k_select's register tile (an "ALL" partition over a large cluster):
-// k_wide's HOME workgroup alone, every job through the sequential protocol with its tester waves as memory scanners over the
-// committed HBM arrays (KParams::serial_only).  The narrowest build serves (its two scanner workgroups per partition leave at once);
-// no workgroup waits for another one, so no co-residency is needed.  Slow — every job reads every slot of its group — and exact.
-// Above W::mem_slots (143 360) the giant instantiation (19-word row masks, up to W::giant_mem_slots) serves the launch: same protocol,
-// more scratch per memory-scanner lane; the launches that fit the ordinary masks keep the ordinary kernel.
-int launch_mem(cns_engine* h, const KParams& K, const LaunchCtx& L, std::string* name) {
-  using W = w8::WideInfo;
-  if (L.max_np > W::giant_mem_slots) return 2;   // (cns_set_nodes refuses such groups: never reached)
-  const bool giant = L.max_np > W::mem_slots;
-  const void* fn = giant ? (const void*)w8::k_wide<1, false, w8::kWMemWordsGiant> : (const void*)w8::k_wide<1, false>;
-  const unsigned groups = (L.nparts + 7u) / 8u;
-  const unsigned grid = 8u * groups * W::group;
-  const size_t need = (size_t)h->P * W::ctl_bytes;
-  if (h->d_wide_mem.ensure(need) != hipSuccess) return 1;
-  if (hipMemsetAsync(h->d_wide_mem.p, 0, need, L.stream) != hipSuccess) return 1;
-  KParams K2 = K;
-  K2.wide_ctl = h->d_wide_mem.as<char>();
-  K2.serial_only = 1;
-  if (hipMemcpyAsync(const_cast<KParams*>(L.dparams), &K2, sizeof(KParams), hipMemcpyHostToDevice, L.stream) != hipSuccess) return 1;
-  size_t dyn = 0;
-  hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.sharedSizeBytes < 84u * 1024u) {
-    dyn = 84u * 1024u - fa.sharedSizeBytes;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) { dyn = 0; (void)hipGetLastError(); }
-  }
-  const KParams* dparams = L.dparams;
-  void* args[2] = {(void*)&K2, (void*)&dparams};
-  if (hipLaunchKernel(fn, dim3(grid), dim3(W::block), args, dyn, L.stream) != hipSuccess) return 1;
-  *name = giant ? "k_mem giant (k_wide<1> home workgroup, sequential protocol over the HBM arrays, 19-word row masks)"
-               : "k_mem (k_wide<1> home workgroup, sequential protocol over the HBM arrays)";
-  return 0;
-}
-// k_giant (wide_kernel.inc, "k_giant"): the giant instantiation in serial-only mode plus `nh` helper workgroups per partition that
-// scan stripes of the job's slots; grid = nparts x (1 + nh), the home of partition i is block i.  The helpers and the home wait for
-// each other, so every workgroup must be resident at once: proven with the runtime's occupancy figure (one workgroup per CU: the
-// LDS pad of launch_mem) against the CUs left by the cycle's other launches.  Returns 0 (launched; *blocks: its workgroups), 1 (HIP
-// error), 3 (not launched: no proof of co-residency, or helpers turned off — the caller runs k_mem, which is exact and needs none).
-// 64 helper workgroups per launch at most (8 per XCD): C4's k_wide launch beside it keeps its 8 x 17 workgroups.
-constexpr u32 kGiantHelperBudget = 64;
-int launch_giant(cns_engine* h, const KParams& K, const LaunchCtx& L, std::string* name, u32* blocks) {
-  using W = w8::WideInfo;
-  if (h->giant_off || h->num_cus == 0 || L.max_np > W::giant_mem_slots) return 3;
-  const u32 nh = std::min<u32>(w8::kGiantHelpersMax, kGiantHelperBudget / std::max<u32>(L.nparts, 1));
-  if (nh < 4) return 3;
-  const void* fn = (const void*)w8::k_wide<1, false, w8::kWMemWordsGiant>;
-  const unsigned grid = L.nparts * (1u + nh);
-  size_t dyn = 0;
-  hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.sharedSizeBytes < 84u * 1024u) {
-    dyn = 84u * 1024u - fa.sharedSizeBytes;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) { dyn = 0; (void)hipGetLastError(); }
-  }
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)W::block, dyn) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
-  if (per_cu < 1 || (u64)per_cu * h->num_cus < (u64)grid + L.other_blocks) return 3;
-  const size_t need = (size_t)h->P * W::ctl_bytes, gneed = (size_t)h->P * sizeof(w8::GiantCtl);
-  if (h->d_wide_mem.ensure(need) != hipSuccess || h->d_giant.ensure(gneed) != hipSuccess) return 1;
-  if (hipMemsetAsync(h->d_wide_mem.p, 0, need, L.stream) != hipSuccess || hipMemsetAsync(h->d_giant.p, 0, gneed, L.stream) != hipSuccess) return 1;
-  KParams K2 = K;
-  K2.wide_ctl = h->d_wide_mem.as<char>();
-  K2.serial_only = 1;
-  K2.giant_ctl = h->d_giant.as<char>();
-  K2.giant_nh = nh;
-  if (hipMemcpyAsync(const_cast<KParams*>(L.dparams), &K2, sizeof(KParams), hipMemcpyHostToDevice, L.stream) != hipSuccess) return 1;
-  const KParams* dparams = L.dparams;
-  void* args[2] = {(void*)&K2, (void*)&dparams};
-  if (hipLaunchKernel(fn, dim3(grid), dim3(W::block), args, dyn, L.stream) != hipSuccess) return 1;
-  *name = "k_giant (k_wide<1> home workgroup + " + std::to_string(nh) + " helper workgroups per partition, sequential protocol over the HBM arrays)";
-  *blocks = grid;
-  return 0;
-}
-// Which selection kernel runs: k_pipe (decoupled test / commit pipeline) for partitions its tile covers, k_select
-// otherwise.  CNS_SELECT_KERNEL=legacy|pipe forces one (A/B measurements, and the parity tests run both).
+// What the plan (plan_host.inc) needs to know about this build.  CNS_SELECT_KERNEL=legacy|pipe|wide... forces a family (A/B
+// measurements, and the parity tests run them all); the defaults of a build:
 #ifndef CNS_DEFAULT_PIPE
 #define CNS_DEFAULT_PIPE 1
 #endif
 #ifndef CNS_DEFAULT_WIDE
 #define CNS_DEFAULT_WIDE 1
 #endif
-// k_wide (many CUs per partition) when every workgroup of the launch can be resident at once and the partitions fit its tile:
-// 64 scanner waves per partition (17 workgroups) for up to 8 partitions, 32 (9 workgroups) for up to 24, 16 (5) for up to 48,
-// 8 (3) for up to 80 — the widest build that fits.  Returns 0 / 8 / 16 / 32 / 64.
-// CNS_SELECT_KERNEL=wide32 | wide16 | wide8 caps the build (A/B measurements, and the parity tests run them).
-// (for a launch over partitions that neither share nodes nor run with preemption: the others go to k_select)
-u32 use_wide_kernel(const cns_engine* h, const LaunchCtx& L) {
-  const char* e = getenv("CNS_SELECT_KERNEL");
-  bool want = CNS_DEFAULT_WIDE != 0;
-  if (e && (!strcmp(e, "legacy") || !strcmp(e, "pipe"))) want = false;
-  u32 cap = 64;
-  if (e && !strcmp(e, "wide32")) cap = 32;
-  if (e && !strcmp(e, "wide16")) cap = 16;
-  if (e && !strcmp(e, "wide8")) cap = 8;
-  if (e && (!strcmp(e, "wide") || cap != 64)) want = true;
-  if (!e && h->cfg.kernel_pin != CNS_KERNEL_AUTO) want = false;   // (cns_config::kernel_pin: a controller that shares its GPU; the environment variable, an A/B and test switch, wins)
-  if (!want || h->wide_off) return 0;
-  // every workgroup of the launch must be resident at once, one per CU (a partitioned or smaller device falls to k_pipe)
-  const u32 groups = (L.nparts + 7u) / 8u;
-  auto fits = [&](u32 wgs_per_part) { return h->num_cus != 0 && 8u * groups * wgs_per_part + L.other_blocks <= h->num_cus; };   // (unknown CU count: no proof of co-residency, no k_wide)
-  auto serves = [&](u32 waves, u32 max_parts, u32 slots, u32 group) { return cap >= waves && L.nparts <= max_parts && L.max_np <= slots && fits(group); };
-  if (serves(64, w64::WideInfo::max_parts, w64::WideInfo::lanes * w64::WideInfo::npl_max, w64::WideInfo::group)) return 64;
-  if (serves(32, w32::WideInfo::max_parts, w32::WideInfo::lanes * w32::WideInfo::npl_max, w32::WideInfo::group)) return 32;
-  if (serves(16, w16::WideInfo::max_parts, w16::WideInfo::lanes * w16::WideInfo::npl_max, w16::WideInfo::group)) return 16;
-  if (serves(8, w8::WideInfo::max_parts, w8::WideInfo::lanes * w8::WideInfo::npl_max, w8::WideInfo::group)) return 8;
-  return 0;
+constexpr u32 kGiantHelperBudget = 64;   // helper workgroups of a k_giant launch at most (plan_host.inc: plan_serial_launch)
+#define CNS_WIDTH(w) (u32)(w),
+constexpr u32 kSelectWidths[] = {CNS_NPL_LIST(CNS_WIDTH)}, kPipeWidths[] = {CNS_PNPL_LIST(CNS_WIDTH)};
+#undef CNS_WIDTH
+static_assert(CNS_KERNEL_AUTO == cns_plan::kPinAuto && CNS_KERNEL_SELECT == cns_plan::kPinSelect, "plan_host.inc: cns_kernel_pin");
+static_assert(kSelectWidths[sizeof kSelectWidths / 4 - 1] == CNS_NPL_MAX && kPipeWidths[sizeof kPipeWidths / 4 - 1] == (u32)kPNplMax, "the lists end in their widest tile");
+template <class W>
+cns_plan::WideBuild wide_build() {
+  cns_plan::WideBuild b;
+  b.waves = W::waves; b.group = W::group; b.max_parts = W::max_parts; b.aux_max = W::aux_max; b.last_in_lds_rows = W::last_in_lds_rows;
+  b.tiles.lanes = W::lanes; b.tiles.block = W::block;
+  b.tiles.widths.assign(std::begin(W::widths), std::end(W::widths));
+  b.window_widths.assign(W::widths, W::widths + W::window_widths);
+  return b;
 }
-bool use_pipe_kernel(const cns_engine* h, const LaunchCtx& L) {
-  const char* e = getenv("CNS_SELECT_KERNEL");
-  bool want = CNS_DEFAULT_PIPE != 0;
-  if (e && !strcmp(e, "legacy")) want = false;
-  if (e && (!strcmp(e, "pipe") || !strncmp(e, "wide", 4))) want = true;
-  if (!e && h->cfg.kernel_pin == CNS_KERNEL_SELECT) want = false;
-  return want && L.max_np <= kPScan * (u32)kPNplMax;
-}
-// One launch: k_wide / k_pipe where the partitions allow it (`plain`: none of them shares nodes or runs with preemption), else
-// k_select.  0 ok (kernel name in *name), else a status for fail().
-int launch_one(cns_engine* h, const KParams& K, const LaunchCtx& L, bool plain, std::string* name, std::string* err) {
-  const u32 np = L.max_np;
+const cns_plan::Facts& plan_facts() {
+  static const cns_plan::Facts F = [] {
+    cns_plan::Facts f;
+    f.wide[0] = wide_build<w64::WideInfo>(); f.wide[1] = wide_build<w32::WideInfo>(); f.wide[2] = wide_build<w16::WideInfo>(); f.wide[3] = wide_build<w8::WideInfo>();
+    f.select.lanes = kScan; f.select.block = kBlock; f.select.widths.assign(std::begin(kSelectWidths), std::end(kSelectWidths));
+    f.pipe.lanes = kPScan; f.pipe.block = kPBlock; f.pipe.widths.assign(std::begin(kPipeWidths), std::end(kPipeWidths));
 #ifdef CNS_ONLY_NPL   // experiment builds: one tile width only
-  if (np > kScan * CNS_ONLY_NPL) { *err = "experiment build: partition too large for its one tile width"; return CNS_ERR_UNSUPPORTED; }
-  launch_select<CNS_ONLY_NPL>(h, K, L);
-  *name = "k_select";
-  return 0;
-#else
-  bool launched = false;
-  if (const u32 ww = plain ? use_wide_kernel(h, L) : 0u) {
-    const int rc = ww == 64 ? launch_wide<w64::WideInfo>(h, K, L, name) : ww == 32 ? launch_wide<w32::WideInfo>(h, K, L, name)
-                 : ww == 16 ? launch_wide<w16::WideInfo>(h, K, L, name) : launch_wide<w8::WideInfo>(h, K, L, name);
-    if (rc == 1) { *err = "k_wide: control block allocation / upload / launch failed"; return CNS_ERR_HIP; }
-    launched = rc == 0;
-  }
-  if (!launched && plain && use_pipe_kernel(h, L)) {
-#define CNS_TRY_PWIDTH(w) if (!launched && np <= kPScan * (w)) { launch_pipe<w>(h, K, L); launched = true; *name = "k_pipe<" #w ">"; }
-    CNS_PNPL_LIST(CNS_TRY_PWIDTH)
-#undef CNS_TRY_PWIDTH
-  }
-#define CNS_TRY_WIDTH(w) if (!launched && np <= kScan * (w)) { launch_select<w>(h, K, L); launched = true; *name = "k_select<" #w ">"; }
-  CNS_NPL_LIST(CNS_TRY_WIDTH)
-#undef CNS_TRY_WIDTH
-  if (!launched) { *err = "partition too large for the widest register tile"; return CNS_ERR_UNSUPPORTED; }
-  return 0;
+    f.only_npl = CNS_ONLY_NPL;
 #endif
+    f.mem_slots = w8::WideInfo::mem_slots; f.giant_mem_slots = w8::WideInfo::giant_mem_slots;
+    f.giant_helpers_max = w8::kGiantHelpersMax; f.giant_helper_budget = kGiantHelperBudget;
+    f.default_wide = CNS_DEFAULT_WIDE != 0; f.default_pipe = CNS_DEFAULT_PIPE != 0;
+    return f;
+  }();
+  return F;
+}
+// The shipped build's figures as tests/cpp/plan_host_test.cpp writes them out (experiment builds change them at will).
+#if defined(CNS_WIDE_WGS_ALL) && !defined(CNS_ONLY_NPL) && !defined(CNS_WIDE_AUX_CAP) && CNS_BLOCK == 512 && CNS_IDLE_WAVE >= 8 && CNS_PIPE_BLOCK == 768 && CNS_PIPE_TESTERS == 3 && CNS_WIDE_SPW == 4 && CNS_WIDE_WIN == 32
+template <class W, u32... Ws>
+constexpr bool wide_is(u32 waves, u32 group, u32 max_parts, u32 lanes, u32 aux_max, u32 windows) {
+  constexpr u32 ws[] = {Ws...};
+  if (sizeof ws != sizeof W::widths) return false;
+  for (size_t i = 0; i < sizeof ws / 4; ++i) if (ws[i] != W::widths[i]) return false;
+  return W::waves == waves && W::group == group && W::max_parts == max_parts && W::lanes == lanes && W::aux_max == aux_max && W::window_widths == windows &&
+         W::last_in_lds_rows == 4 && W::block == 512;
+}
+static_assert(wide_is<w64::WideInfo, 1, 2, 4, 8, 16>(64, 17, 8, 4096, 3, 2) && wide_is<w32::WideInfo, 1, 2, 4, 8>(32, 9, 24, 2048, 1, 0) &&
+              wide_is<w16::WideInfo, 1, 2, 4, 8>(16, 5, 48, 1024, 1, 0) && wide_is<w8::WideInfo, 1, 2, 4, 8>(8, 3, 80, 512, 1, 0), "plan_host_test.cpp: k_wide's builds");
+static_assert(kScan == 448 && kBlock == 512 && sizeof kSelectWidths == 24 && kSelectWidths[0] == 1 && kSelectWidths[1] == 3 && kSelectWidths[2] == 10 &&
+              kSelectWidths[3] == 19 && kSelectWidths[4] == 28 && kSelectWidths[5] == 37, "plan_host_test.cpp: k_select's tiles");
+static_assert(kPScan == 512 && kPBlock == 768 && sizeof kPipeWidths == 16 && kPipeWidths[0] == 1 && kPipeWidths[1] == 4 && kPipeWidths[2] == 8 && kPipeWidths[3] == 16,
+              "plan_host_test.cpp: k_pipe's tiles");
+static_assert(w8::WideInfo::mem_slots == 143360 && w8::WideInfo::giant_mem_slots == 544768 && w8::kGiantHelpersMax == 64 && kGiantHelperBudget == 64 &&
+              CNS_DEFAULT_WIDE == 1 && CNS_DEFAULT_PIPE == 1, "plan_host_test.cpp: k_mem / k_giant, the defaults");
+#endif
+
+// One launch of a cycle: its stream, its copy of the parameter block in HBM (the out-of-line routines read that one) and the
+// workgroups of the cycle's other launches (they hold CUs while a kernel whose workgroups wait needs all of its own resident).
+struct LaunchCtx {
+  hipStream_t stream;
+  const KParams* dparams;
+  u32 other_blocks;
+};
+enum class Launched { Yes, NotProven, HipError };
+struct CtlBuf { DevBuf* buf; size_t bytes; };   // a control buffer to size and zero before the launch (0 bytes: not used)
+// One launch of the k_wide family (k_wide, k_mem, k_giant): `edit` points the kernel's parameter block at the zeroed control buffers.
+// `whole_block`: the device copy of the block gets all of it (k_mem, k_giant); else only wide_ctl — the caller uploaded the rest (k_wide).
+template <class Edit>
+Launched launch_wide_family(const void* fn, const cns_plan::Candidate& c, const KParams& K, const LaunchCtx& L, u32 num_cus,
+                            std::initializer_list<CtlBuf> ctl, bool whole_block, Edit edit) {
+  // A pad of dynamic LDS keeps the kernel at one workgroup per CU (one scanner wave per SIMD is the point of k_wide).
+  size_t dyn = 0;
+  hipFuncAttributes fa;
+  if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.sharedSizeBytes < 84u * 1024u) {
+    dyn = 84u * 1024u - fa.sharedSizeBytes;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) { dyn = 0; (void)hipGetLastError(); }
+  }
+  // The workgroups of a candidate that `waits` spin on each other: ALL of them must be resident at once.  Proof, not assumption: the
+  // runtime's own occupancy figure for this kernel at this block size and LDS footprint, times the device's CUs, must cover the grid
+  // and what the cycle's other launches hold — else the launch is refused here and the caller takes the plan's next candidate
+  // (k_pipe / k_select, k_mem), which needs no co-residency.
+  if (c.waits) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)c.block, dyn) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
+    if (per_cu < 1 || (u64)per_cu * num_cus < (u64)c.grid + L.other_blocks) return Launched::NotProven;
+  }
+  for (const CtlBuf& b : ctl)
+    if (b.bytes && (b.buf->ensure(b.bytes) != hipSuccess || hipMemsetAsync(b.buf->p, 0, b.bytes, L.stream) != hipSuccess)) return Launched::HipError;
+  KParams K2 = K;
+  edit(K2);
+  KParams* dp = const_cast<KParams*>(L.dparams);
+  if ((whole_block ? hipMemcpyAsync(dp, &K2, sizeof(KParams), hipMemcpyHostToDevice, L.stream)
+                   : hipMemcpyAsync(&dp->wide_ctl, &K2.wide_ctl, sizeof(char*), hipMemcpyHostToDevice, L.stream)) != hipSuccess) return Launched::HipError;
+  const KParams* dparams = L.dparams;
+  void* args[2] = {(void*)&K2, (void*)&dparams};
+  return hipLaunchKernel(fn, dim3(c.grid), dim3(c.block), args, dyn, L.stream) == hipSuccess ? Launched::Yes : Launched::HipError;
+}
+// k_wide: 1 + 8 (or 1 + 16, ...) workgroups per partition plus the candidate's extra homes.
+template <class W>
+Launched launch_wide(cns_engine* h, const KParams& K, const LaunchCtx& L, const cns_plan::Candidate& c) {
+  const char* kname = "";
+  const void* fn = W::pick(W::lanes * c.width, &kname, c.windows);
+  const bool last_in_hbm = c.width > W::last_in_lds_rows;   // 8 / 16 rows per lane: the home workgroup's last-task table does not fit the LDS
+  return launch_wide_family(fn, c, K, L, h->num_cus, {{&h->d_wide, (size_t)h->P * W::ctl_bytes}, {&h->d_wide_last, last_in_hbm ? (size_t)h->P * W::lanes * W::npl_max * sizeof(u32) : 0}},
+                            false, [&](KParams& K2) {
+                              K2.wide_ctl = h->d_wide.as<char>();
+                              K2.wide_aux = c.extra;
+                              if (last_in_hbm) K2.wide_last = h->d_wide_last.as<u32>();
+                            });
+}
+// k_mem — groups of partitions that share nodes and are wider than k_select's register tile (an "ALL" partition over a large cluster):
+// k_wide's HOME workgroup alone, every job through the sequential protocol with its tester waves as memory scanners over the
+// committed HBM arrays (KParams::serial_only).  The narrowest build serves (its two scanner workgroups per partition leave at once);
+// no workgroup waits for another one.  Slow — every job reads every slot of its group — and exact.  Above W::mem_slots (143 360) the
+// giant instantiation (19-word row masks, up to W::giant_mem_slots) serves the launch: same protocol, more scratch per memory-scanner
+// lane; the launches that fit the ordinary masks keep the ordinary kernel.
+// k_giant (wide_kernel.inc, "k_giant"): the giant instantiation in serial-only mode plus the candidate's helper workgroups per partition
+// that scan stripes of the job's slots; grid = nparts x (1 + helpers).  The helpers and the home wait for each other.
+Launched launch_serial(cns_engine* h, const KParams& K, const LaunchCtx& L, const cns_plan::Candidate& c) {
+  using W = w8::WideInfo;
+  const bool giant = c.family == cns_plan::Family::Giant;
+  const void* fn = c.giant_masks ? (const void*)w8::k_wide<1, false, w8::kWMemWordsGiant> : (const void*)w8::k_wide<1, false>;
+  return launch_wide_family(fn, c, K, L, h->num_cus, {{&h->d_wide_mem, (size_t)h->P * W::ctl_bytes}, {&h->d_giant, giant ? (size_t)h->P * sizeof(w8::GiantCtl) : 0}},
+                            true, [&](KParams& K2) {
+                              K2.wide_ctl = h->d_wide_mem.as<char>();
+                              K2.serial_only = 1;
+                              if (giant) { K2.giant_ctl = h->d_giant.as<char>(); K2.giant_nh = c.extra; }
+                            });
+}
+// One launch of the plan: its candidates in order, the first that launches in *chosen.  0 ok, else a status (h->err is set).
+int run_launch(cns_engine* h, const KParams& K, hipStream_t stream, const KParams* dparams, const cns_plan::Launch& PL, cns_plan::Candidate* chosen) {
+  using cns_plan::Family;
+  const LaunchCtx L{stream, dparams, PL.other_blocks};
+  for (const cns_plan::Candidate& c : PL.cands) {
+    Launched r = Launched::Yes;
+    switch (c.family) {
+      case Family::Wide:
+        r = c.build == 0 ? launch_wide<w64::WideInfo>(h, K, L, c) : c.build == 1 ? launch_wide<w32::WideInfo>(h, K, L, c)
+          : c.build == 2 ? launch_wide<w16::WideInfo>(h, K, L, c) : launch_wide<w8::WideInfo>(h, K, L, c);
+        break;
+      case Family::Mem: case Family::Giant: r = launch_serial(h, K, L, c); break;
+      case Family::Pipe:
+#define CNS_LAUNCH_WIDTH(w) if (c.width == (w)) hipLaunchKernelGGL((k_pipe<w>), dim3(c.grid), dim3(c.block), 0, L.stream, K, L.dparams);
+        CNS_PNPL_LIST(CNS_LAUNCH_WIDTH)
+#undef CNS_LAUNCH_WIDTH
+        break;
+      case Family::Select:
+#ifdef CNS_ONLY_NPL
+        hipLaunchKernelGGL((k_select<CNS_ONLY_NPL>), dim3(c.grid), dim3(c.block), 0, L.stream, K, L.dparams);
+#else
+#define CNS_LAUNCH_WIDTH(w) if (c.width == (w)) hipLaunchKernelGGL((k_select<w>), dim3(c.grid), dim3(c.block), 0, L.stream, K, L.dparams);
+        CNS_NPL_LIST(CNS_LAUNCH_WIDTH)
+#undef CNS_LAUNCH_WIDTH
+#endif
+        break;
+    }
+    if (r == Launched::HipError) return fail(h, CNS_ERR_HIP, c.family == Family::Wide ? "k_wide: control block allocation / upload / launch failed"
+                                                                                     : "k_mem / k_giant: control block allocation / upload / launch failed");
+    if (r == Launched::Yes) { *chosen = c; return 0; }
+  }
+  return fail(h, CNS_ERR_UNSUPPORTED, PL.exhausted);
 }
 
 // Everything that depends on the slot list (real + virtual): per-slot res_total / time-map end, node types
@@ -1158,12 +1131,14 @@ enum { B_QPOFF, B_QP, B_PJQOS, B_PJQP, B_PJPRIO, B_PJREC0, B_PJK, B_PJEND, B_RNJ
        B_RJSTART, B_RJEND, B_RJPRE, B_RJOFF, B_RJENT, B_HEAD, B_RECNEXT, B_RECORIG, B_RECSLOT, B_RECGONE, B_MISC };
 
 // One pass of the cycle on the device.  *fault_code: the device fault it ended with (0: none).
-static int run_resident_once(cns_handle* h, int64_t now, u32* fault_code) {
+// `protocol_off`: the retry — no kernel whose workgroups wait for each other.
+static int run_resident_once(cns_handle* h, int64_t now, const RunKnobs& kn, bool protocol_off, u32* fault_code) {
   *fault_code = 0;
+  h->pass_waits = false;
   h->have_probes = h->probes_answered = false;   // (probes are routed against the snapshot of the cycle they follow)
   HIPCHK(h, hipSetDevice(h->device));
   KParams K;
-  fill_params(h, K, now);
+  fill_params(h, K, now, kn);
   char* rb = h->d_results.as<char>();
   const u64 pl = std::max<u64>(h->places, 1), J = std::max<u64>(h->J, 1);
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
@@ -1191,104 +1166,66 @@ static int run_resident_once(cns_handle* h, int64_t now, u32* fault_code) {
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
   bool split = false;
+  cns_plan::Candidate ca, cb, cc;   // what launched for the plan's a / b / c
   if (h->Jg) {
-    // Which partitions need k_select: groups of partitions that share nodes (one time map per node, a cost per partition) and,
-    // in a cycle with preemption, the partitions that have a pending job whose qos may preempt anything (TryPreempt_ returns at
-    // JobScheduler.cpp:6384-6385 for every other job).  Everything else runs on k_wide / k_pipe IN THE SAME CYCLE, side by
-    // side on a second stream: partitions with disjoint node sets never interact (:6723-6732,6746-6761).
-    // Only partitions that HAVE pending jobs get a scheduler (the reference builds NodeStates and a LocalScheduler only for
-    // the partitions some pending job names, JobScheduler.cpp:6516-6530,6571-6573,6723-6732): the launch, and with it the choice
-    // of the k_wide build (workgroups per partition), is sized by the busy partitions, not by the snapshot.
-    // ... and a group of partitions that share nodes and is wider than k_select's register tile runs on k_wide's home workgroup
-    // alone (launch_mem): the ordinary "ALL partition over the whole cluster" layout of a large site.
-    // CNS_SELECT_KERNEL=giant: every partition and group without preemption on k_giant (A/B runs against k_wide / k_select / k_mem);
-    // =mem: the shapes of k_giant on k_mem (19-word masks above 143 360 slots), helpers off
-    const char* ek = getenv("CNS_SELECT_KERNEL");
-    const bool force_giant = ek && !strcmp(ek, "giant"), force_mem = ek && !strcmp(ek, "mem");
-    bool giant_shape = false;   // a partition wider than k_wide's tile, or a group wider than k_mem's ordinary masks: k_giant
-    std::vector<u32> pa, pb, pc;
-    u32 npa = 0, npb = 0, npc = 0;
-    for (u32 p = 0; p < h->P; ++p) {
-      if (p >= h->part_jobs.size() || h->part_jobs[p] == 0) continue;
-      const bool pre = h->pre_active && p < h->pre_part.size() && h->pre_part[p];
-      const bool sel = (p < h->eng_members.size() && h->eng_members[p] > 1) || pre;
-      const u32 np = h->part_off[p + 1] - h->part_off[p];
-      // (a partition that shares no node and is wider than k_wide's widest tile: k_mem too — it needs no co-residency, and what the
-      // ordinary kernels hold stays on them)
-      const bool giant = !sel && np > w64::WideInfo::lanes * w64::WideInfo::npl_max;
-      giant_shape = giant_shape || giant || (sel && !pre && np > w8::WideInfo::mem_slots);
-      if (giant || (force_giant && !pre)) { pc.push_back(p); npc = std::max(npc, np); }
-      else if (sel && np > kScan * (u32)CNS_NPL_MAX) {
-        if (pre) return fail(h, CNS_ERR_UNSUPPORTED, "preemption among the jobs of a partition (or group of partitions sharing nodes) with more than " +
-                                                         std::to_string(kScan * (u32)CNS_NPL_MAX) + " (partition, node) slots");
-        pc.push_back(p); npc = std::max(npc, np);
-      } else if (sel) { pb.push_back(p); npb = std::max(npb, np); }
-      else { pa.push_back(p); npa = std::max(npa, np); }
-    }
-    std::string err, name_a, name_b, name_c;
-    u32 held_c = 0;
-    if (!pc.empty()) {
-      if (int rc = upload(h, h->d_pmap_c, pc)) return rc;
+    cns_plan::Inputs in;
+    in.parts.resize(h->P);
+    for (u32 p = 0; p < h->P; ++p)
+      in.parts[p] = {p < h->part_jobs.size() ? h->part_jobs[p] : 0, h->part_off[p + 1] - h->part_off[p], p < h->eng_members.size() ? h->eng_members[p] : 1u,
+                     p < h->pre_part.size() && h->pre_part[p]};
+    in.pre_active = h->pre_active; in.num_cus = h->num_cus; in.kernel_pin = h->cfg.kernel_pin;
+    in.sw = kn.sw; in.protocol_off = protocol_off; in.wide_window = K.wide_window; in.aux_override = kn.aux;
+    cns_plan::CyclePlan plan = cns_plan::plan_cycle(plan_facts(), in);
+    if (plan.unsupported) return fail(h, CNS_ERR_UNSUPPORTED, plan.error);
+    const bool has_c = !plan.c.parts.empty();
+    if (has_c) {
+      if (int rc = upload(h, h->d_pmap_c, plan.c.parts)) return rc;
       HIPCHK(h, h->d_params3.ensure(sizeof(KParams)));
       KParams KC = K;
-      KC.part_map = h->d_pmap_c.as<u32>(); KC.launch_parts = (u32)pc.size();
+      KC.part_map = h->d_pmap_c.as<u32>(); KC.launch_parts = (u32)plan.c.parts.size();
       KC.general_only = 0; KC.pre = PreParams{};
       HIPCHK(h, hipEventRecord(h->ev2[0], h->stream));                  // tables + init kernels done: the second stream may start
       HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev2[0], 0));
-      LaunchCtx LC{(u32)pc.size(), npc, h->stream2, h->d_params3.as<KParams>(), 0u};
-      int rc = (giant_shape || force_giant) && !force_mem ? launch_giant(h, KC, LC, &name_c, &held_c) : 3;
-      if (rc == 3) { rc = launch_mem(h, KC, LC, &name_c); held_c = (u32)pc.size(); }
-      if (rc) return rc == 2 ? fail(h, CNS_ERR_UNSUPPORTED, "k_mem: a group wider than its giant row masks")
-                             : fail(h, CNS_ERR_HIP, "k_mem / k_giant: control block allocation / upload / launch failed");
-      name_c += " on " + std::to_string(pc.size()) + " group(s) of up to " + std::to_string(npc) + " slots";
+      if (int rc = run_launch(h, KC, h->stream2, h->d_params3.as<KParams>(), plan.c, &cc)) return rc;
+      // (the other launches were planned beside c's first candidate: where k_giant's helpers were not proven, beside k_mem's home workgroups instead)
+      if (cc.family != plan.c.cands[0].family) { in.helpers_unproven = true; plan = cns_plan::plan_cycle(plan_facts(), in); }
     }
-    const u32 held = held_c;   // workgroups of k_mem (its home workgroups) / k_giant that hold a CU while the other launches run
-    if (pa.empty() && pb.empty()) {
-      h->last_kernel = pc.empty() ? std::string("none (no pending job reaches an ordered loop)") : name_c;   // (never empty: callers parse it)
-    } else if (pb.empty() || pa.empty()) {
+    if (const cns_plan::Launch* one = plan.single()) {
       // one launch: over all partitions (identity map) when every one is busy, else over the busy ones (part_map)
-      const bool plain = pb.empty();
-      const std::vector<u32>& pm = plain ? pa : pb;
-      const bool ident = pm.size() == h->P;
-      LaunchCtx L{(u32)pm.size(), plain ? npa : npb, h->stream, h->d_params.as<KParams>(), held};
+      const bool plain = one == &plan.a;
       KParams K1 = K;
       if (plain) { K1.general_only = 0; K1.pre = PreParams{}; }
-      if (!ident) {
-        if (int rc = upload(h, h->d_pmap_a, pm)) return rc;
-        K1.part_map = h->d_pmap_a.as<u32>(); K1.launch_parts = (u32)pm.size();
+      if (!plan.identity) {
+        if (int rc = upload(h, h->d_pmap_a, one->parts)) return rc;
+        K1.part_map = h->d_pmap_a.as<u32>(); K1.launch_parts = (u32)one->parts.size();
       }
-      if (K1.general_only != K.general_only || !ident) HIPCHK(h, hipMemcpyAsync(h->d_params.p, &K1, sizeof(KParams), hipMemcpyHostToDevice, h->stream));
-      if (const int rc = launch_one(h, K1, L, plain, &h->last_kernel, &err)) return fail(h, rc, err);
-      if (!ident) h->last_kernel += " on " + std::to_string(pm.size()) + " busy of " + std::to_string(h->P) + " partitions";
-      if (!pc.empty()) h->last_kernel += " + " + name_c;
-    } else {
-      if (int rc = upload(h, h->d_pmap_a, pa)) return rc;
-      if (int rc = upload(h, h->d_pmap_b, pb)) return rc;
+      if (K1.general_only != K.general_only || !plan.identity) HIPCHK(h, hipMemcpyAsync(h->d_params.p, &K1, sizeof(KParams), hipMemcpyHostToDevice, h->stream));
+      if (int rc = run_launch(h, K1, h->stream, h->d_params.as<KParams>(), *one, plain ? &ca : &cb)) return rc;
+    } else if (plan.split) {
+      if (int rc = upload(h, h->d_pmap_a, plan.a.parts)) return rc;
+      if (int rc = upload(h, h->d_pmap_b, plan.b.parts)) return rc;
       HIPCHK(h, h->d_params2.ensure(sizeof(KParams)));
       KParams KA = K, KB = K;
-      KA.part_map = h->d_pmap_a.as<u32>(); KA.launch_parts = (u32)pa.size();
+      KA.part_map = h->d_pmap_a.as<u32>(); KA.launch_parts = (u32)plan.a.parts.size();
       KA.general_only = 0; KA.pre = PreParams{};
       KA.slot_block = nullptr; KA.sib_off = nullptr; KA.sib = nullptr; KA.slot_tag = nullptr;   // (none of these partitions shares a node)
-      KB.part_map = h->d_pmap_b.as<u32>(); KB.launch_parts = (u32)pb.size();
+      KB.part_map = h->d_pmap_b.as<u32>(); KB.launch_parts = (u32)plan.b.parts.size();
       HIPCHK(h, hipMemcpyAsync(h->d_params.p, &KA, sizeof(KParams), hipMemcpyHostToDevice, h->stream));
       HIPCHK(h, hipMemcpyAsync(h->d_params2.p, &KB, sizeof(KParams), hipMemcpyHostToDevice, h->stream));
       HIPCHK(h, hipEventRecord(h->ev2[0], h->stream));                  // tables + init kernels done: the second stream may start
       HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev2[0], 0));
-      LaunchCtx LB{(u32)pb.size(), npb, h->stream2, h->d_params2.as<KParams>(), 0u};
-      if (const int rc = launch_one(h, KB, LB, false, &name_b, &err)) return fail(h, rc, err);   // first: its few workgroups take their CUs
-      LaunchCtx LA{(u32)pa.size(), npa, h->stream, h->d_params.as<KParams>(), (u32)pb.size() + held};
-      if (const int rc = launch_one(h, KA, LA, true, &name_a, &err)) return fail(h, rc, err);
+      if (int rc = run_launch(h, KB, h->stream2, h->d_params2.as<KParams>(), plan.b, &cb)) return rc;   // first: its few workgroups take their CUs
+      if (int rc = run_launch(h, KA, h->stream, h->d_params.as<KParams>(), plan.a, &ca)) return rc;
       HIPCHK(h, hipEventRecord(h->ev[3], h->stream));                   // the partitions on the fast kernels are done here
       split = true;
-      HIPCHK(h, hipEventRecord(h->ev2[1], h->stream2));
-      HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev2[1], 0));           // the cycle ends when both have
-      h->last_kernel = name_a + " + " + name_b + " on " + std::to_string(pb.size()) + " of " + std::to_string(h->P) + " partitions";
-      if (!pc.empty()) h->last_kernel += " + " + name_c;
     }
-    if (!pc.empty() && !split) {   // the cycle ends when the launch on the second stream has
+    if (has_c || split) {   // the cycle ends when the launch(es) on the second stream have
       HIPCHK(h, hipEventRecord(h->ev2[1], h->stream2));
       HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev2[1], 0));
     }
+    h->last_kernel = cns_plan::last_kernel_text(plan, plan.a.parts.empty() ? nullptr : &ca, plan.b.parts.empty() ? nullptr : &cb, has_c ? &cc : nullptr);
+    // (k_wide serves plain launches only — a, the launch last_kernel names first — and k_giant only c: b's k_select never waits)
+    h->pass_waits = (!plan.a.parts.empty() && ca.waits) || (has_c && cc.waits);
     HIPCHK(h, hipGetLastError());
   }
   HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
@@ -1302,7 +1239,7 @@ static int run_resident_once(cns_handle* h, int64_t now, u32* fault_code) {
     float c = 0;
     HIPCHK(h, hipEventElapsedTime(&c, h->ev[1], h->ev[3]));
     char buf[64];
-    snprintf(buf, sizeof buf, " [%s partitions done after %.1f ms]", h->last_kernel.substr(0, h->last_kernel.find(' ')).c_str(), c);
+    snprintf(buf, sizeof buf, " [%s partitions done after %.1f ms]", cns_plan::kernel_of(ca).c_str(), c);
     h->last_kernel += buf;
   }
   h->timing.jobs_ordered = h->jobs_ordered;
@@ -1338,21 +1275,15 @@ int cns_run_resident(cns_handle* h, int64_t now) {
   if (!h) return fail(h, CNS_ERR_INVALID_ARG, "cns_run_resident: null handle");
   if (!h->have_nodes || !h->have_jobs) return fail(h, CNS_ERR_STATE, "cns_run_resident before set_nodes/upload_jobs");
   u32 code = 0;
-  h->wide_off = false;
-  int rc = run_resident_once(h, now, &code);
+  const RunKnobs kn = RunKnobs::read();
+  int rc = run_resident_once(h, now, kn, false, &code);
   // (CNS_WIDE_NO_RETRY=1: the fault fails the call — the GPU parity tests run that way, so that a k_wide that breaks is seen
   // and not papered over by the kernels behind it)
-  const char* no_retry = getenv("CNS_WIDE_NO_RETRY");
   // (k_giant's helpers wait for the home and the home for them: a fault of that protocol, 43, is re-run the same way, on k_mem)
-  const bool protocol = h->last_kernel.rfind("k_wide", 0) == 0 || h->last_kernel.find("k_giant") != std::string::npos;
-  if (rc == CNS_ERR_DEVICE_FAULT && code >= 20 && protocol && !(no_retry && no_retry[0] == '1')) {
+  if (rc == CNS_ERR_DEVICE_FAULT && code >= 20 && h->pass_waits && !kn.no_retry) {
     const std::string first = h->err;
-    h->wide_off = true;
-    h->giant_off = true;
     ++h->wide_retries;
-    rc = run_resident_once(h, now, &code);
-    h->wide_off = false;
-    h->giant_off = false;
+    rc = run_resident_once(h, now, kn, true, &code);
     if (rc == CNS_OK) h->last_kernel += " (retry after: " + first + ")";
     else h->err = first + "; retry on " + h->last_kernel + ": " + h->err;
   }

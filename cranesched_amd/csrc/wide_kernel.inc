@@ -2843,6 +2843,15 @@ struct WideInfo {
   static constexpr size_t ctl_bytes = sizeof(WideCtl);
   static constexpr u32 mem_slots = kWMs * 64u * kWMemWords;   // widest group the serial-only mode (KParams::serial_only) scans
   static constexpr u32 giant_mem_slots = kWMs * 64u * kWMemWordsGiant;   // ... and its giant instantiation (the 8-wave build only)
+  // the tile widths (rows per lane) of this build, ascending, and how many of the first ones also have a windows build
+#define CNS_WIDE_WIDTH(w) (u32)(w),
+  static constexpr u32 widths[] = {CNS_WNPL_LIST(CNS_WIDE_WIDTH)};
+#undef CNS_WIDE_WIDTH
+#ifdef CNS_WIDE_WINDOWS
+  static constexpr u32 window_widths = 2;
+#else
+  static constexpr u32 window_widths = 0;
+#endif
   // the narrowest tile that holds `np` nodes per partition: the kernel and its name (nullptr: none)
   static const void* pick(u32 np, const char** name, bool windows = false) {
 #ifdef CNS_WIDE_WINDOWS
