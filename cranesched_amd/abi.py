@@ -501,3 +501,97 @@ class PreemptOut:
 
     def preempting_ids(self):
         return [int(x) for x in self.preempting[:self._c.num_preempting]]
+
+
+# ---- reservation what-ifs (include/crane_gpu_resv/resv_probe.h) ---------------------------------------------------------
+RESVQ_OK, RESVQ_NOT_ENOUGH, RESVQ_IN_THE_PAST = 0, 1, 2
+RESVQ_FREE, RESVQ_RUNNING, RESVQ_RESERVED, RESVQ_NOT_FOUND = 0, 1, 2, 3
+
+
+class CnsResvqSoa(C.Structure):
+    _fields_ = [("num_queries", C.c_uint64), ("start_sec", _P), ("duration_sec", _P), ("node_num", _P), ("cand_offsets", _P),
+                ("cand_nodes", _P), ("find_earliest", _P)]
+
+
+class CnsResvqOut(C.Structure):
+    _fields_ = [("code_capacity", C.c_uint64), ("chosen_capacity", C.c_uint64), ("status", _P), ("start_sec", _P), ("num_free", _P),
+                ("code", _P), ("chosen_offsets", _P), ("chosen_nodes", _P)]
+
+
+@dataclass
+class ResvQueries:
+    """Q reservation requests (cns_resvq_soa): start, duration, node count (0: the whole list), candidates in the caller's order."""
+    start_sec: np.ndarray
+    duration_sec: np.ndarray
+    node_num: np.ndarray
+    cand_offsets: np.ndarray
+    cand_nodes: np.ndarray
+    find_earliest: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        self.start_sec = _arr(self.start_sec, np.int64)
+        q = len(self.start_sec)
+        self.duration_sec = _arr(self.duration_sec, np.int64, q)
+        self.node_num = _arr(self.node_num, np.uint32, q)
+        self.cand_offsets = _arr(self.cand_offsets, np.uint64, q + 1)
+        self.cand_nodes = _arr(self.cand_nodes, np.uint32)
+        if self.find_earliest is not None:
+            self.find_earliest = _arr(self.find_earliest, np.uint8, q)
+
+    @property
+    def num_queries(self):
+        return len(self.start_sec)
+
+    def k(self) -> np.ndarray:
+        """Nodes asked for per query: node_num, or the list length (JobScheduler.cpp:4357-4358)."""
+        lens = np.diff(self.cand_offsets.astype(np.int64))
+        return np.where(self.node_num != 0, self.node_num.astype(np.int64), lens)
+
+    def take(self, order) -> "ResvQueries":
+        """The queries `order`, in that order."""
+        order = np.asarray(order, np.int64)
+        lens = np.diff(self.cand_offsets.astype(np.int64))[order]
+        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+        parts = [self.cand_nodes[int(self.cand_offsets[i]):int(self.cand_offsets[i + 1])] for i in order]
+        nodes = np.concatenate(parts) if parts else np.zeros(0, np.uint32)
+        return ResvQueries(self.start_sec[order], self.duration_sec[order], self.node_num[order], off, nodes,
+                           None if self.find_earliest is None else self.find_earliest[order])
+
+    def to_c(self) -> CnsResvqSoa:
+        s = CnsResvqSoa()
+        s.num_queries = self.num_queries
+        s.start_sec, s.duration_sec, s.node_num = _ptr(self.start_sec), _ptr(self.duration_sec), _ptr(self.node_num)
+        s.cand_offsets, s.cand_nodes, s.find_earliest = _ptr(self.cand_offsets), _ptr(self.cand_nodes), _ptr(self.find_earliest)
+        return s
+
+
+class ResvAnswers:
+    """Caller-allocated cns_resvq_out: status / start_sec / num_free per query, code per candidate, the chosen nodes as a CSR."""
+    FIELDS = ("status", "start_sec", "num_free", "code", "chosen_offsets", "chosen_nodes")
+
+    def __init__(self, queries: "ResvQueries", code_capacity: int | None = None, chosen_capacity: int | None = None):
+        q = queries.num_queries
+        lens = np.diff(queries.cand_offsets.astype(np.int64))
+        self.num_queries = q
+        self.code_capacity = int(lens.sum()) if code_capacity is None else code_capacity
+        self.chosen_capacity = int(np.minimum(queries.k(), lens).sum()) if chosen_capacity is None else chosen_capacity
+        self.status = np.zeros(max(q, 1), np.uint8)
+        self.start_sec = np.zeros(max(q, 1), np.int64)
+        self.num_free = np.zeros(max(q, 1), np.uint32)
+        self.code = np.zeros(max(self.code_capacity, 1), np.uint8)
+        self.chosen_offsets = np.zeros(q + 1, np.uint64)
+        self.chosen_nodes = np.zeros(max(self.chosen_capacity, 1), np.uint32)
+        self._codes = int(lens.sum())
+
+    def to_c(self) -> CnsResvqOut:
+        s = CnsResvqOut()
+        s.code_capacity, s.chosen_capacity = self.code_capacity, self.chosen_capacity
+        s.status, s.start_sec, s.num_free, s.code = _ptr(self.status), _ptr(self.start_sec), _ptr(self.num_free), _ptr(self.code)
+        s.chosen_offsets, s.chosen_nodes = _ptr(self.chosen_offsets), _ptr(self.chosen_nodes)
+        return s
+
+    def trimmed(self) -> dict:
+        """The arrays cut to what the call wrote."""
+        q = self.num_queries
+        return {"status": self.status[:q], "start_sec": self.start_sec[:q], "num_free": self.num_free[:q], "code": self.code[:self._codes],
+                "chosen_offsets": self.chosen_offsets, "chosen_nodes": self.chosen_nodes[:int(self.chosen_offsets[q])]}

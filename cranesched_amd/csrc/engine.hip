@@ -22,6 +22,7 @@
 #include "../../include/crane_gpu/preempt.h"
 #include "../../include/crane_gpu/priority.h"
 #include "../../include/crane_gpu_probe/probe.h"
+#include "../../include/crane_gpu_resv/resv_probe.h"
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
 #include <limits>
@@ -32,6 +33,7 @@
 #include "limits_kernels.hip"
 #include "steps_kernels.hip"
 #include "probe_kernel.inc"    // k_probe: what-if probes against the final state of a cycle (include/crane_gpu_probe/probe.h)
+#include "resvq_kernels.inc"  // reservation what-ifs: which nodes, how soon (include/crane_gpu_resv/resv_probe.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 #include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
 
@@ -154,6 +156,11 @@ struct cns_engine {
   bool pre_call = false;                        // inside cns_select_preempt with preemption enabled
   bool run_preempt = false;                     // the last successful cycle was such a call (probes are not served behind it)
   double probe_ms = 0.0;
+  // reservation what-ifs (resvq_host.inc): per-node tables, queries, event times and results in buffers of their own
+  DevBuf d_rq[32];
+  u32 rq_N = 0;                                 // the node count the tables were built for
+  std::vector<u32> rq_rv_cnt;                   // node -> reservations that list it
+  bool rq_have = false;
   cns_timing timing{};
   std::string last_kernel;
   i64 last_now = 0;
@@ -676,6 +683,7 @@ void cns_destroy(cns_handle* h) {
   for (DevBuf& b : h->d_step) b.release();
   for (DevBuf& b : h->d_pre) b.release();
   for (DevBuf& b : h->d_pb) b.release();
+  for (DevBuf& b : h->d_rq) b.release();
   h->d_gather.release();
   if (h->comm) (void)ncclCommDestroy((ncclComm_t)h->comm);
   for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
@@ -693,6 +701,7 @@ int cns_set_nodes(cns_handle* h, const cns_node_soa* nd) {
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = build_gres(h, nd->gres)) return rc;
   h->have_nodes = h->have_jobs = h->have_run = false;
+  h->rq_have = false;   // (the per-node tables of cns_resvq_set_state index the nodes of the snapshot they were built for)
   const u32 N = nd->num_nodes;
   u32 P = nd->num_partitions;
   std::vector<Res> total(N);
@@ -1662,6 +1671,7 @@ int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity
 #include "limits_host.inc"
 #include "steps_host.inc"
 #include "probe_host.inc"
+#include "resvq_host.inc"
 
 }  // extern "C"
 

@@ -43,6 +43,8 @@ STEPS_ABI_SYMBOLS = ("cns_schedule_steps",)
 PREEMPT_ABI_SYMBOLS = ("cns_select_preempt",)
 # ... and include/crane_gpu_probe/probe.h
 PROBE_ABI_SYMBOLS = ("cns_probe", "cns_probe_upload", "cns_probe_run_resident", "cns_probe_download")
+# ... and include/crane_gpu_resv/resv_probe.h
+RESVQ_ABI_SYMBOLS = ("cns_resvq_set_state", "cns_resvq_run")
 LIMITS_ABI_SYMBOLS = ("cns_set_run_limits", "cns_apply_run_limits", "cns_upload_limit_jobs", "cns_run_limits_resident",
                       "cns_download_limits", "cns_get_limit_timing", "cns_get_usage")
 
@@ -360,6 +362,29 @@ class GpuNodeSelector:
     def probe_timing(self) -> dict:
         """HIP-event time of the last k_probe launch of this object."""
         return {"kernel_ms": getattr(self, "_probe_ms", 0.0)}
+
+    # -- reservation what-ifs (include/crane_gpu_resv/resv_probe.h) --------------------------------------------------------
+    def set_resv_query_state(self, running: "abi.Running | None", reservations: "abi.Reservations | None"):
+        """Per-node tables for query_reservations: the latest end of the running allocations on every node and the (start, end) of
+        every reservation that lists it.  After set_nodes; independent of the cycle's set_running / set_reservations."""
+        rn = running.to_c() if running is not None else None
+        rv = reservations.to_c() if reservations is not None else None
+        self._check(self._L.cns_resvq_set_state(self._h, C.byref(rn) if rn is not None else None, C.byref(rv) if rv is not None else None))
+
+    def query_reservations(self, now: int, queries: "abi.ResvQueries", out: "abi.ResvAnswers | None" = None) -> dict:
+        """JobScheduler::CreateResv_'s node walk (JobScheduler.cpp:4383-4419) for every query at once, at its start or at the earliest
+        start that fits; nothing is created.  -> {status, start_sec, num_free, code, chosen_offsets, chosen_nodes} as numpy arrays."""
+        if out is None:
+            out = abi.ResvAnswers(queries)
+        cq, co = queries.to_c(), out.to_c()
+        ms = C.c_double(0)
+        self._check(self._L.cns_resvq_run(self._h, C.c_int64(now), C.byref(cq), C.byref(co), C.byref(ms)))
+        self._resvq_ms = ms.value
+        return out.trimmed()
+
+    def resv_query_timing(self) -> dict:
+        """HIP-event time of the kernels of the last query_reservations of this object."""
+        return {"kernel_ms": getattr(self, "_resvq_ms", 0.0)}
 
     def device_results(self):
         p, n = C.c_void_p(), C.c_uint64()

@@ -18,6 +18,7 @@
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
 #include "../../include/crane_gpu_probe/probe.h"
+#include "../../include/crane_gpu_resv/resv_probe.h"
 
 namespace crane {
 
@@ -79,6 +80,7 @@ struct GpuNodeSelectionAlgo::Impl {
   std::vector<std::vector<SlotId>> class_bit_slot;          // per class: bit offset -> slot path
   cns_gres_layout layout{};
   bool have_snapshot = false;
+  bool resvq_stale = true;   // the engine's per-node tables of the reservation what-ifs are older than the packed running set / the snapshot
   std::vector<const PdJobInScheduler*> last_ord;                      // the jobs of the last cns_select, in its order
   std::unordered_map<const PdJobInScheduler*, uint64_t> last_index;  // job -> its index there (built when the run-limit pass asks)
   // Incremental packing of the running jobs: an allocation never changes while its job runs, so its
@@ -109,6 +111,7 @@ struct GpuNodeSelectionAlgo::Impl {
     nd.gres = layout;
     nd.core_w2 = n_w2.data(); nd.core_w3 = n_w3.data();
     nd.unsupported = n_unsup.empty() ? nullptr : n_unsup.data();
+    resvq_stale = true;
     int st = grp ? cns_group_set_nodes(grp, &nd) : cns_set_nodes(h, &nd);
     if (st != 0) { err = grp ? cns_group_last_error(grp) : cns_last_error(h); return st; }
     if (!v_start.empty()) {
@@ -422,6 +425,7 @@ struct GpuNodeSelectionAlgo::Impl {
     return true;
   }
   void pack_from_mirror() {
+    resvq_stale = true;
     r_src.clear();        // the mirror has no RnJobInScheduler objects: a cycle with preemption must be refused, never served from an
     r_src_valid = false;  // earlier explicit cycle's (freed) pointers that happen to match in number
     if (!mirror_packed || mirror_full || !pack_from_mirror_patch()) pack_from_mirror_full();
@@ -449,6 +453,7 @@ struct GpuNodeSelectionAlgo::Impl {
     r_end.clear(); r_cpu.clear(); r_node.clear(); r_resv.clear(); r_mem.clear(); r_lo.clear(); r_hi.clear(); r_g.clear(); r_w2.clear(); r_w3.clear();
     r_src.clear();
     r_src_valid = true;
+    resvq_stale = true;
     mirror_packed = false;   // (r_* now hold the caller's vector)
     packed_from_mirror = false;
     run_overflow = false;
@@ -1287,6 +1292,83 @@ void GpuNodeSelectionAlgo::ProbeStart(const std::vector<PdJobInScheduler*>& jobs
   I.lazy_write_back = false; I.deferred_write_back = false;
   I.write_back(jobs, out);
   I.lazy_write_back = lazy; I.deferred_write_back = deferred;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Reservation what-ifs (include/crane_gpu_resv/resv_probe.h)
+// ---------------------------------------------------------------------------------------------------------
+std::vector<GpuNodeSelectionAlgo::ResvAnswer> GpuNodeSelectionAlgo::QueryReservation(const TimeSec& now, std::span<const ResvRequest> requests,
+                                                                                     double* kernel_ms) {
+  Impl& I = *impl_;
+  if (kernel_ms) *kernel_ms = 0.0;
+  auto fail = [&](int st, const std::string& msg) { status_ = st; error_ = msg; return std::vector<ResvAnswer>{}; };
+  if (I.grp) return fail(CNS_ERR_UNSUPPORTED, "QueryReservation on an algorithm object over several devices");
+  if (!I.h) return fail(status_ ? status_ : CNS_ERR_NO_DEVICE, error_);
+  if (!I.have_snapshot) return fail(CNS_ERR_STATE, "QueryReservation before SetClusterSnapshot");
+  // the per-node tables from what the adapter keeps packed across cycles: the running set of the last pack, the snapshot's reservations;
+  // rebuilt only when one of the two was packed anew since the last call
+  int st = 0;
+  if (I.resvq_stale) {
+    cns_running_soa rs{};
+    rs.num_jobs = (uint32_t)I.r_end.size(); rs.num_allocs = (uint32_t)I.r_node.size();
+    rs.end_sec = I.r_end.data(); rs.alloc_offsets = I.r_off.data(); rs.alloc_node = I.r_node.data();
+    cns_resv_soa rv{};
+    rv.num_resv = (uint32_t)I.v_start.size(); rv.num_allocs = (uint32_t)I.v_node.size();
+    rv.start_sec = I.v_start.data(); rv.end_sec = I.v_end.data(); rv.alloc_offsets = I.v_off.data(); rv.alloc_node = I.v_node.data();
+    st = cns_resvq_set_state(I.h, rs.num_jobs ? &rs : nullptr, rv.num_resv ? &rv : nullptr);
+    if (st != 0) return fail(st, cns_last_error(I.h));
+    I.resvq_stale = false;
+  }
+  const size_t Q = requests.size();
+  const uint32_t N = (uint32_t)I.node_name.size();
+  std::vector<int64_t> start(Q), dur(Q);
+  std::vector<uint32_t> k(Q), cand;
+  std::vector<uint64_t> off(Q + 1, 0);
+  std::vector<uint8_t> mode(Q);
+  uint64_t chosen_cap = 0;
+  std::unordered_map<CranedId, uint32_t> unknown;   // a name no node of the snapshot has: an index >= N of its own ("not found", :4385-4388)
+  for (size_t q = 0; q < Q; ++q) {
+    const ResvRequest& r = requests[q];
+    start[q] = r.start; dur[q] = r.duration; k[q] = r.node_num; mode[q] = r.find_earliest ? 1 : 0;
+    unknown.clear();
+    for (const CranedId& id : r.craned_ids) {
+      auto it = I.node_idx.find(id);
+      cand.push_back(it != I.node_idx.end() ? it->second : unknown.emplace(id, N + (uint32_t)unknown.size()).first->second);
+    }
+    off[q + 1] = cand.size();
+    chosen_cap += r.node_num ? std::min<uint64_t>(r.node_num, r.craned_ids.size()) : r.craned_ids.size();
+  }
+  cns_resvq_soa qs{};
+  qs.num_queries = Q; qs.start_sec = start.data(); qs.duration_sec = dur.data(); qs.node_num = k.data();
+  qs.cand_offsets = off.data(); qs.cand_nodes = cand.data(); qs.find_earliest = mode.data();
+  std::vector<uint8_t> status(Q + 1), code(cand.size() + 1);
+  std::vector<int64_t> ostart(Q + 1);
+  std::vector<uint32_t> nfree(Q + 1), chosen(chosen_cap + 1);
+  std::vector<uint64_t> choff(Q + 1, 0);
+  cns_resvq_out out{};
+  out.code_capacity = cand.size(); out.chosen_capacity = chosen_cap;
+  out.status = status.data(); out.start_sec = ostart.data(); out.num_free = nfree.data(); out.code = code.data();
+  out.chosen_offsets = choff.data(); out.chosen_nodes = chosen.data();
+  st = cns_resvq_run(I.h, now, &qs, &out, kernel_ms);
+  if (st != 0) return fail(st, cns_last_error(I.h));
+  status_ = 0;
+  error_.clear();
+  std::vector<ResvAnswer> ans(Q);
+  for (size_t q = 0; q < Q; ++q) {
+    ResvAnswer& a = ans[q];
+    a.ok = status[q] == CNS_RESVQ_OK;
+    a.in_the_past = status[q] == CNS_RESVQ_IN_THE_PAST;
+    a.start = ostart[q];
+    if (a.in_the_past) continue;
+    for (uint64_t c = choff[q]; c < choff[q + 1]; ++c) a.chosen.push_back(I.node_name[chosen[c]]);
+    const std::vector<CranedId>& ids = requests[q].craned_ids;
+    for (size_t i = 0; i < ids.size(); ++i) {
+      const uint8_t cd = code[off[q] + i];
+      if (cd == CNS_RESVQ_NOT_FOUND) a.not_found.push_back(ids[i]);
+      else if (cd != CNS_RESVQ_FREE) a.conflicted.push_back(ids[i]);
+    }
+  }
+  return ans;
 }
 
 // ---------------------------------------------------------------------------------------------------------

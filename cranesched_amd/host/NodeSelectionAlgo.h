@@ -22,6 +22,7 @@
 #include <map>
 #include <memory>
 #include <set>
+#include <span>
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
@@ -353,6 +354,31 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   // preemption, no device) the jobs without a reason get "GpuEngineError" and Ok() / LastStatus() / LastError() say why; nothing is
   // thrown.  One device only: an algorithm object built over several devices refuses with CNS_ERR_UNSUPPORTED.
   void ProbeStart(const std::vector<PdJobInScheduler*>& jobs);
+
+  // ---- reservation what-ifs (include/crane_gpu_resv/resv_probe.h) ----------------------------------------------------------------
+  // The node walk of JobScheduler::CreateResv_ (JobScheduler.cpp:4383-4419) for every request at once, against the running set the
+  // adapter packed last (NodeSelect / the mirror) and the reservations of the snapshot: which of `craned_ids` could the reservation
+  // take, in list order — at `start`, or with find_earliest at the first start >= `start` at which `node_num` of them are free for
+  // `duration` (node_num 0: all of the list, :4357-4358).  Nothing is created.  Per request what CreateResv_'s error text is built
+  // from (:4421-4437): ok, the start the answer holds for, the chosen nodes, and the conflicted / not-found nodes of the WHOLE list at
+  // that start (the reference stops at the node_num-th free node; its lists are the prefix up to there).  A request whose end is not
+  // after `now` (:4323) comes back with in_the_past and nothing else.  On an engine error (no device, no snapshot, a node named twice
+  // in one list, duration <= 0) the result is empty and Ok() / LastStatus() / LastError() say why; nothing is thrown.
+  // The engine's per-node tables (cns_resvq_set_state) are rebuilt only when the running set or the snapshot was packed anew since the
+  // last call.  As in a cycle, a running job whose reservation name the snapshot does not know is not part of the packed running set.
+  struct ResvRequest {
+    TimeSec start{0};
+    int64_t duration{0};
+    uint32_t node_num{0};
+    std::vector<CranedId> craned_ids;
+    bool find_earliest{false};
+  };
+  struct ResvAnswer {
+    bool ok{false}, in_the_past{false};
+    TimeSec start{0};
+    std::vector<CranedId> chosen, conflicted, not_found;
+  };
+  std::vector<ResvAnswer> QueryReservation(const TimeSec& now, std::span<const ResvRequest> requests, double* kernel_ms = nullptr);
 
   // ---- event-fed mirror of the running allocations -------------------------------------------------
   // Instead of re-deriving the running jobs' allocations from the vector NodeSelect is handed every cycle, the adapter
