@@ -595,3 +595,16 @@ class ResvAnswers:
         q = self.num_queries
         return {"status": self.status[:q], "start_sec": self.start_sec[:q], "num_free": self.num_free[:q], "code": self.code[:self._codes],
                 "chosen_offsets": self.chosen_offsets, "chosen_nodes": self.chosen_nodes[:int(self.chosen_offsets[q])]}
+
+
+# ---- validity of a batch of submissions (include/crane_gpu_valid/validity.h) ---------------------------------------------
+(VALID_OK, VALID_BAD_REQUEST, VALID_ZERO_MEM, VALID_ZERO_CPU, VALID_PARTITION_NOT_FOUND, VALID_REFUSED, VALID_NO_RESOURCE,
+ VALID_NODE_NUM, VALID_RESV_NOT_FOUND, VALID_RESV_NODE, VALID_NOT_ENOUGH_NODES) = range(11)
+VALID_STR = {VALID_OK: "OK", VALID_BAD_REQUEST: "BAD_REQUEST", VALID_ZERO_MEM: "ZERO_MEM", VALID_ZERO_CPU: "ZERO_CPU",
+             VALID_PARTITION_NOT_FOUND: "PARTITION_NOT_FOUND", VALID_REFUSED: "REFUSED", VALID_NO_RESOURCE: "NO_RESOURCE",
+             VALID_NODE_NUM: "NODE_NUM", VALID_RESV_NOT_FOUND: "RESV_NOT_FOUND", VALID_RESV_NODE: "RESV_NODE",
+             VALID_NOT_ENOUGH_NODES: "NOT_ENOUGH_NODES"}
+
+
+class CnsValidityOut(C.Structure):
+    _fields_ = [("code", _P), ("eligible", _P)]

@@ -23,6 +23,7 @@
 #include "../../include/crane_gpu/priority.h"
 #include "../../include/crane_gpu_probe/probe.h"
 #include "../../include/crane_gpu_resv/resv_probe.h"
+#include "../../include/crane_gpu_valid/validity.h"
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
 #include <limits>
@@ -34,6 +35,7 @@
 #include "steps_kernels.hip"
 #include "probe_kernel.inc"    // k_probe: what-if probes against the final state of a cycle (include/crane_gpu_probe/probe.h)
 #include "resvq_kernels.inc"  // reservation what-ifs: which nodes, how soon (include/crane_gpu_resv/resv_probe.h)
+#include "valid_kernels.inc"  // can each job of a batch ever run in its partition (include/crane_gpu_valid/validity.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 #include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
 
@@ -161,6 +163,15 @@ struct cns_engine {
   u32 rq_N = 0;                                 // the node count the tables were built for
   std::vector<u32> rq_rv_cnt;                   // node -> reservations that list it
   bool rq_have = false;
+  // the validity check of a batch of submissions (valid_host.inc): the caller's node arrays as cns_set_nodes got them, derived tables,
+  // the call's job arrays and results in buffers of their own
+  DevBuf d_vd[28];
+  std::vector<i64> vd_cpu;
+  std::vector<u64> vd_mem, vd_gres;
+  std::vector<uint8_t> vd_unsup;
+  std::vector<u32> vd_poff, vd_pnodes;          // the caller's partition lists: every listed node, schedulable or not
+  u32 vd_V = 0;                                 // reservations of the device's membership table
+  bool vd_tab_have = false, vd_rv_have = false; // the tables derived from the node arrays / from the reservations are built
   cns_timing timing{};
   std::string last_kernel;
   i64 last_now = 0;
@@ -684,6 +695,7 @@ void cns_destroy(cns_handle* h) {
   for (DevBuf& b : h->d_pre) b.release();
   for (DevBuf& b : h->d_pb) b.release();
   for (DevBuf& b : h->d_rq) b.release();
+  for (DevBuf& b : h->d_vd) b.release();
   h->d_gather.release();
   if (h->comm) (void)ncclCommDestroy((ncclComm_t)h->comm);
   for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
@@ -693,6 +705,7 @@ void cns_destroy(cns_handle* h) {
   delete h;
 }
 
+static void valid_keep_nodes(cns_handle* h, const cns_node_soa* nd);   // valid_host.inc
 int cns_set_nodes(cns_handle* h, const cns_node_soa* nd) {
   if (!h || !nd) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_nodes: null argument");
   if (!nd->cpu_total_raw || !nd->mem_total || !nd->core_lo || !nd->part_offsets || (!nd->part_nodes && nd->part_offsets[nd->num_partitions]))
@@ -854,6 +867,7 @@ int cns_set_nodes(cns_handle* h, const cns_node_soa* nd) {
   h->resv_start.clear(); h->resv_end.clear(); h->resv_node_slot.clear();
   h->rv_off.assign(S + 1, 0); h->rv_start.clear(); h->rv_endt.clear(); h->rv_res.clear();
   if (int rc = finalize_layout(h)) return rc;
+  valid_keep_nodes(h, nd);   // (cns_validate_jobs derives its tables from these at its first call)
   h->have_nodes = true;
   return CNS_OK;
 }
@@ -863,6 +877,7 @@ int cns_set_reservations(cns_handle* h, const cns_resv_soa* rv) {
   if (!h->have_nodes) return fail(h, CNS_ERR_STATE, "cns_set_reservations before cns_set_nodes");
   HIPCHK(h, hipSetDevice(h->device));
   h->have_jobs = h->have_run = false;
+  h->vd_rv_have = false;   // (cns_validate_jobs rebuilds its table of the reservations' nodes)
   const u32 V = rv ? rv->num_resv : 0;
   if (V && (!rv->start_sec || !rv->end_sec || !rv->alloc_offsets || !rv->alloc_node || !rv->alloc_cpu_raw ||
             !rv->alloc_mem || !rv->alloc_core_lo))
@@ -1672,6 +1687,7 @@ int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity
 #include "steps_host.inc"
 #include "probe_host.inc"
 #include "resvq_host.inc"
+#include "valid_host.inc"
 
 }  // extern "C"
 

@@ -45,6 +45,8 @@ PREEMPT_ABI_SYMBOLS = ("cns_select_preempt",)
 PROBE_ABI_SYMBOLS = ("cns_probe", "cns_probe_upload", "cns_probe_run_resident", "cns_probe_download")
 # ... and include/crane_gpu_resv/resv_probe.h
 RESVQ_ABI_SYMBOLS = ("cns_resvq_set_state", "cns_resvq_run")
+# ... and include/crane_gpu_valid/validity.h
+VALID_ABI_SYMBOLS = ("cns_validate_jobs", "cns_validate_shape")
 LIMITS_ABI_SYMBOLS = ("cns_set_run_limits", "cns_apply_run_limits", "cns_upload_limit_jobs", "cns_run_limits_resident",
                       "cns_download_limits", "cns_get_limit_timing", "cns_get_usage")
 
@@ -385,6 +387,30 @@ class GpuNodeSelector:
     def resv_query_timing(self) -> dict:
         """HIP-event time of the kernels of the last query_reservations of this object."""
         return {"kernel_ms": getattr(self, "_resvq_ms", 0.0)}
+
+    # -- validity of a batch of submissions (include/crane_gpu_valid/validity.h) -------------------------------------------
+    def validate_jobs(self, jobs: "abi.Jobs", out=None):
+        """JobScheduler::CheckJobValidity's partition checks (JobScheduler.cpp:7262-7374) for every job at once: can the job EVER run in
+        its partition.  -> (code, eligible): abi.VALID_* per job, and the number of nodes of its partition that pass the walk's test.
+        out: (code uint8 [J], eligible uint32 [J]) to write into, else fresh arrays."""
+        j = jobs.num_jobs
+        code, elig = out if out is not None else (np.zeros(max(j, 1), np.uint8), np.zeros(max(j, 1), np.uint32))
+        cj = jobs.to_c()
+        co = abi.CnsValidityOut(abi._ptr(code), abi._ptr(elig))
+        ms = C.c_double(0)
+        self._check(self._L.cns_validate_jobs(self._h, C.byref(cj), C.byref(co), C.byref(ms)))
+        self._valid_ms = ms.value
+        return code[:j], elig[:j]
+
+    def validate_shape(self):
+        """(node_tile, job_chunk) of the walk kernel: where its paths change."""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._L.cns_validate_shape(C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def validity_timing(self) -> dict:
+        """HIP-event time of the walk kernel of the last validate_jobs of this object."""
+        return {"kernel_ms": getattr(self, "_valid_ms", 0.0)}
 
     def device_results(self):
         p, n = C.c_void_p(), C.c_uint64()

@@ -19,6 +19,7 @@
 #include "../../include/crane_gpu/steps.h"
 #include "../../include/crane_gpu_probe/probe.h"
 #include "../../include/crane_gpu_resv/resv_probe.h"
+#include "../../include/crane_gpu_valid/validity.h"
 
 namespace crane {
 
@@ -1369,6 +1370,61 @@ std::vector<GpuNodeSelectionAlgo::ResvAnswer> GpuNodeSelectionAlgo::QueryReserva
     }
   }
   return ans;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Validity of a batch of submissions (include/crane_gpu_valid/validity.h)
+// ---------------------------------------------------------------------------------------------------------
+bool GpuNodeSelectionAlgo::CheckJobValidity(const std::vector<const PdJobInScheduler*>& jobs, std::vector<ValidityAnswer>* out, double* kernel_ms) {
+  Impl& I = *impl_;
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (out) out->clear();
+  auto fail = [&](int st, const std::string& msg) { status_ = st; error_ = msg; return false; };
+  if (!out) return fail(CNS_ERR_INVALID_ARG, "CheckJobValidity: null result");
+  if (I.grp) return fail(CNS_ERR_UNSUPPORTED, "CheckJobValidity on an algorithm object over several devices");
+  if (!I.h) return fail(status_ ? status_ : CNS_ERR_NO_DEVICE, error_);
+  if (!I.have_snapshot) return fail(CNS_ERR_STATE, "CheckJobValidity before SetClusterSnapshot");
+  const size_t Q = jobs.size();
+  if (Q == 0) { status_ = 0; error_.clear(); return true; }
+  // the packer of the cycle, into a table of its own (without a placement store it writes nothing into a job)
+  std::vector<PdJobInScheduler*> ord(Q);
+  for (size_t j = 0; j < Q; ++j) ord[j] = const_cast<PdJobInScheduler*>(jobs[j]);
+  Impl::PackedJobs B(nullptr);
+  I.pack_pending(ord, B);
+  // an included name no node of the snapshot has matches nothing (the reference holds names): an index >= N of its own inside its list
+  // (the packer gives every such name the same index; a list is a set)
+  const uint32_t N = (uint32_t)I.node_name.size();
+  for (size_t j = 0; j < Q; ++j) {
+    uint32_t unknown = 0;
+    for (uint64_t x = B.ioff[j]; x < B.ioff[j + 1]; ++x)
+      if (B.inodes[x] >= N) B.inodes[x] = N + unknown++;
+  }
+  cns_job_soa js{};
+  js.num_jobs = Q;
+  js.partition = B.part.data(); js.time_limit_sec = B.L.data(); js.node_cpu_raw = B.ncpu.data(); js.node_mem = B.nmem.data();
+  js.task_cpu_raw = B.tcpu.data(); js.task_mem = B.tmem.data(); js.node_num = B.k.data(); js.ntasks = B.nt.data();
+  js.ntasks_per_node_min = B.tmin.data(); js.ntasks_per_node_max = B.tmax.data(); js.exclusive = B.excl.data();
+  js.gres_total = B.gtot.data(); js.gres_spec = B.gspec.data(); js.incl_offsets = B.ioff.data(); js.incl_nodes = B.inodes.data();
+  js.excl_offsets = B.eoff.data(); js.excl_nodes = B.enodes.data(); js.skip = B.skip.data(); js.reservation = B.jresv.data();
+  std::vector<uint8_t> code(Q);
+  std::vector<uint32_t> elig(Q);
+  cns_validity_out vo{code.data(), elig.data()};
+  const int st = cns_validate_jobs(I.h, &js, &vo, kernel_ms);
+  if (st != 0) return fail(st, cns_last_error(I.h));
+  status_ = 0;
+  error_.clear();
+  static const char* const kErr[] = {"", "ERR_INVALID_PARAM", "ERR_INVALID_PARAM", "ERR_INVALID_PARAM", "ERR_INVALID_PARTITION", "", "ERR_NO_RESOURCE",
+                                     "ERR_INVALID_NODE_NUM", "ERR_INVALID_PARAM", "ERR_INVALID_PARAM", "ERR_NO_ENOUGH_NODE"};
+  static_assert(CNS_VALID_NOT_ENOUGH_NODES == 10 && CNS_VALID_NO_RESOURCE == 6 && CNS_VALID_NODE_NUM == 7 && CNS_VALID_PARTITION_NOT_FOUND == 4 && CNS_VALID_REFUSED == 5,
+                "kErr follows cns_valid_code");
+  out->resize(Q);
+  for (size_t j = 0; j < Q; ++j) {
+    ValidityAnswer& a = (*out)[j];
+    a.code = code[j]; a.eligible = elig[j];
+    a.crane_err = code[j] <= CNS_VALID_NOT_ENOUGH_NODES ? kErr[code[j]] : "ERR_INVALID_PARAM";
+    a.refused = code[j] == CNS_VALID_REFUSED;
+  }
+  return true;
 }
 
 // ---------------------------------------------------------------------------------------------------------

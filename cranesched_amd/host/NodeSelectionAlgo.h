@@ -380,6 +380,31 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   };
   std::vector<ResvAnswer> QueryReservation(const TimeSec& now, std::span<const ResvRequest> requests, double* kernel_ms = nullptr);
 
+  // ---- validity of a batch of submissions (include/crane_gpu_valid/validity.h) -----------------------------------------------------
+  // The partition checks of JobScheduler::CheckJobValidity (JobScheduler.cpp:7262-7374) for every job at once: can the partition the
+  // job names EVER run it, and on how many of its nodes — the call at :371 batched over the recovered queue, or a bulk re-check after a
+  // partition changed.  The jobs go through the packer of the cycle; nothing of a job is written.  Per job the engine's code
+  // (cns_valid_code), the number of nodes of the partition that pass the walk's test (the full count, :7364's break is not taken) and
+  // the CraneErrCode NAME the reference returns there: "" when the job is valid, ERR_INVALID_PARAM (:7264,:7268,:7312,:7347; also a
+  // request whose arithmetic overflows), ERR_INVALID_PARTITION (an unknown partition: the reference refuses it before this function,
+  // :7022), ERR_NO_RESOURCE (:7296), ERR_INVALID_NODE_NUM (:7304), ERR_NO_ENOUGH_NODE (:7373).  `refused`: the partition lists a node
+  // this adapter could not express (UnsupportedNodes()): nothing was decided, ask the CPU code.
+  // What the snapshot packs as res_total of a node that is down or drained is its res_total, unchanged: SetCranedState only flips the
+  // schedulable flag, as CranedDown leaves res_total alone (CranedMetaContainer.cpp:83-122) — and the walk (:7354-7357) reads exactly that,
+  // whether the node is alive or not; the check does not read the flag.
+  // The packer saturates GRES counts (a total at 255, a specified count at 127; an unknown name or type: 255): such a request is never
+  // valid, but where the reference says ERR_NO_RESOURCE for a count between the saturation and the partition's total this says
+  // ERR_NO_ENOUGH_NODE.  The time limit, the array spec, the deadline and the reservation's partition / account / user lists
+  // (:7225-7272,:7317-7336) stay with the caller.  false on an engine error (no device, no snapshot, several devices: CNS_ERR_UNSUPPORTED, as
+  // ProbeStart): `out` is empty and Ok() / LastStatus() / LastError() say why; nothing is thrown.
+  struct ValidityAnswer {
+    uint8_t code{0};               // cns_valid_code
+    uint32_t eligible{0};
+    const char* crane_err{""};     // CraneErrCode name, "" = valid (or refused)
+    bool refused{false};
+  };
+  bool CheckJobValidity(const std::vector<const PdJobInScheduler*>& jobs, std::vector<ValidityAnswer>* out, double* kernel_ms = nullptr);
+
   // ---- event-fed mirror of the running allocations -------------------------------------------------
   // Instead of re-deriving the running jobs' allocations from the vector NodeSelect is handed every cycle, the adapter
   // can be told what the meta container is told: the same calls, at the same places (JobScheduler.cpp:1590-1612 for the
