@@ -608,3 +608,99 @@ VALID_STR = {VALID_OK: "OK", VALID_BAD_REQUEST: "BAD_REQUEST", VALID_ZERO_MEM: "
 
 class CnsValidityOut(C.Structure):
     _fields_ = [("code", _P), ("eligible", _P)]
+
+
+# ---- the commit loop's checks behind a cycle (include/crane_gpu_commit/commit_check.h) ------------------------------------
+CC_TIME_INFINITE_PAST = -(1 << 63)
+(COMMIT_OK, COMMIT_GONE, COMMIT_NOT_STARTED, COMMIT_RESOURCE_CHANGED, COMMIT_RESV_DELETED, COMMIT_RESV_ENDS_EARLY, COMMIT_RESV_CHANGED,
+ COMMIT_WAITING_PREEMPTION) = range(8)
+COMMIT_STR = {COMMIT_OK: "OK", COMMIT_GONE: "GONE", COMMIT_NOT_STARTED: "NOT_STARTED", COMMIT_RESOURCE_CHANGED: "RESOURCE_CHANGED",
+              COMMIT_RESV_DELETED: "RESV_DELETED", COMMIT_RESV_ENDS_EARLY: "RESV_ENDS_EARLY", COMMIT_RESV_CHANGED: "RESV_CHANGED",
+              COMMIT_WAITING_PREEMPTION: "WAITING_PREEMPTION"}
+# what the reference writes into job->reason there (JobScheduler.cpp:1518-1552); "" where it writes nothing
+COMMIT_REASON = {COMMIT_OK: "", COMMIT_GONE: "", COMMIT_NOT_STARTED: "", COMMIT_RESOURCE_CHANGED: "Resource changed",
+                 COMMIT_RESV_DELETED: "Reservation deleted", COMMIT_RESV_ENDS_EARLY: "Resource", COMMIT_RESV_CHANGED: "Reservation changed",
+                 COMMIT_WAITING_PREEMPTION: "Waiting for Preemption"}
+
+
+class CnsCommitEvents(C.Structure):
+    _fields_ = [("num_node_events", C.c_uint32), ("num_affected_resv", C.c_uint32), ("ev_time_sec", _P), ("ev_offsets", _P), ("ev_nodes", _P),
+                ("ar_resv", _P), ("ar_exists", _P), ("ar_end_sec", _P), ("ar_offsets", _P), ("ar_nodes", _P)]
+
+
+class CnsCommitJobs(C.Structure):
+    _fields_ = [("num_jobs", C.c_uint64), ("time_limit_sec", _P), ("reservation", _P), ("gone", _P), ("preempt_offsets", _P), ("preempted", _P),
+                ("num_running", C.c_uint32), ("reserved0", C.c_uint32), ("running_alive", _P)]
+
+
+class CnsCommitOut(C.Structure):
+    _fields_ = [("code", _P), ("counts", _P)]
+
+
+def _csr(lists):
+    off = np.zeros(len(lists) + 1, np.uint64)
+    off[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64) if len(lists) else []
+    flat = np.asarray([int(v) for x in lists for v in x], np.uint32)
+    return off, flat
+
+
+@dataclass
+class CommitEvents:
+    """cns_commit_events: what LockAndGetResReduceEvents() holds, split by alternative.
+    node_events: [(time_sec, [node, ...]), ...];  affected_resv: [(resv index, exists, end_sec, [node, ...]), ...]."""
+    node_events: list = field(default_factory=list)
+    affected_resv: list = field(default_factory=list)
+
+    def __post_init__(self):
+        self.ev_time_sec = np.asarray([int(t) for t, _ in self.node_events], np.int64)
+        self.ev_offsets, self.ev_nodes = _csr([n for _, n in self.node_events])
+        self.ar_resv = np.asarray([int(a[0]) for a in self.affected_resv], np.uint32)
+        self.ar_exists = np.asarray([1 if a[1] else 0 for a in self.affected_resv], np.uint8)
+        self.ar_end_sec = np.asarray([int(a[2]) for a in self.affected_resv], np.int64)
+        self.ar_offsets, self.ar_nodes = _csr([a[3] for a in self.affected_resv])
+
+    def to_c(self) -> CnsCommitEvents:
+        s = CnsCommitEvents()
+        s.num_node_events, s.num_affected_resv = len(self.ev_time_sec), len(self.ar_resv)
+        for f, _ in CnsCommitEvents._fields_[2:]:
+            a = getattr(self, f)
+            setattr(s, f, _ptr(a if len(a) else np.zeros(1, a.dtype)))
+        return s
+
+
+@dataclass
+class CommitJobs:
+    """cns_commit_jobs: the queue of the last cycle.  time_limit_sec / reservation as given to the cycle, gone[j] != 0: no longer in the
+    pending map; preempt_offsets / preempted: the cycle's PreemptOut; running_alive[r] != 0: running job r is still in the running map."""
+    time_limit_sec: np.ndarray
+    reservation: Optional[np.ndarray] = None
+    gone: Optional[np.ndarray] = None
+    preempt_offsets: Optional[np.ndarray] = None
+    preempted: Optional[np.ndarray] = None
+    running_alive: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        self.time_limit_sec = _arr(self.time_limit_sec, np.int64)
+        n = len(self.time_limit_sec)
+        if self.reservation is not None:
+            self.reservation = _arr(self.reservation, np.uint32, n)
+        if self.gone is not None:
+            self.gone = _arr(self.gone, np.uint8, n)
+        if self.preempt_offsets is not None:
+            self.preempt_offsets = _arr(self.preempt_offsets, np.uint64, n + 1)
+            self.preempted = _arr(self.preempted if self.preempted is not None else [], np.uint32)
+        if self.running_alive is not None:
+            self.running_alive = _arr(self.running_alive, np.uint8)
+
+    @property
+    def num_jobs(self) -> int:
+        return len(self.time_limit_sec)
+
+    def to_c(self) -> CnsCommitJobs:
+        s = CnsCommitJobs()
+        s.num_jobs = self.num_jobs
+        for f in ("time_limit_sec", "reservation", "gone", "preempt_offsets", "preempted", "running_alive"):
+            a = getattr(self, f)
+            setattr(s, f, None if a is None else _ptr(a if len(a) else np.zeros(1, a.dtype)))
+        s.num_running = 0 if self.running_alive is None else len(self.running_alive)
+        return s

@@ -24,6 +24,7 @@
 #include "../../include/crane_gpu_probe/probe.h"
 #include "../../include/crane_gpu_resv/resv_probe.h"
 #include "../../include/crane_gpu_valid/validity.h"
+#include "../../include/crane_gpu_commit/commit_check.h"
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
 #include <limits>
@@ -36,6 +37,7 @@
 #include "probe_kernel.inc"    // k_probe: what-if probes against the final state of a cycle (include/crane_gpu_probe/probe.h)
 #include "resvq_kernels.inc"  // reservation what-ifs: which nodes, how soon (include/crane_gpu_resv/resv_probe.h)
 #include "valid_kernels.inc"  // can each job of a batch ever run in its partition (include/crane_gpu_valid/validity.h)
+#include "commit_kernels.inc" // the commit loop's resource-changed and preempted-alive checks (include/crane_gpu_commit/commit_check.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 #include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
 
@@ -172,6 +174,8 @@ struct cns_engine {
   std::vector<u32> vd_poff, vd_pnodes;          // the caller's partition lists: every listed node, schedulable or not
   u32 vd_V = 0;                                 // reservations of the device's membership table
   bool vd_tab_have = false, vd_rv_have = false; // the tables derived from the node arrays / from the reservations are built
+  // the commit loop's checks behind a cycle (commit_host.inc): the call's events, job arrays and results in buffers of their own
+  DevBuf d_cc[18];
   cns_timing timing{};
   std::string last_kernel;
   i64 last_now = 0;
@@ -696,6 +700,7 @@ void cns_destroy(cns_handle* h) {
   for (DevBuf& b : h->d_pb) b.release();
   for (DevBuf& b : h->d_rq) b.release();
   for (DevBuf& b : h->d_vd) b.release();
+  for (DevBuf& b : h->d_cc) b.release();
   h->d_gather.release();
   if (h->comm) (void)ncclCommDestroy((ncclComm_t)h->comm);
   for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
@@ -1688,6 +1693,7 @@ int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity
 #include "probe_host.inc"
 #include "resvq_host.inc"
 #include "valid_host.inc"
+#include "commit_host.inc"
 
 }  // extern "C"
 

@@ -47,6 +47,8 @@ PROBE_ABI_SYMBOLS = ("cns_probe", "cns_probe_upload", "cns_probe_run_resident", 
 RESVQ_ABI_SYMBOLS = ("cns_resvq_set_state", "cns_resvq_run")
 # ... and include/crane_gpu_valid/validity.h
 VALID_ABI_SYMBOLS = ("cns_validate_jobs", "cns_validate_shape")
+# ... and include/crane_gpu_commit/commit_check.h
+COMMIT_ABI_SYMBOLS = ("cns_commit_check", "cns_commit_shape")
 LIMITS_ABI_SYMBOLS = ("cns_set_run_limits", "cns_apply_run_limits", "cns_upload_limit_jobs", "cns_run_limits_resident",
                       "cns_download_limits", "cns_get_limit_timing", "cns_get_usage")
 
@@ -411,6 +413,32 @@ class GpuNodeSelector:
     def validity_timing(self) -> dict:
         """HIP-event time of the walk kernel of the last validate_jobs of this object."""
         return {"kernel_ms": getattr(self, "_valid_ms", 0.0)}
+
+    # -- the commit loop's checks behind a cycle (include/crane_gpu_commit/commit_check.h) -----------------------------------
+    def commit_check(self, events: "abi.CommitEvents | None", jobs: "abi.CommitJobs"):
+        """The resource-reduce and preempted-still-alive checks of the commit loop (JobScheduler.cpp:1464-1555) for every job of the last
+        cycle at once, on the cycle's results where they are on the device.  -> (code, counts): abi.COMMIT_* per job (the first failing
+        check in the reference's order) and the number of jobs per code [8].  A code other than COMMIT_OK is a `skip` of
+        apply_run_limits.  After a successful node_select / node_select_preempt / run_resident only."""
+        j = jobs.num_jobs
+        code, counts = np.zeros(max(j, 1), np.uint8), np.zeros(8, np.uint64)
+        ce = events.to_c() if events is not None else None
+        cj = jobs.to_c()
+        co = abi.CnsCommitOut(abi._ptr(code), abi._ptr(counts))
+        ms = C.c_double(0)
+        self._check(self._L.cns_commit_check(self._h, C.byref(ce) if ce is not None else None, C.byref(cj), C.byref(co), C.byref(ms)))
+        self._commit_ms = ms.value
+        return code[:j], counts
+
+    def commit_shape(self):
+        """(job_chunk, lane_max_nodes) of the check kernel: where its paths change."""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._L.cns_commit_shape(C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def commit_timing(self) -> dict:
+        """HIP-event time of the kernels of the last commit_check of this object."""
+        return {"kernel_ms": getattr(self, "_commit_ms", 0.0)}
 
     def device_results(self):
         p, n = C.c_void_p(), C.c_uint64()

@@ -20,6 +20,7 @@
 #include "../../include/crane_gpu_probe/probe.h"
 #include "../../include/crane_gpu_resv/resv_probe.h"
 #include "../../include/crane_gpu_valid/validity.h"
+#include "../../include/crane_gpu_commit/commit_check.h"
 
 namespace crane {
 
@@ -84,6 +85,11 @@ struct GpuNodeSelectionAlgo::Impl {
   bool resvq_stale = true;   // the engine's per-node tables of the reservation what-ifs are older than the packed running set / the snapshot
   std::vector<const PdJobInScheduler*> last_ord;                      // the jobs of the last cns_select, in its order
   std::unordered_map<const PdJobInScheduler*, uint64_t> last_index;  // job -> its index there (built when the run-limit pass asks)
+  // what CommitCheck needs of the last cycle beside `packed` (time limits, reservation indices): the preempted lists and the running ids
+  bool cc_have_pre = false;
+  std::vector<uint64_t> cc_pre_off;
+  std::vector<uint32_t> cc_pre;
+  std::vector<job_id_t> cc_run_id;
   // Incremental packing of the running jobs: an allocation never changes while its job runs, so its
   // dense form (node indices, core / GRES masks) is kept per job id across cycles; a cycle costs one lookup per
   // running job instead of one string lookup + set -> mask conversion per allocated node.  Entries of jobs that did
@@ -1189,6 +1195,7 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
   I.last_index.clear();
   I.last_ord.clear();
   I.cancelled.clear();
+  I.cc_have_pre = false;
   const auto tp1 = std::chrono::steady_clock::now();
   I.t_pack_ms = std::chrono::duration<double, std::milli>(tp1 - tp0).count();
   if (!I.preempt_enabled) {
@@ -1232,6 +1239,10 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
         else ord[j]->preempted_jobs.emplace_back(I.r_src[ref]);
       }
     I.cancelled.assign(po_cancel.begin(), po_cancel.begin() + po.num_cancelled);
+    I.cc_pre_off = po_off;
+    I.cc_pre.assign(po_refs.begin(), po_refs.begin() + po_off[J]);
+    I.cc_run_id.assign(rj_id.begin(), rj_id.begin() + R);
+    I.cc_have_pre = true;
     I.preempting.clear();
     for (uint32_t i = 0; i < po.num_preempting; ++i) I.preempting.insert(po_set[i]);
   }
@@ -1424,6 +1435,83 @@ bool GpuNodeSelectionAlgo::CheckJobValidity(const std::vector<const PdJobInSched
     a.crane_err = code[j] <= CNS_VALID_NOT_ENOUGH_NODES ? kErr[code[j]] : "ERR_INVALID_PARAM";
     a.refused = code[j] == CNS_VALID_REFUSED;
   }
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The commit loop's checks behind NodeSelect (include/crane_gpu_commit/commit_check.h)
+// ---------------------------------------------------------------------------------------------------------
+bool GpuNodeSelectionAlgo::CommitCheck(const std::vector<ResReduceEvent>& events, const std::function<const ResvMetaNow*(const std::string&)>& resv_now,
+                                       const std::unordered_set<job_id_t>& running_alive, const std::unordered_set<job_id_t>& pending_alive,
+                                       std::vector<uint8_t>* codes, double* kernel_ms) {
+  Impl& I = *impl_;
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (codes) codes->clear();
+  auto fail = [&](int st, const std::string& msg) { status_ = st; error_ = msg; return false; };
+  if (I.grp) return fail(CNS_ERR_UNSUPPORTED, "CommitCheck on an algorithm object over several devices");
+  if (!I.h) return fail(status_ ? status_ : CNS_ERR_NO_DEVICE, error_);
+  if (!I.have_snapshot || I.last.jobs != I.last_ord.size()) return fail(CNS_ERR_STATE, "CommitCheck before a NodeSelect that succeeded");
+  const size_t J = I.last_ord.size();
+  // ---- events -> dense indices (:1470-1486) ----
+  std::vector<int64_t> ev_time, ar_end;
+  std::vector<uint64_t> ev_off{0}, ar_off{0};
+  std::vector<uint32_t> ev_nodes, ar_resv, ar_nodes;
+  std::vector<uint8_t> ar_exists;
+  std::unordered_set<uint32_t> seen_resv;
+  for (const ResReduceEvent& e : events) {
+    if (const std::string* name = std::get_if<std::string>(&e.affected_resources)) {
+      auto it = I.resv_idx.find(*name);
+      if (it == I.resv_idx.end() || !seen_resv.insert(it->second).second) continue;   // (affected_resv_set is a set, :1467)
+      const ResvMetaNow* m = resv_now ? resv_now(*name) : nullptr;                     // :1522-1523
+      ar_resv.push_back(it->second);
+      ar_exists.push_back(m ? 1 : 0);
+      ar_end.push_back(m ? m->end_time : 0);
+      if (m) {
+        std::unordered_set<uint32_t> once;                                              // craned_ids is a set (:1530)
+        for (const CranedId& c : m->craned_ids) {
+          auto nit = I.node_idx.find(c);
+          if (nit != I.node_idx.end() && once.insert(nit->second).second) ar_nodes.push_back(nit->second);
+        }
+      }
+      ar_off.push_back(ar_nodes.size());
+    } else {
+      const auto& an = std::get<std::pair<TimeSec, std::vector<CranedId>>>(e.affected_resources);   // :1474-1477
+      ev_time.push_back(an.first);
+      for (const CranedId& c : an.second) {
+        auto nit = I.node_idx.find(c);
+        if (nit != I.node_idx.end()) ev_nodes.push_back(nit->second);
+      }
+      ev_off.push_back(ev_nodes.size());
+    }
+  }
+  cns_commit_events ce{};
+  ce.num_node_events = (uint32_t)ev_time.size(); ce.num_affected_resv = (uint32_t)ar_resv.size();
+  ce.ev_time_sec = ev_time.data(); ce.ev_offsets = ev_off.data(); ce.ev_nodes = ev_nodes.data();
+  ce.ar_resv = ar_resv.data(); ce.ar_exists = ar_exists.data(); ce.ar_end_sec = ar_end.data(); ce.ar_offsets = ar_off.data(); ce.ar_nodes = ar_nodes.data();
+  // ---- the queue of the last cycle ----
+  std::vector<uint8_t> gone(J + 1, 0), alive(I.cc_run_id.size() + 1, 0), code(J + 1, 0);
+  for (size_t j = 0; j < J; ++j) gone[j] = pending_alive.count(I.last_ord[j]->job_id) ? 0 : 1;            // :1493
+  for (size_t r = 0; r < I.cc_run_id.size(); ++r) alive[r] = running_alive.count(I.cc_run_id[r]) ? 1 : 0;  // :1546
+  cns_commit_jobs cj{};
+  cj.num_jobs = J;
+  cj.time_limit_sec = I.packed.L.data(); cj.reservation = I.packed.jresv.data(); cj.gone = gone.data();
+  if (I.cc_have_pre) {
+    cj.preempt_offsets = I.cc_pre_off.data(); cj.preempted = I.cc_pre.data();
+    cj.num_running = (uint32_t)I.cc_run_id.size(); cj.running_alive = alive.data();
+  }
+  uint64_t counts[8];
+  cns_commit_out co{code.data(), counts};
+  const int st = cns_commit_check(I.h, &ce, &cj, &co, kernel_ms);
+  if (st != 0) return fail(st, cns_last_error(I.h));
+  status_ = 0;
+  error_.clear();
+  static const char* const kReason[] = {"", "", "", "Resource changed", "Reservation deleted", "Resource", "Reservation changed", "Waiting for Preemption"};
+  static_assert(CNS_COMMIT_RESOURCE_CHANGED == 3 && CNS_COMMIT_RESV_DELETED == 4 && CNS_COMMIT_RESV_ENDS_EARLY == 5 && CNS_COMMIT_RESV_CHANGED == 6 &&
+                CNS_COMMIT_WAITING_PREEMPTION == 7, "kReason follows cns_commit_code");
+  for (size_t j = 0; j < J; ++j)
+    if (code[j] >= CNS_COMMIT_RESOURCE_CHANGED && code[j] <= CNS_COMMIT_WAITING_PREEMPTION)
+      const_cast<PdJobInScheduler*>(I.last_ord[j])->reason = kReason[code[j]];                             // :1518-1552
+  if (codes) codes->assign(code.begin(), code.begin() + J);
   return true;
 }
 

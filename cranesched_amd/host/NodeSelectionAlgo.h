@@ -18,6 +18,7 @@
 //   CranedId/SlotId -> std::string, as in the reference
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <list>
 #include <map>
 #include <memory>
@@ -404,6 +405,33 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
     bool refused{false};
   };
   bool CheckJobValidity(const std::vector<const PdJobInScheduler*>& jobs, std::vector<ValidityAnswer>* out, double* kernel_ms = nullptr);
+
+  // ---- the commit loop's checks behind NodeSelect (include/crane_gpu_commit/commit_check.h) ----------------------------------------
+  // The resource-reduce check (JobScheduler.cpp:1464-1540) and the preempted-still-alive check (:1542-1555) for every job of the last
+  // NodeSelect at once, in front of the loop at :1492.  Inputs in the reference's own shapes:
+  //   events         what g_meta_container->LockAndGetResReduceEvents() holds (:1468): per event a ResvId, or (time, craned ids);
+  //   resv_now       GetResvMetaPtr(name) NOW (:1523): nullptr = deleted, else its end_time and craned_ids;
+  //   running_alive  the ids of m_running_job_map_ NOW (:1546) — only the victims of the last cycle are looked up;
+  //   pending_alive  the ids still in m_pending_job_map_ (:1493).
+  // They are packed to dense indices with the tables of the last NodeSelect / SetClusterSnapshot: a craned name the snapshot does not know
+  // touches no placed job and is dropped; so is a reservation name the cycle did not know (its jobs carry "Reservation Not Found").  The
+  // preempted lists of the last cycle with preemption go along.  The reference's string is written into job->reason exactly where
+  // :1518-1552 does ("Resource changed", "Reservation deleted", "Resource", "Reservation changed", "Waiting for Preemption"); a job that
+  // is gone is reported and not written, a job the cycle left a reason keeps it.  CheckAndMallocMetaResource skips a job whose reason is
+  // not empty, so calling this first makes the batched admission exact.  `codes` (may be null): cns_commit_code per job, in the order of
+  // the last cycle (LastOrder()).  Licenses (:1557-1563) stay with the caller.  false on an engine error (no device, no cycle yet,
+  // several devices: CNS_ERR_UNSUPPORTED): nothing is written and Ok() / LastStatus() / LastError() say why; nothing is thrown.
+  struct ResvMetaNow {
+    TimeSec end_time{0};
+    std::vector<CranedId> craned_ids;
+  };
+  struct ResReduceEvent {   // CranedMetaContainer.h: ResReduceEvent::affected_resources
+    std::variant<std::string, std::pair<TimeSec, std::vector<CranedId>>> affected_resources;
+  };
+  static constexpr TimeSec kInfinitePast = INT64_MIN;   // absl::InfinitePast(): CranedDown / drain events
+  bool CommitCheck(const std::vector<ResReduceEvent>& events, const std::function<const ResvMetaNow*(const std::string&)>& resv_now,
+                   const std::unordered_set<job_id_t>& running_alive, const std::unordered_set<job_id_t>& pending_alive,
+                   std::vector<uint8_t>* codes = nullptr, double* kernel_ms = nullptr);
 
   // ---- event-fed mirror of the running allocations -------------------------------------------------
   // Instead of re-deriving the running jobs' allocations from the vector NodeSelect is handed every cycle, the adapter
