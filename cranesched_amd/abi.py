@@ -637,6 +637,49 @@ class CnsCommitOut(C.Structure):
     _fields_ = [("code", _P), ("counts", _P)]
 
 
+# ---- the submit limits over a batch of submissions (include/crane_gpu_submit/submit_limits.h) ----------------------------
+SUBMIT_JOB_MAX_TIME_LIMIT_SEC = 315576000000   # kJobMaxTimeLimitSec
+SUBMIT_CARRY = 1
+SUBMIT_MAX_JOBS = 1 << 24
+(SUBMIT_OK, SUBMIT_NOT_CANDIDATE, SUBMIT_BAD_COUNT, SUBMIT_BAD_REQUEST, SUBMIT_MAX_JOB_COUNT_PER_USER, SUBMIT_MAX_JOB_COUNT_PER_ACCOUNT,
+ SUBMIT_QOS_JOB_COUNT_EXCEEDED, SUBMIT_CPUS_PER_TASK_BEYOND, SUBMIT_TRES_PER_JOB_BEYOND, SUBMIT_TIME_LIMIT_BEYOND, SUBMIT_USER_ACCOUNT_MISMATCH,
+ SUBMIT_PARTITION_TRES_PER_JOB_BEYOND, SUBMIT_PARTITION_TIME_BEYOND, SUBMIT_PARTITION_MAX_SUBMIT_JOBS_PER_USER,
+ SUBMIT_PARTITION_MAX_SUBMIT_JOBS_PER_ACCOUNT, SUBMIT_MAX_TRES_PER_USER_BEYOND, SUBMIT_MAX_TRES_PER_ACCOUNT_BEYOND) = range(17)
+SUBMIT_STR = {SUBMIT_OK: "OK", SUBMIT_NOT_CANDIDATE: "NOT_CANDIDATE", SUBMIT_BAD_COUNT: "BAD_COUNT", SUBMIT_BAD_REQUEST: "BAD_REQUEST",
+              SUBMIT_MAX_JOB_COUNT_PER_USER: "MAX_JOB_COUNT_PER_USER", SUBMIT_MAX_JOB_COUNT_PER_ACCOUNT: "MAX_JOB_COUNT_PER_ACCOUNT",
+              SUBMIT_QOS_JOB_COUNT_EXCEEDED: "QOS_JOB_COUNT_EXCEEDED", SUBMIT_CPUS_PER_TASK_BEYOND: "CPUS_PER_TASK_BEYOND",
+              SUBMIT_TRES_PER_JOB_BEYOND: "TRES_PER_JOB_BEYOND", SUBMIT_TIME_LIMIT_BEYOND: "TIME_LIMIT_BEYOND",
+              SUBMIT_USER_ACCOUNT_MISMATCH: "USER_ACCOUNT_MISMATCH", SUBMIT_PARTITION_TRES_PER_JOB_BEYOND: "PARTITION_TRES_PER_JOB_BEYOND",
+              SUBMIT_PARTITION_TIME_BEYOND: "PARTITION_TIME_BEYOND",
+              SUBMIT_PARTITION_MAX_SUBMIT_JOBS_PER_USER: "PARTITION_MAX_SUBMIT_JOBS_PER_USER",
+              SUBMIT_PARTITION_MAX_SUBMIT_JOBS_PER_ACCOUNT: "PARTITION_MAX_SUBMIT_JOBS_PER_ACCOUNT",
+              SUBMIT_MAX_TRES_PER_USER_BEYOND: "MAX_TRES_PER_USER_BEYOND", SUBMIT_MAX_TRES_PER_ACCOUNT_BEYOND: "MAX_TRES_PER_ACCOUNT_BEYOND"}
+# the reference's CraneErrCode names (ERR_TIME_TIMIT_BEYOND is its spelling); "" for the three codes it has no name for
+SUBMIT_ERR_NAME = {c: ("SUCCESS" if c == SUBMIT_OK else "" if c < SUBMIT_MAX_JOB_COUNT_PER_USER else
+                       "ERR_TIME_TIMIT_BEYOND" if c == SUBMIT_TIME_LIMIT_BEYOND else "ERR_" + SUBMIT_STR[c]) for c in range(17)}
+
+
+class CnsSubmitTables(C.Structure):
+    _fields_ = [("num_users", C.c_uint32), ("num_user_accts", C.c_uint32), ("num_accounts", C.c_uint32), ("num_qos", C.c_uint32),
+                ("num_partitions", C.c_uint32), ("num_part_limits", C.c_uint32), ("gres", CnsGresLayout), ("qos", _P), ("acct_parent", _P),
+                ("part_limits", _P), ("user_part_limit", _P), ("acct_part_limit", _P), ("user_qos", _P), ("user_part", _P), ("acct_qos", _P),
+                ("acct_part", _P), ("qos_usage", _P), ("user_qos_submit", _P), ("user_part_submit", _P), ("acct_qos_submit", _P),
+                ("acct_part_submit", _P), ("qos_submit", _P), ("user_exists", _P), ("acct_exists", _P), ("qos_exists", _P)]
+
+
+class CnsSubmitKeys(C.Structure):
+    _fields_ = [("user", _P), ("user_acct", _P), ("account", _P), ("qos", _P), ("count", _P), ("skip", _P)]
+
+
+class CnsSubmitOut(C.Structure):
+    _fields_ = [("code", _P), ("time_limit_out", _P), ("num_admitted", _P)]
+
+
+class CnsSubmitTiming(C.Structure):
+    _fields_ = [("h2d_ms", C.c_double), ("prep_ms", C.c_double), ("admit_ms", C.c_double), ("d2h_ms", C.c_double),
+                ("candidates", C.c_uint64), ("admitted", C.c_uint64), ("rounds", C.c_uint32), ("ordered_fallback", C.c_uint32)]
+
+
 def _csr(lists):
     off = np.zeros(len(lists) + 1, np.uint64)
     off[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64) if len(lists) else []

@@ -25,6 +25,7 @@
 #include "../../include/crane_gpu_resv/resv_probe.h"
 #include "../../include/crane_gpu_valid/validity.h"
 #include "../../include/crane_gpu_commit/commit_check.h"
+#include "../../include/crane_gpu_submit/submit_limits.h"
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
 #include <limits>
@@ -38,6 +39,7 @@
 #include "resvq_kernels.inc"  // reservation what-ifs: which nodes, how soon (include/crane_gpu_resv/resv_probe.h)
 #include "valid_kernels.inc"  // can each job of a batch ever run in its partition (include/crane_gpu_valid/validity.h)
 #include "commit_kernels.inc" // the commit loop's resource-changed and preempted-alive checks (include/crane_gpu_commit/commit_check.h)
+#include "submit_kernels.inc" // the submit limits over a batch of submissions (include/crane_gpu_submit/submit_limits.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 #include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
 
@@ -217,6 +219,13 @@ struct cns_engine {
   u64 lim_NR = 0, lim_J = 0, lim_sel_J = 0;
   std::vector<u32> lim_level;
   cns_limit_timing lim_timing{};
+  // the submit limits over a batch of submissions (submit_host.inc): tables, the call's job arrays, items and results in buffers of their own
+  DevBuf d_sub[48];
+  bool sub_have = false, sub_has_upl = false, sub_has_apl = false, sub_has_uq = false, sub_has_aq = false, sub_has_g = false;
+  u32 sub_U = 0, sub_UA = 0, sub_A = 0, sub_Q = 0, sub_Pn = 0, sub_NR = 0, sub_NE = 0, sub_base[5] = {0, 0, 0, 0, 0}, sub_ent[3] = {0, 0, 0};
+  u32 sub_max_set = 0, sub_max_cur = 0;         // the largest submit count of the tables as set / as the last call left them
+  cns_gres_layout sub_lay{};
+  cns_submit_timing sub_timing{};
 };
 
 namespace {
@@ -701,6 +710,7 @@ void cns_destroy(cns_handle* h) {
   for (DevBuf& b : h->d_rq) b.release();
   for (DevBuf& b : h->d_vd) b.release();
   for (DevBuf& b : h->d_cc) b.release();
+  for (DevBuf& b : h->d_sub) b.release();
   h->d_gather.release();
   if (h->comm) (void)ncclCommDestroy((ncclComm_t)h->comm);
   for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
@@ -1694,6 +1704,7 @@ int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity
 #include "resvq_host.inc"
 #include "valid_host.inc"
 #include "commit_host.inc"
+#include "submit_host.inc"
 
 }  // extern "C"
 

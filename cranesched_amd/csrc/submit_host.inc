@@ -1,0 +1,301 @@
+// Host side of include/crane_gpu_submit/submit_limits.h.  Included by engine.hip inside extern "C".
+// Host work: validation of the tables (once, cns_set_submit_limits) and of the call's key indices (the pass that uploads), the input rule
+// on the 32-bit counts, the buffers, the launches.  Every check of a job against a limit or a counter runs on the device
+// (submit_kernels.inc).  Everything lives in cns_engine::d_sub: no buffer of a cycle, of the validity check or of the run limits is read or
+// written.  No CPU fallback.
+
+// cns_engine::d_sub
+enum { SB_QOS = 0, SB_PL, SB_PARENT, SB_UPL, SB_APL, SB_UQ, SB_AQ, SB_G, SB_ST_SET, SB_ST,                                    // tables
+       SB_JPART, SB_JTL, SB_JNCPU, SB_JNMEM, SB_JTCPU, SB_JTMEM, SB_JK, SB_JNT, SB_JGT, SB_JGS,                                // jobs
+       SB_KUSER, SB_KUA, SB_KACCT, SB_KQOS, SB_KCOUNT, SB_KSKIP,                                                                // keys
+       SB_PRE, SB_STATE, SB_STAT, SB_COND, SB_IKEY, SB_ITHR, SB_CODE, SB_TLO, SB_CTR,                                           // per job
+       SB_SK0, SB_SK1, SB_SV0, SB_SV1, SB_HIST, SB_SKEY, SB_SITEM, SB_SADD, SB_VAL, SB_TAILS, SB_HEADS, SB_CARRY, SB_COUNT };   // the parallel pass
+static_assert(SB_COUNT <= sizeof(cns_engine::d_sub) / sizeof(DevBuf), "cns_engine::d_sub holds every buffer of the submit check");
+
+int cns_set_submit_limits(cns_handle* h, const cns_submit_tables* t) {
+  if (!h || !t) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: null argument");
+  h->sub_have = false;
+  const u64 U = t->num_users, UA = t->num_user_accts, A = t->num_accounts, Q = t->num_qos, Pn = t->num_partitions, L = t->num_part_limits;
+  if ((Q && !t->qos) || (A && !t->acct_parent) || (L && !t->part_limits)) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: missing table");
+  if (t->gres.num_classes > CNS_MAX_GRES_CLASSES) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: gres.num_classes > 8");
+  for (u32 g = 0; g < t->gres.num_classes; ++g)
+    if (t->gres.class_name[g] >= CNS_MAX_GRES_NAMES) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: gres class name id >= 4");
+  const u64 n_uq = U * Q, n_up = UA * Pn, n_aq = A * Q, n_ap = A * Pn;
+  const u64 NR = n_uq + n_up + n_aq + n_ap + Q, NE = U + A + Q;
+  if (n_uq > 0xFFFFFFF0ull || n_up > 0xFFFFFFF0ull || n_aq > 0xFFFFFFF0ull || n_ap > 0xFFFFFFF0ull || NR + NE >= 0xFFFFFFF0ull)
+    return fail(h, CNS_ERR_UNSUPPORTED, "cns_set_submit_limits: more than 2^32 - 16 records");
+  for (u64 a = 0; a < A; ++a) {
+    const u32 p = t->acct_parent[a];
+    if (p != CNS_LIM_NONE && p >= A) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: acct_parent out of range");
+  }
+  for (u64 a = 0; a < A; ++a) {
+    u64 depth = 0;
+    for (u32 x = (u32)a; x != CNS_LIM_NONE && depth <= A; x = t->acct_parent[x]) ++depth;
+    if (depth > A) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: the chain of account " + std::to_string(a) + " does not end");
+    if (depth > CNS_LIM_MAX_CHAIN) return fail(h, CNS_ERR_UNSUPPORTED, "cns_set_submit_limits: account " + std::to_string(a) + ": a chain of more than 6 accounts");
+  }
+  for (int w = 0; w < 2; ++w) {
+    const u32* m = w ? t->acct_part_limit : t->user_part_limit;
+    const u64 n = w ? n_ap : n_up;
+    if (m)
+      for (u64 i = 0; i < n; ++i)
+        if (m[i] != CNS_LIM_NONE && m[i] >= L) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: partition limit index out of range");
+  }
+  {
+    const cns_usage* tabs[5] = {t->user_qos, t->user_part, t->acct_qos, t->acct_part, t->qos_usage};
+    const u64 lens[5] = {n_uq, n_up, n_aq, n_ap, Q};
+    for (int w = 0; w < 5; ++w)
+      if (tabs[w])
+        for (u64 i = 0; i < lens[w]; ++i)
+          if (tabs[w][i].jobs_count == 0xFFFFFFFFu) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: a jobs_count of UINT32_MAX");
+  }
+  // the table: five count tables back to back, then one exists value per user, account, QoS
+  std::vector<u32> st((size_t)(NR + NE), 0u);
+  u32 mx = 0;
+  {
+    const u32* cnt[5] = {t->user_qos_submit, t->user_part_submit, t->acct_qos_submit, t->acct_part_submit, t->qos_submit};
+    const u64 lens[5] = {n_uq, n_up, n_aq, n_ap, Q};
+    u64 off = 0;
+    for (int w = 0; w < 5; ++w) {
+      h->sub_base[w] = (u32)off;
+      if (cnt[w])
+        for (u64 i = 0; i < lens[w]; ++i) { st[(size_t)(off + i)] = cnt[w][i]; mx = std::max(mx, cnt[w][i]); }
+      off += lens[w];
+    }
+    const uint8_t* ex[3] = {t->user_exists, t->acct_exists, t->qos_exists};
+    const u64 elen[3] = {U, A, Q};
+    for (int w = 0; w < 3; ++w) {
+      h->sub_ent[w] = (u32)off;
+      if (ex[w])
+        for (u64 i = 0; i < elen[w]; ++i) st[(size_t)(off + i)] = ex[w][i] ? 1u : 0u;
+      off += elen[w];
+    }
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  DevBuf* B = h->d_sub;
+  auto up = [&](int b, const void* src, size_t bytes) -> int {
+    HIPCHK(h, B[b].ensure(bytes));
+    if (bytes && src) HIPCHK(h, hipMemcpyAsync(B[b].p, src, bytes, hipMemcpyHostToDevice, h->stream));
+    return 0;
+  };
+  int rc = 0;
+  if ((rc = up(SB_QOS, t->qos, (size_t)Q * sizeof(cns_submit_qos))) || (rc = up(SB_PL, t->part_limits, (size_t)L * sizeof(cns_submit_part_limit))) ||
+      (rc = up(SB_PARENT, t->acct_parent, (size_t)A * 4)) || (rc = up(SB_UPL, t->user_part_limit, (size_t)n_up * 4)) ||
+      (rc = up(SB_APL, t->acct_part_limit, (size_t)n_ap * 4)) || (rc = up(SB_UQ, t->user_qos, (size_t)n_uq * sizeof(cns_usage))) ||
+      (rc = up(SB_AQ, t->acct_qos, (size_t)n_aq * sizeof(cns_usage))) || (rc = up(SB_G, t->qos_usage, (size_t)Q * sizeof(cns_usage))) ||
+      (rc = up(SB_ST_SET, st.data(), st.size() * 4)) || (rc = up(SB_ST, st.data(), st.size() * 4))) {
+    resvq_drain(h);
+    return rc;
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->sub_U = (u32)U; h->sub_UA = (u32)UA; h->sub_A = (u32)A; h->sub_Q = (u32)Q; h->sub_Pn = (u32)Pn;
+  h->sub_NR = (u32)NR; h->sub_NE = (u32)NE;
+  h->sub_has_upl = t->user_part_limit != nullptr; h->sub_has_apl = t->acct_part_limit != nullptr;
+  h->sub_has_uq = t->user_qos != nullptr; h->sub_has_aq = t->acct_qos != nullptr; h->sub_has_g = t->qos_usage != nullptr;
+  h->sub_lay = t->gres;
+  h->sub_max_set = h->sub_max_cur = mx;
+  h->sub_timing = cns_submit_timing{};
+  h->sub_have = true;
+  return CNS_OK;
+}
+
+static int submit_impl(cns_handle* h, const cns_job_soa* jb, const cns_submit_keys* ky, u32 flags, const cns_submit_out* out) {
+  const u32 J = (u32)jb->num_jobs;
+  if (!jb->partition || !jb->time_limit_sec || !jb->node_mem || !jb->task_cpu_raw || !jb->task_mem || !jb->node_num || !jb->ntasks)
+    return fail(h, CNS_ERR_INVALID_ARG, "cns_check_submissions: missing job array");
+  if (!ky->user || !ky->user_acct || !ky->account || !ky->qos || !ky->count) return fail(h, CNS_ERR_INVALID_ARG, "cns_check_submissions: missing key array");
+  if (!out->code || !out->time_limit_out) return fail(h, CNS_ERR_INVALID_ARG, "cns_check_submissions: missing result array");
+  const bool carry = (flags & CNS_SUBMIT_CARRY) != 0;
+  // ---- the validating pass: indices of the jobs that are not skipped, and the input rule on the 32-bit counts ----
+  u64 total = 0;
+  for (u32 j = 0; j < J; ++j) {
+    if (ky->skip && ky->skip[j]) continue;
+    if (ky->user[j] >= h->sub_U || ky->account[j] >= h->sub_A || ky->qos[j] >= h->sub_Q || jb->partition[j] >= h->sub_Pn ||
+        (ky->user_acct[j] != CNS_LIM_NONE && ky->user_acct[j] >= h->sub_UA))
+      return fail(h, CNS_ERR_INVALID_ARG, "cns_check_submissions: job " + std::to_string(j) + ": a key index out of range");
+    total += ky->count[j];
+  }
+  if ((u64)(carry ? h->sub_max_cur : h->sub_max_set) + total > 0xFFFFFFFFull)
+    return fail(h, CNS_ERR_UNSUPPORTED, "cns_check_submissions: the largest submit count + the sum of count over the call exceeds UINT32_MAX");
+
+  HIPCHK(h, hipSetDevice(h->device));
+  DevBuf* B = h->d_sub;
+  auto up = [&](int b, const void* src, size_t bytes) -> int {
+    HIPCHK(h, B[b].ensure(bytes));
+    if (bytes && src) HIPCHK(h, hipMemcpyAsync(B[b].p, src, bytes, hipMemcpyHostToDevice, h->stream));
+    return 0;
+  };
+  HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+  {
+    const struct { int b; const void* p; size_t sz; } ups[] = {
+        {SB_JPART, jb->partition, 4}, {SB_JTL, jb->time_limit_sec, 8}, {SB_JNCPU, jb->node_cpu_raw, 8}, {SB_JNMEM, jb->node_mem, 8},
+        {SB_JTCPU, jb->task_cpu_raw, 8}, {SB_JTMEM, jb->task_mem, 8}, {SB_JK, jb->node_num, 4}, {SB_JNT, jb->ntasks, 4},
+        {SB_JGT, jb->gres_total, CNS_MAX_GRES_NAMES}, {SB_JGS, jb->gres_spec, CNS_MAX_GRES_CLASSES}, {SB_KUSER, ky->user, 4}, {SB_KUA, ky->user_acct, 4},
+        {SB_KACCT, ky->account, 4}, {SB_KQOS, ky->qos, 4}, {SB_KCOUNT, ky->count, 4}, {SB_KSKIP, ky->skip, 1}};
+    for (const auto& u : ups)
+      if (int rc = up(u.b, u.p, (size_t)J * u.sz)) return rc;
+  }
+  const u32 NK = h->sub_NR + h->sub_NE;
+  const size_t n = (size_t)J * kSubItems;
+  HIPCHK(h, B[SB_PRE].ensure(J)); HIPCHK(h, B[SB_STATE].ensure(J)); HIPCHK(h, B[SB_STAT].ensure((size_t)J * 8)); HIPCHK(h, B[SB_COND].ensure((size_t)J * 8));
+  HIPCHK(h, B[SB_IKEY].ensure(n * 4)); HIPCHK(h, B[SB_ITHR].ensure(n * 4)); HIPCHK(h, B[SB_CODE].ensure(J)); HIPCHK(h, B[SB_TLO].ensure((size_t)J * 8));
+  HIPCHK(h, B[SB_CTR].ensure(64));
+  HIPCHK(h, hipMemsetAsync(B[SB_CTR].p, 0, 64, h->stream));
+  if (!carry) HIPCHK(h, hipMemcpyAsync(B[SB_ST].p, B[SB_ST_SET].p, (size_t)NK * 4, hipMemcpyDeviceToDevice, h->stream));
+  const char* mode_env = getenv("CNS_SUBMIT_MODE");   // "seq": force the ordered single-wave kernel (tests cover both)
+  const bool par = !(mode_env && std::string(mode_env) == "seq");
+  if (par) HIPCHK(h, B[SB_SK0].ensure(n * 8));
+
+  SubParams P;
+  memset(&P, 0, sizeof P);
+  P.J = J; P.Q = h->sub_Q; P.Pn = h->sub_Pn; P.NK = NK;
+  P.base_uq = h->sub_base[0]; P.base_up = h->sub_base[1]; P.base_aq = h->sub_base[2]; P.base_ap = h->sub_base[3]; P.base_g = h->sub_base[4];
+  P.ent_user = h->sub_ent[0]; P.ent_acct = h->sub_ent[1]; P.ent_qos = h->sub_ent[2];
+  P.part = B[SB_JPART].as<u32>(); P.tl = B[SB_JTL].as<i64>(); P.ncpu = jb->node_cpu_raw ? B[SB_JNCPU].as<i64>() : nullptr; P.nmem = B[SB_JNMEM].as<u64>();
+  P.tcpu = B[SB_JTCPU].as<i64>(); P.tmem = B[SB_JTMEM].as<u64>(); P.k = B[SB_JK].as<u32>(); P.nt = B[SB_JNT].as<u32>();
+  P.gt = jb->gres_total ? B[SB_JGT].as<u32>() : nullptr; P.gs = jb->gres_spec ? B[SB_JGS].as<u64>() : nullptr;
+  P.user = B[SB_KUSER].as<u32>(); P.ua = B[SB_KUA].as<u32>(); P.account = B[SB_KACCT].as<u32>(); P.qos = B[SB_KQOS].as<u32>();
+  P.count = B[SB_KCOUNT].as<u32>(); P.skip = ky->skip ? B[SB_KSKIP].as<uint8_t>() : nullptr;
+  P.q = B[SB_QOS].as<cns_submit_qos>(); P.pl = B[SB_PL].as<cns_submit_part_limit>(); P.acct_parent = B[SB_PARENT].as<u32>();
+  P.upl = h->sub_has_upl ? B[SB_UPL].as<u32>() : nullptr; P.apl = h->sub_has_apl ? B[SB_APL].as<u32>() : nullptr;
+  P.uq_use = h->sub_has_uq ? B[SB_UQ].as<cns_usage>() : nullptr; P.aq_use = h->sub_has_aq ? B[SB_AQ].as<cns_usage>() : nullptr;
+  P.g_use = h->sub_has_g ? B[SB_G].as<cns_usage>() : nullptr;
+  P.lay = h->sub_lay;
+  P.st = B[SB_ST].as<u32>();
+  P.pre = B[SB_PRE].as<uint8_t>(); P.state = B[SB_STATE].as<uint8_t>(); P.stat = B[SB_STAT].as<u64>(); P.cond = B[SB_COND].as<u64>();
+  P.item_key = B[SB_IKEY].as<u32>(); P.item_thr = B[SB_ITHR].as<u32>(); P.sort_key = par ? B[SB_SK0].as<u64>() : nullptr;
+  P.code = B[SB_CODE].as<uint8_t>(); P.tlo = B[SB_TLO].as<i64>(); P.ctr = B[SB_CTR].as<u64>();
+
+  const dim3 jg((J + kSubChunk - 1) / kSubChunk);
+  HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+  hipLaunchKernelGGL(k_sub_prep, jg, dim3(256), 0, h->stream, P);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+
+  u32 rounds = 0;
+  bool decided = false;
+  if (par) {
+    const u32 n32 = (u32)n, ntiles = (n32 + kSortTile - 1) / kSortTile;
+    HIPCHK(h, B[SB_SK1].ensure(n * 8)); HIPCHK(h, B[SB_SV0].ensure(n * 4)); HIPCHK(h, B[SB_SV1].ensure(n * 4));
+    HIPCHK(h, B[SB_HIST].ensure(((size_t)256 * ntiles + 256) * 4));
+    HIPCHK(h, B[SB_SKEY].ensure(n * 4)); HIPCHK(h, B[SB_SITEM].ensure(n * 4)); HIPCHK(h, B[SB_SADD].ensure(n * 4)); HIPCHK(h, B[SB_VAL].ensure(n * 8));
+    // (job, position) items sorted by table index, stable: inside a record the jobs stay in arrival order
+    hipLaunchKernelGGL(k_iota, dim3((n32 + 255) / 256), dim3(256), 0, h->stream, B[SB_SV0].as<u32>(), n32);
+    u64* kin = B[SB_SK0].as<u64>(); u64* kout = B[SB_SK1].as<u64>();
+    u32* vin = B[SB_SV0].as<u32>(); u32* vout = B[SB_SV1].as<u32>();
+    u32* hist = B[SB_HIST].as<u32>();
+    u32* rowtot = hist + (size_t)256 * ntiles;
+    u32 bits = 0;
+    while (((u64)NK >> bits) != 0) ++bits;
+    for (u32 pass = 0; pass * 8 < bits; ++pass) {
+      hipLaunchKernelGGL(k_sort_hist, dim3(ntiles), dim3(256), 0, h->stream, (const u64*)kin, n32, pass * 8, hist, ntiles);
+      hipLaunchKernelGGL(k_sort_rowscan, dim3(256), dim3(256), 0, h->stream, hist, ntiles, rowtot);
+      hipLaunchKernelGGL(k_sort_scatter, dim3(ntiles), dim3(256), 0, h->stream, (const u64*)kin, (const u32*)vin, kout, vout, n32, pass * 8, (const u32*)hist, ntiles,
+                         (const u32*)rowtot);
+      std::swap(kin, kout);
+      std::swap(vin, vout);
+    }
+    hipLaunchKernelGGL(k_sub_gather, dim3((n32 + 255) / 256), dim3(256), 0, h->stream, (const u64*)kin, (const u32*)vin, n32, NK, P.count, B[SB_SKEY].as<u32>(),
+                       B[SB_SITEM].as<u32>(), B[SB_SADD].as<u32>(), P.ctr);
+    HIPCHK(h, hipGetLastError());
+    u64 ctr[4] = {0, 0, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(ctr, P.ctr, 32, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // the number of items that carry a key sizes the rounds' grids
+    SubPar R;
+    memset(&R, 0, sizeof R);
+    R.n = (u32)ctr[2]; R.nchunks = (R.n + kSubItemChunk - 1) / kSubItemChunk; R.J = J; R.NK = NK;
+    R.s_key = B[SB_SKEY].as<u32>(); R.s_item = B[SB_SITEM].as<u32>(); R.s_add = B[SB_SADD].as<u32>(); R.state = P.state; R.st = P.st;
+    HIPCHK(h, B[SB_TAILS].ensure((size_t)R.nchunks * 8)); HIPCHK(h, B[SB_HEADS].ensure(R.nchunks)); HIPCHK(h, B[SB_CARRY].ensure((size_t)R.nchunks * 8));
+    R.tails = B[SB_TAILS].as<uint2>(); R.heads = B[SB_HEADS].as<uint8_t>(); R.carry = B[SB_CARRY].as<uint2>(); R.val = B[SB_VAL].as<uint2>();
+    u64 und = R.n ? 1 : 0;   // without items nothing depends on the batch: the final pass decides from the static codes
+    while (und && rounds < kSubMaxRounds) {
+      ++rounds;
+      HIPCHK(h, hipMemsetAsync(P.ctr + 3, 0, 8, h->stream));
+      hipLaunchKernelGGL(k_sub_tails, dim3(R.nchunks), dim3(256), 0, h->stream, R);
+      hipLaunchKernelGGL(k_sub_carry, dim3(1), dim3(1024), 0, h->stream, R);
+      hipLaunchKernelGGL(k_sub_eval<false>, dim3(R.nchunks), dim3(256), 0, h->stream, R);
+      hipLaunchKernelGGL(k_sub_decide, jg, dim3(256), 0, h->stream, P, (const uint2*)R.val);
+      HIPCHK(h, hipGetLastError());
+      HIPCHK(h, hipMemcpyAsync(&und, P.ctr + 3, 8, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    if (und == 0) {   // every job decided: exact values -> codes, and the table after the batch
+      if (R.n) {
+        hipLaunchKernelGGL(k_sub_tails, dim3(R.nchunks), dim3(256), 0, h->stream, R);
+        hipLaunchKernelGGL(k_sub_carry, dim3(1), dim3(1024), 0, h->stream, R);
+        hipLaunchKernelGGL(k_sub_eval<true>, dim3(R.nchunks), dim3(256), 0, h->stream, R);
+      }
+      hipLaunchKernelGGL(k_sub_final, jg, dim3(256), 0, h->stream, P, (const uint2*)R.val);
+      decided = true;
+    }
+  }
+  if (!decided) hipLaunchKernelGGL(k_sub_admit, dim3(1), dim3(64), 0, h->stream, P);   // CNS_SUBMIT_MODE=seq, or a chain the rounds did not finish
+  if (h->sub_NR) hipLaunchKernelGGL(k_sub_max, dim3((h->sub_NR + 255) / 256), dim3(256), 0, h->stream, (const u32*)P.st, h->sub_NR, P.ctr);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float a = 0, b = 0, c = 0, d = 0;
+  HIPCHK(h, hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+  HIPCHK(h, hipEventElapsedTime(&b, h->ev[1], h->ev[2]));
+  HIPCHK(h, hipEventElapsedTime(&c, h->ev[2], h->ev[3]));
+  u64 ctr[5] = {0, 0, 0, 0, 0};
+  HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+  HIPCHK(h, hipMemcpyAsync(out->code, P.code, J, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(out->time_limit_out, P.tlo, (size_t)J * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(ctr, P.ctr, 40, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipEventElapsedTime(&d, h->ev[0], h->ev[1]));
+  if (out->num_admitted) *out->num_admitted = ctr[1];
+  h->sub_max_cur = (u32)ctr[4];
+  h->sub_timing.h2d_ms = a; h->sub_timing.prep_ms = b; h->sub_timing.admit_ms = c; h->sub_timing.d2h_ms = d;
+  h->sub_timing.candidates = ctr[0]; h->sub_timing.admitted = ctr[1];
+  h->sub_timing.rounds = rounds; h->sub_timing.ordered_fallback = decided ? 0 : 1;
+  return CNS_OK;
+}
+
+int cns_check_submissions(cns_handle* h, const cns_job_soa* jobs, const cns_submit_keys* keys, uint32_t flags, const cns_submit_out* out) {
+  if (!h || !jobs || !keys) return fail(h, CNS_ERR_INVALID_ARG, "cns_check_submissions: null argument");
+  if (!h->sub_have) return fail(h, CNS_ERR_STATE, "cns_check_submissions before cns_set_submit_limits");
+  if (jobs->num_jobs == 0) return CNS_OK;   // nothing asked, nothing written
+  if (jobs->num_jobs > CNS_SUBMIT_MAX_JOBS) return fail(h, CNS_ERR_UNSUPPORTED, "cns_check_submissions: more than 2^24 jobs in one call");
+  if (!out) return fail(h, CNS_ERR_INVALID_ARG, "cns_check_submissions: null result");
+  const int rc = submit_impl(h, jobs, keys, flags, out);
+  if (rc != 0) resvq_drain(h);   // nothing of the call is left in flight, the message survives
+  return rc;
+}
+
+int cns_get_submit_usage(cns_handle* h, uint32_t* user_qos_submit, uint32_t* user_part_submit, uint32_t* acct_qos_submit, uint32_t* acct_part_submit,
+                         uint32_t* qos_submit, uint8_t* user_exists, uint8_t* acct_exists, uint8_t* qos_exists) {
+  if (!h) return fail(h, CNS_ERR_INVALID_ARG, "cns_get_submit_usage: null handle");
+  if (!h->sub_have) return fail(h, CNS_ERR_STATE, "cns_get_submit_usage before cns_set_submit_limits");
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<u32> st((size_t)h->sub_NR + h->sub_NE);
+  if (!st.empty()) HIPCHK(h, hipMemcpyAsync(st.data(), h->d_sub[SB_ST].p, st.size() * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  uint32_t* cnt[5] = {user_qos_submit, user_part_submit, acct_qos_submit, acct_part_submit, qos_submit};
+  for (int w = 0; w < 5; ++w) {
+    const size_t beg = h->sub_base[w], end = w < 4 ? h->sub_base[w + 1] : h->sub_NR;
+    if (cnt[w] && end > beg) memcpy(cnt[w], st.data() + beg, (end - beg) * 4);
+  }
+  uint8_t* ex[3] = {user_exists, acct_exists, qos_exists};
+  for (int w = 0; w < 3; ++w) {
+    const size_t beg = h->sub_ent[w], end = w < 2 ? h->sub_ent[w + 1] : st.size();
+    if (ex[w])
+      for (size_t i = beg; i < end; ++i) ex[w][i - beg] = st[i] ? 1 : 0;
+  }
+  return CNS_OK;
+}
+
+int cns_get_submit_timing(const cns_handle* h, cns_submit_timing* t) {
+  if (!h || !t) return CNS_ERR_INVALID_ARG;
+  *t = h->sub_timing;
+  return CNS_OK;
+}
+
+int cns_submit_shape(uint32_t* job_chunk, uint32_t* item_chunk, uint32_t* max_rounds) {
+  if (job_chunk) *job_chunk = kSubChunk;
+  if (item_chunk) *item_chunk = kSubItemChunk;
+  if (max_rounds) *max_rounds = kSubMaxRounds;
+  return CNS_OK;
+}

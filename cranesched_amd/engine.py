@@ -49,6 +49,8 @@ RESVQ_ABI_SYMBOLS = ("cns_resvq_set_state", "cns_resvq_run")
 VALID_ABI_SYMBOLS = ("cns_validate_jobs", "cns_validate_shape")
 # ... and include/crane_gpu_commit/commit_check.h
 COMMIT_ABI_SYMBOLS = ("cns_commit_check", "cns_commit_shape")
+# ... and include/crane_gpu_submit/submit_limits.h
+SUBMIT_ABI_SYMBOLS = ("cns_set_submit_limits", "cns_check_submissions", "cns_get_submit_usage", "cns_get_submit_timing", "cns_submit_shape")
 LIMITS_ABI_SYMBOLS = ("cns_set_run_limits", "cns_apply_run_limits", "cns_upload_limit_jobs", "cns_run_limits_resident",
                       "cns_download_limits", "cns_get_limit_timing", "cns_get_usage")
 
@@ -439,6 +441,45 @@ class GpuNodeSelector:
     def commit_timing(self) -> dict:
         """HIP-event time of the kernels of the last commit_check of this object."""
         return {"kernel_ms": getattr(self, "_commit_ms", 0.0)}
+
+    # -- the submit limits over a batch of submissions (include/crane_gpu_submit/submit_limits.h) -----------------------------
+    def set_submit_limits(self, tables):
+        """Submit-side limits, the usage the DenyOnLimit checks read, the submit counts and the exists bits before the batch
+        (submit.SubmitTables).  Needs no node snapshot."""
+        t = tables.to_c()
+        self._check(self._L.cns_set_submit_limits(self._h, C.byref(t)))
+        self._sub_tables = tables
+
+    def check_submissions(self, jobs: "abi.Jobs", keys, carry: bool = False):
+        """TryMallocMetaSubmitResource + MallocMetaSubmitResource (AccountMetaContainer.cpp:75-153) for every job of the batch in the order
+        given; job i sees the counters as jobs 0..i-1 left them.  -> (code, time_limit_out, num_admitted): abi.SUBMIT_* per job (the first
+        failing check in the reference's order), the time limit after the QoS's rewrite, the number of jobs admitted.  carry: start from
+        what the previous call left instead of the tables as set."""
+        j = jobs.num_jobs
+        if keys.num_jobs != j:
+            raise ValueError("keys and jobs differ in length")
+        code, tlo, adm = np.zeros(max(j, 1), np.uint8), np.zeros(max(j, 1), np.int64), np.zeros(1, np.uint64)
+        cj, ck = jobs.to_c(), keys.to_c()
+        co = abi.CnsSubmitOut(abi._ptr(code), abi._ptr(tlo), abi._ptr(adm))
+        self._check(self._L.cns_check_submissions(self._h, C.byref(cj), C.byref(ck), C.c_uint32(abi.SUBMIT_CARRY if carry else 0), C.byref(co)))
+        return code[:j], tlo[:j], int(adm[0])
+
+    def submit_usage(self):
+        """submit.SubmitState after the last check_submissions: the five submit-count tables and the three exists arrays."""
+        s = self._sub_tables.state()
+        self._check(self._L.cns_get_submit_usage(self._h, *s.pointers()))
+        return s
+
+    def submit_timing(self) -> dict:
+        t = abi.CnsSubmitTiming()
+        self._check(self._L.cns_get_submit_timing(self._h, C.byref(t)))
+        return {f: getattr(t, f) for f, _ in abi.CnsSubmitTiming._fields_}
+
+    def submit_shape(self):
+        """(job_chunk, item_chunk, max_rounds): where the submit kernels' paths change."""
+        a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._check(self._L.cns_submit_shape(C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def device_results(self):
         p, n = C.c_void_p(), C.c_uint64()

@@ -21,6 +21,7 @@
 #include "../../include/crane_gpu_resv/resv_probe.h"
 #include "../../include/crane_gpu_valid/validity.h"
 #include "../../include/crane_gpu_commit/commit_check.h"
+#include "../../include/crane_gpu_submit/submit_limits.h"
 
 namespace crane {
 
@@ -1641,7 +1642,7 @@ const char* kLimitReasonStr[] = {"", "QosEntryNotFound", "QosCpuResourceLimit", 
 }  // namespace
 
 Qos::Qos() : max_tres(UnlimitedTres()), max_tres_per_user(UnlimitedTres()), max_tres_per_account(UnlimitedTres()) {}
-PartitionResourceLimit::PartitionResourceLimit() : max_tres(UnlimitedTres()) {}
+PartitionResourceLimit::PartitionResourceLimit() : max_tres(UnlimitedTres()), max_tres_per_job(UnlimitedTres()) {}
 
 void GpuNodeSelectionAlgo::CheckAndMallocMetaResource(AccountMetaSnapshot& meta,
                                                       const std::vector<std::unique_ptr<PdJobInScheduler>>& pending_jobs,
@@ -1880,6 +1881,243 @@ void GpuNodeSelectionAlgo::CheckAndMallocMetaResource(AccountMetaSnapshot& meta,
   error_.clear();
 }
 
+
+// ---------------------------------------------------------------------------------------------------------
+// The submit limits over a batch of submissions (include/crane_gpu_submit/submit_limits.h)
+// ---------------------------------------------------------------------------------------------------------
+bool GpuNodeSelectionAlgo::CheckSubmitLimits(const std::vector<SubmitRequest>& requests, AccountMetaSnapshot* meta_ptr, std::vector<SubmitAnswer>* out,
+                                             cns_submit_timing* timing) {
+  Impl& I = *impl_;
+  if (out) out->clear();
+  auto fail = [&](int st, const std::string& msg) { status_ = st; error_ = msg; return false; };
+  if (!out || !meta_ptr) return fail(CNS_ERR_INVALID_ARG, "CheckSubmitLimits: null argument");
+  if (I.grp) return fail(CNS_ERR_UNSUPPORTED, "CheckSubmitLimits on an algorithm object over several devices");
+  if (!I.h) return fail(status_ ? status_ : CNS_ERR_NO_DEVICE, error_);
+  if (!I.have_snapshot) return fail(CNS_ERR_STATE, "CheckSubmitLimits before SetClusterSnapshot");
+  AccountMetaSnapshot& meta = *meta_ptr;
+  const size_t J = requests.size();
+  if (J == 0) { status_ = 0; error_.clear(); return true; }
+
+  // ---- dense indices (sorted names: deterministic), as CheckAndMallocMetaResource ----
+  auto index_of = [](const auto& m) {
+    std::map<std::string, uint32_t> ix;
+    for (const auto& kv : m) ix.emplace(kv.first, 0);
+    uint32_t n = 0;
+    for (auto& kv : ix) kv.second = n++;
+    return ix;
+  };
+  const std::map<std::string, uint32_t> qos_ix = index_of(meta.qos), acct_ix = index_of(meta.account_parent), user_ix = index_of(meta.user_accounts);
+  std::map<std::pair<std::string, std::string>, uint32_t> ua_ix;
+  for (const auto& [u, accts] : meta.user_accounts)
+    for (const auto& [a, lims] : accts) ua_ix.emplace(std::make_pair(u, a), 0);
+  { uint32_t n = 0; for (auto& kv : ua_ix) kv.second = n++; }
+  const uint32_t Q = (uint32_t)qos_ix.size(), A = (uint32_t)acct_ix.size(), U = (uint32_t)user_ix.size(), UA = (uint32_t)ua_ix.size();
+  const uint32_t Pn = (uint32_t)I.part_idx.size();
+  std::vector<std::string> part_name(Pn);
+  for (const auto& [name, ix] : I.part_idx) part_name[ix] = name;
+
+  auto to_tres = [&](const ResourceView& v) {
+    cns_tres t{};
+    t.cpu_raw = v.cpu_count.raw;
+    t.mem = v.memory_bytes;
+    for (const auto& [name, gc] : v.gres_map) {
+      auto nit = I.name_id.find(name);
+      if (nit == I.name_id.end()) continue;
+      t.name_mask |= 1u << nit->second;
+      t.name_total[nit->second] = gc.total;
+      for (const auto& [type, cnt] : gc.specified) {
+        const int c = I.class_of(name, type);
+        if (c < 0) continue;
+        t.class_mask |= 1u << c;
+        t.class_count[c] = cnt;
+      }
+    }
+    return t;
+  };
+  auto to_usage = [&](const MetaResource& m) {
+    cns_usage u{};
+    u.cpu_raw = m.resource.cpu_count.raw;
+    u.mem = m.resource.memory_bytes;
+    u.wall_sec = m.wall_time;
+    u.jobs_count = m.jobs_count;
+    for (const auto& [name, gc] : m.resource.gres_map) {
+      auto nit = I.name_id.find(name);
+      if (nit == I.name_id.end()) continue;
+      u.name_total[nit->second] = gc.total;
+      for (const auto& [type, cnt] : gc.specified) {
+        const int c = I.class_of(name, type);
+        if (c >= 0) u.class_count[c] = cnt;
+      }
+    }
+    return u;
+  };
+
+  // ---- limits ----
+  std::vector<cns_submit_qos> qos(Q);
+  for (const auto& [name, ix] : qos_ix) {
+    const Qos& s = meta.qos.at(name);
+    cns_submit_qos& d = qos[ix];
+    d.max_submit_jobs_per_user = s.max_submit_jobs_per_user; d.max_submit_jobs_per_account = s.max_submit_jobs_per_account; d.max_submit_jobs = s.max_submit_jobs;
+    d.max_jobs_per_user = s.max_jobs_per_user; d.max_jobs_per_account = s.max_jobs_per_account; d.max_jobs = s.max_jobs;
+    d.deny_on_limit = s.deny_on_limit ? 1u : 0u;
+    d.max_cpus_per_user_raw = s.max_cpus_per_user.raw; d.max_wall_sec = s.max_wall; d.max_time_limit_per_job_sec = s.max_time_limit_per_job;
+    d.max_tres = to_tres(s.max_tres); d.max_tres_per_user = to_tres(s.max_tres_per_user); d.max_tres_per_account = to_tres(s.max_tres_per_account);
+  }
+  std::vector<uint32_t> parent(A, CNS_LIM_NONE);
+  for (const auto& [name, ix] : acct_ix) {
+    const std::string& p = meta.account_parent.at(name);
+    if (!p.empty()) { auto it = acct_ix.find(p); if (it != acct_ix.end()) parent[ix] = it->second; }
+  }
+  std::vector<cns_submit_part_limit> plims;
+  auto add_plim = [&](const PartitionResourceLimit& s) {
+    cns_submit_part_limit d{};
+    d.max_submit_jobs = s.max_submit_jobs; d.max_wall_duration_per_job_sec = s.max_wall_duration_per_job; d.max_tres_per_job = to_tres(s.max_tres_per_job);
+    plims.push_back(d);
+    return (uint32_t)plims.size() - 1;
+  };
+  std::vector<uint32_t> upl((size_t)UA * Pn, CNS_LIM_NONE), apl((size_t)A * Pn, CNS_LIM_NONE);
+  for (const auto& [key, x] : ua_ix)
+    for (const auto& [pname, lim] : meta.user_accounts.at(key.first).at(key.second)) {
+      auto pit = I.part_idx.find(pname);
+      if (pit != I.part_idx.end()) upl[(size_t)x * Pn + pit->second] = add_plim(lim);
+    }
+  for (const auto& [aname, lims] : meta.account_partition_limits) {
+    auto ait = acct_ix.find(aname);
+    if (ait == acct_ix.end()) continue;
+    for (const auto& [pname, lim] : lims) {
+      auto pit = I.part_idx.find(pname);
+      if (pit != I.part_idx.end()) apl[(size_t)ait->second * Pn + pit->second] = add_plim(lim);
+    }
+  }
+  // ---- usage, submit counts, exists (an entity is in its map or not; a missing nested entry is a zero entry) ----
+  std::vector<cns_usage> uq((size_t)U * Q), aq((size_t)A * Q), qu(Q);
+  std::vector<uint32_t> uqs((size_t)U * Q, 0), ups((size_t)UA * Pn, 0), aqs((size_t)A * Q, 0), aps((size_t)A * Pn, 0), qs(Q, 0);
+  std::vector<uint8_t> uex(U, 0), aex(A, 0), qex(Q, 0);
+  for (const auto& [uname, stat] : meta.user_meta) {
+    auto uit = user_ix.find(uname);
+    if (uit == user_ix.end()) continue;
+    uex[uit->second] = 1;
+    for (const auto& [qname, m] : stat.qos_to_resource_map) {
+      auto qit = qos_ix.find(qname);
+      if (qit != qos_ix.end()) { uq[(size_t)uit->second * Q + qit->second] = to_usage(m); uqs[(size_t)uit->second * Q + qit->second] = m.submit_jobs_count; }
+    }
+    for (const auto& [aname, pm] : stat.account_to_partition_to_resource_map) {
+      auto x = ua_ix.find({uname, aname});
+      if (x == ua_ix.end()) continue;
+      for (const auto& [pname, m] : pm) {
+        auto pit = I.part_idx.find(pname);
+        if (pit != I.part_idx.end()) ups[(size_t)x->second * Pn + pit->second] = m.submit_jobs_count;
+      }
+    }
+  }
+  for (const auto& [aname, stat] : meta.account_meta) {
+    auto ait = acct_ix.find(aname);
+    if (ait == acct_ix.end()) continue;
+    aex[ait->second] = 1;
+    for (const auto& [qname, m] : stat.qos_to_resource_map) {
+      auto qit = qos_ix.find(qname);
+      if (qit != qos_ix.end()) { aq[(size_t)ait->second * Q + qit->second] = to_usage(m); aqs[(size_t)ait->second * Q + qit->second] = m.submit_jobs_count; }
+    }
+    for (const auto& [pname, m] : stat.partition_to_resource_map) {
+      auto pit = I.part_idx.find(pname);
+      if (pit != I.part_idx.end()) aps[(size_t)ait->second * Pn + pit->second] = m.submit_jobs_count;
+    }
+  }
+  for (const auto& [qname, m] : meta.qos_meta) {
+    auto qit = qos_ix.find(qname);
+    if (qit != qos_ix.end()) { qu[qit->second] = to_usage(m); qs[qit->second] = m.submit_jobs_count; qex[qit->second] = 1; }
+  }
+  cns_submit_tables t{};
+  t.num_users = U; t.num_user_accts = UA; t.num_accounts = A; t.num_qos = Q; t.num_partitions = Pn; t.num_part_limits = (uint32_t)plims.size();
+  t.gres = I.layout;
+  t.qos = qos.data(); t.acct_parent = parent.data(); t.part_limits = plims.data(); t.user_part_limit = upl.data(); t.acct_part_limit = apl.data();
+  t.user_qos = uq.data(); t.acct_qos = aq.data(); t.qos_usage = qu.data();
+  t.user_qos_submit = uqs.data(); t.user_part_submit = ups.data(); t.acct_qos_submit = aqs.data(); t.acct_part_submit = aps.data(); t.qos_submit = qs.data();
+  t.user_exists = uex.data(); t.acct_exists = aex.data(); t.qos_exists = qex.data();
+  int st = cns_set_submit_limits(I.h, &t);
+  if (st != 0) return fail(st, cns_last_error(I.h));
+
+  // ---- the jobs through the packer of the cycle; the keys, and the lookups the reference fails on before the checks (:85-95, the caller's) ----
+  std::vector<PdJobInScheduler*> ord(J);
+  for (size_t j = 0; j < J; ++j) ord[j] = requests[j].job;
+  Impl::PackedJobs B(nullptr);
+  I.pack_pending(ord, B);
+  std::vector<uint32_t> user(J, 0), ua(J, CNS_LIM_NONE), acct(J, 0), qosv(J, 0), count(J, 1);
+  std::vector<uint8_t> skip(J, 0);
+  std::vector<const char*> lookup_err(J, nullptr);
+  for (size_t i = 0; i < J; ++i) {
+    const PdJobInScheduler& p = *requests[i].job;
+    count[i] = requests[i].count;
+    if (requests[i].skip) { skip[i] = 1; continue; }
+    auto uit = user_ix.find(p.username);
+    auto qit = qos_ix.find(p.qos);
+    auto ait = acct_ix.find(p.account);
+    auto xit = ua_ix.find({p.username, p.account});
+    const char* err = nullptr;
+    if (uit == user_ix.end()) err = "ERR_INVALID_USER";
+    else if (ait == acct_ix.end()) err = "ERR_INVALID_ACCOUNT";            // :88
+    else if (qit == qos_ix.end()) err = "ERR_INVALID_QOS";                 // :94
+    else if (B.part[i] >= Pn) err = "ERR_INVALID_PARTITION";
+    if (err) { skip[i] = 1; lookup_err[i] = err; continue; }
+    user[i] = uit->second; acct[i] = ait->second; qosv[i] = qit->second;
+    if (xit != ua_ix.end()) ua[i] = xit->second;                           // else :703-708 decides, in its place
+  }
+  cns_job_soa js{};
+  js.num_jobs = J;
+  js.partition = B.part.data(); js.time_limit_sec = B.L.data(); js.node_cpu_raw = B.ncpu.data(); js.node_mem = B.nmem.data();
+  js.task_cpu_raw = B.tcpu.data(); js.task_mem = B.tmem.data(); js.node_num = B.k.data(); js.ntasks = B.nt.data();
+  js.gres_total = B.gtot.data(); js.gres_spec = B.gspec.data();
+  cns_submit_keys ks{user.data(), ua.data(), acct.data(), qosv.data(), count.data(), skip.data()};
+  std::vector<uint8_t> code(J);
+  std::vector<int64_t> tlo(J);
+  uint64_t admitted = 0;
+  cns_submit_out so{code.data(), tlo.data(), &admitted};
+  st = cns_check_submissions(I.h, &js, &ks, 0, &so);
+  if (st != 0) return fail(st, cns_last_error(I.h));
+  if (timing) cns_get_submit_timing(I.h, timing);
+
+  static const char* const kErr[] = {"SUCCESS", "", "ERR_INVALID_PARAM", "ERR_INVALID_PARAM", "ERR_MAX_JOB_COUNT_PER_USER", "ERR_MAX_JOB_COUNT_PER_ACCOUNT",
+                                     "ERR_QOS_JOB_COUNT_EXCEEDED", "ERR_CPUS_PER_TASK_BEYOND", "ERR_TRES_PER_JOB_BEYOND", "ERR_TIME_TIMIT_BEYOND",
+                                     "ERR_USER_ACCOUNT_MISMATCH", "ERR_PARTITION_TRES_PER_JOB_BEYOND", "ERR_PARTITION_TIME_BEYOND",
+                                     "ERR_PARTITION_MAX_SUBMIT_JOBS_PER_USER", "ERR_PARTITION_MAX_SUBMIT_JOBS_PER_ACCOUNT", "ERR_MAX_TRES_PER_USER_BEYOND",
+                                     "ERR_MAX_TRES_PER_ACCOUNT_BEYOND"};
+  static_assert(CNS_SUBMIT_MAX_TRES_PER_ACCOUNT_BEYOND == 16 && CNS_SUBMIT_TIME_LIMIT_BEYOND == 9 && CNS_SUBMIT_USER_ACCOUNT_MISMATCH == 10, "kErr follows cns_submit_code");
+  out->resize(J);
+  for (size_t i = 0; i < J; ++i) {
+    SubmitAnswer& a = (*out)[i];
+    a.code = code[i];
+    a.crane_err = lookup_err[i] ? lookup_err[i] : code[i] <= CNS_SUBMIT_MAX_TRES_PER_ACCOUNT_BEYOND ? kErr[code[i]] : "ERR_INVALID_PARAM";
+    a.time_limit = tlo[i];
+    if (code[i] == CNS_SUBMIT_OK) requests[i].job->time_limit = tlo[i];   // :119 rewrites the job
+  }
+
+  // ---- MallocMetaSubmitResource's result back into the caller's maps: the counts that grew, and the records it created ----
+  std::vector<uint32_t> uqs2(uqs.size()), ups2(ups.size()), aqs2(aqs.size()), aps2(aps.size()), qs2(qs.size());
+  std::vector<uint8_t> uex2(U), aex2(A), qex2(Q);
+  st = cns_get_submit_usage(I.h, uqs2.data(), ups2.data(), aqs2.data(), aps2.data(), qs2.data(), uex2.data(), aex2.data(), qex2.data());
+  if (st != 0) return fail(st, cns_last_error(I.h));
+  for (const auto& [uname, uix] : user_ix) {
+    if (uex2[uix] && !uex[uix]) meta.user_meta[uname];
+    for (const auto& [qname, qix] : qos_ix)
+      if (uqs2[(size_t)uix * Q + qix] != uqs[(size_t)uix * Q + qix]) meta.user_meta[uname].qos_to_resource_map[qname].submit_jobs_count = uqs2[(size_t)uix * Q + qix];
+  }
+  for (const auto& [key, x] : ua_ix)
+    for (uint32_t pp = 0; pp < Pn; ++pp)
+      if (ups2[(size_t)x * Pn + pp] != ups[(size_t)x * Pn + pp])
+        meta.user_meta[key.first].account_to_partition_to_resource_map[key.second][part_name[pp]].submit_jobs_count = ups2[(size_t)x * Pn + pp];
+  for (const auto& [aname, aix] : acct_ix) {
+    if (aex2[aix] && !aex[aix]) meta.account_meta[aname];
+    for (const auto& [qname, qix] : qos_ix)
+      if (aqs2[(size_t)aix * Q + qix] != aqs[(size_t)aix * Q + qix]) meta.account_meta[aname].qos_to_resource_map[qname].submit_jobs_count = aqs2[(size_t)aix * Q + qix];
+    for (uint32_t pp = 0; pp < Pn; ++pp)
+      if (aps2[(size_t)aix * Pn + pp] != aps[(size_t)aix * Pn + pp]) meta.account_meta[aname].partition_to_resource_map[part_name[pp]].submit_jobs_count = aps2[(size_t)aix * Pn + pp];
+  }
+  for (const auto& [qname, qix] : qos_ix)
+    if (qs2[qix] != qs[qix] || (qex2[qix] && !qex[qix])) meta.qos_meta[qname].submit_jobs_count = qs2[qix];
+  status_ = 0;
+  error_.clear();
+  return true;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // Step scheduling (JobScheduler.cpp:1992-2001 -> CtldPublicDefs.cpp:2038-2159), all jobs in one device call.

@@ -32,6 +32,7 @@
 
 struct cns_engine;
 struct cns_group_info;
+struct cns_submit_timing;
 
 namespace crane {
 
@@ -177,12 +178,22 @@ struct Qos {
   cpu_t max_cpus_per_user{cpu_t::from_raw(int64_t{1} << 53)};   // kUnlimitedCpu
   int64_t max_wall{0};                                          // absl::Duration seconds, 0 = unlimited
   ResourceView max_tres, max_tres_per_user, max_tres_per_account;
+  // the submit side (TryMallocMetaSubmitResource, AccountMetaContainer.cpp:75-153); the defaults mean "unlimited / flag off"
+  uint32_t max_submit_jobs_per_user{UINT32_MAX};
+  uint32_t max_submit_jobs_per_account{UINT32_MAX};
+  uint32_t max_submit_jobs{UINT32_MAX};
+  bool deny_on_limit{false};                                    // flags[QosFlags::DenyOnLimit]
+  int64_t max_time_limit_per_job{315576000000};                 // absl::Duration seconds; kJobMaxTimeLimitSec
   Qos();
 };
 struct PartitionResourceLimit {  // AccountDefs.h:163-175
   ResourceView max_tres;
   uint32_t max_jobs{UINT32_MAX};
   int64_t max_wall{0};
+  // the submit side (CheckSubmitLimits_, AccountMetaContainer.cpp:715-749,784-819)
+  ResourceView max_tres_per_job;
+  uint32_t max_submit_jobs{UINT32_MAX};
+  int64_t max_wall_duration_per_job{315576000000};              // the reference sets it from the database; kJobMaxTimeLimitSec = no cap
   PartitionResourceLimit();
 };
 struct MetaResource {  // AccountMetaContainer.h:30-35
@@ -432,6 +443,35 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   bool CommitCheck(const std::vector<ResReduceEvent>& events, const std::function<const ResvMetaNow*(const std::string&)>& resv_now,
                    const std::unordered_set<job_id_t>& running_alive, const std::unordered_set<job_id_t>& pending_alive,
                    std::vector<uint8_t>* codes = nullptr, double* kernel_ms = nullptr);
+
+  // ---- the submit limits over a batch of submissions (include/crane_gpu_submit/submit_limits.h) -----------------------------------------
+  // AccountMetaContainer::TryMallocMetaSubmitResource + MallocMetaSubmitResource (AccountMetaContainer.cpp:75-153, the call at
+  // JobScheduler.cpp:3465-3476) for every request, IN THE ORDER GIVEN (arrival order): request i sees the submit counts as requests 0..i-1
+  // left them.  The jobs go through the packer of the cycle (its partition and GRES name tables); `meta` is packed to dense indices as
+  // CheckAndMallocMetaResource packs it, with the submit-side fields of Qos / PartitionResourceLimit, MetaResource::submit_jobs_count and
+  // "the user / account / QoS has a record" (user_meta / account_meta / qos_meta contain the name).  Per request the engine's code
+  // (cns_submit_code: the first failing check in the reference's order), the CraneErrCode NAME the reference returns there ("SUCCESS" when
+  // admitted; ERR_INVALID_PARAM for count == 0, JobScheduler.cpp:3466, and for a request whose arithmetic overflows) and the time limit
+  // after :118-119.  A request with `skip` set is not looked at (it failed CheckJobValidity or an earlier check): "" and
+  // CNS_SUBMIT_NOT_CANDIDATE; an unknown user, account, QoS or partition — lookups that stay with the caller, :3461-3463, :85-95 — comes back
+  // as ERR_INVALID_USER / ERR_INVALID_ACCOUNT / ERR_INVALID_QOS / ERR_INVALID_PARTITION with the same code and nothing checked.
+  // Written: `meta`'s submit_jobs_count of every record an admitted request touched and the records an admission created
+  // (DoMallocResource_, :1067-1124); jobs_count, resource and wall_time stay.  An admitted job's time_limit is rewritten as :119 does.
+  // UserAddJob (:3476), qos_priority (:116) and the frees stay with the caller.  false on an engine error (no device, no snapshot, several
+  // devices: CNS_ERR_UNSUPPORTED, counts that could pass UINT32_MAX, a chain of more than 6 accounts): `out` is empty, nothing is written and
+  // Ok() / LastStatus() / LastError() say why; nothing is thrown.
+  struct SubmitRequest {
+    PdJobInScheduler* job{nullptr};
+    uint32_t count{1};             // QosSubmitReserveCount(job): an array job's children, else 1
+    bool skip{false};
+  };
+  struct SubmitAnswer {
+    uint8_t code{0};               // cns_submit_code
+    const char* crane_err{""};     // CraneErrCode name
+    int64_t time_limit{0};
+  };
+  bool CheckSubmitLimits(const std::vector<SubmitRequest>& requests, AccountMetaSnapshot* meta, std::vector<SubmitAnswer>* out,
+                         cns_submit_timing* timing = nullptr);
 
   // ---- event-fed mirror of the running allocations -------------------------------------------------
   // Instead of re-deriving the running jobs' allocations from the vector NodeSelect is handed every cycle, the adapter

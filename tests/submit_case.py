@@ -1,0 +1,205 @@
+"""Inputs for the submit-limit tests: the hand-derived table (expected codes written out by hand from the cited lines of
+AccountMetaContainer.cpp, NOT produced by running tests/submit_pyref.py), and seeded random tables."""
+import numpy as np
+
+from cranesched_amd import abi, limits as lm, submit as sb
+
+KMAX = abi.SUBMIT_JOB_MAX_TIME_LIMIT_SEC
+GIB = 1 << 30
+NONE = sb.LIM_NONE
+LAYOUT = abi.GresLayout(class_name=[0, 0, 1], class_shift=[0, 8, 16], class_width=[8, 8, 8])   # name 0: classes 0, 1; name 1: class 2
+
+
+def make_jobs(J, partition=0, time_limit_sec=600, task_cpu_raw=256, task_mem=GIB, node_num=1, ntasks=1, node_mem=0, gres_total=None, gres_spec=None):
+    full = lambda v, dt: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dt), (J,))).copy()
+    one = np.ones(J, np.uint32)
+    return abi.Jobs(partition=full(partition, np.uint32), time_limit_sec=full(time_limit_sec, np.int64), node_mem=full(node_mem, np.uint64),
+                    task_cpu_raw=full(task_cpu_raw, np.int64), task_mem=full(task_mem, np.uint64), node_num=full(node_num, np.uint32),
+                    ntasks=full(ntasks, np.uint32), ntasks_per_node_min=one, ntasks_per_node_max=one.copy(),
+                    gres_total=gres_total, gres_spec=gres_spec)
+
+
+def hand_table():
+    """-> (tables, jobs, keys, expected codes, expected time limits, admitted: [(user, user_acct, qos, chain accounts, partition, count)],
+    created: (users, accounts, qos) whose record the batch creates).  One line per job below says which statement decides it."""
+    U = 28                      # user j serves job j unless a line says otherwise; user_acct index = user index
+    Q, Pn, A = 15, 2, 11
+    # accounts: 0 root, 1 -> 0; 2 root <- 3 <- 4 <- 5 <- 6 <- 7 (a chain of six from 7); 8, 9, 10 roots
+    parent = np.array([NONE, 0, NONE, 2, 3, 4, 5, 6, NONE, NONE, NONE], np.uint32)
+    q = [sb.submit_qos() for _ in range(Q)]                                     # q0: the defaults, nothing limited
+    q[1] = sb.submit_qos(max_submit_jobs_per_user=3, max_submit_jobs_per_account=5, max_submit_jobs=6, max_cpus_per_user=64,
+                         max_time_limit_per_job_sec=3600)
+    q[2] = sb.submit_qos(deny_on_limit=True, max_jobs_per_user=0)
+    q[3] = sb.submit_qos(deny_on_limit=True, max_wall_sec=1000)
+    q[4] = sb.submit_qos(max_submit_jobs_per_account=2)
+    q[5] = sb.submit_qos(max_submit_jobs=2)
+    q[6] = sb.submit_qos(deny_on_limit=True, max_cpus_per_user=8, max_tres_per_user=lm.tres(cpu=8))
+    q[7] = sb.submit_qos(max_tres_per_account=lm.tres(mem=4 * GIB))
+    q[8] = sb.submit_qos()
+    q[9] = sb.submit_qos(max_submit_jobs_per_user=10)
+    q[10] = sb.submit_qos(max_submit_jobs_per_user=60)
+    q[11] = sb.submit_qos(deny_on_limit=True, max_time_limit_per_job_sec=500, max_wall_sec=1000)
+    q[12] = sb.submit_qos(max_submit_jobs_per_account=4)
+    q[13] = sb.submit_qos(deny_on_limit=True, max_tres_per_user=lm.tres(mem=8 * GIB))
+    q[14] = sb.submit_qos(deny_on_limit=True, max_tres_per_account=lm.tres(names={0: 100}, classes={1: 2}))
+    pl = [sb.submit_part_limit(max_tres_per_job=lm.tres(names={0: 2})),          # pl0
+          sb.submit_part_limit(max_wall_duration_per_job_sec=86400),             # pl1
+          sb.submit_part_limit(max_submit_jobs=1),                               # pl2
+          sb.submit_part_limit(max_tres_per_job=lm.tres(names={1: 0})),          # pl3: holds name 1 only
+          sb.submit_part_limit(max_submit_jobs=3)]                               # pl4
+    upl = np.full(U * Pn, NONE, np.uint32)
+    apl = np.full(A * Pn, NONE, np.uint32)
+    upl[11 * Pn + 1], upl[12 * Pn + 0], upl[13 * Pn + 0], upl[14 * Pn + 0], upl[23 * Pn + 1] = 0, 1, 2, 2, 3
+    apl[10 * Pn + 0] = 4
+    uq_use, aq_use, g_use = np.zeros(U * Q, lm.USAGE_DT), np.zeros(A * Q, lm.USAGE_DT), np.zeros(Q, lm.USAGE_DT)
+    uq_use[6 * Q + 6]["cpu_raw"] = 4 * 256
+    uq_use[24 * Q + 13]["mem"] = 15 * GIB // 2
+    aq_use[9 * Q + 14]["name_total"][0] = 2
+    aq_use[9 * Q + 14]["class_count"][1] = 2
+    g_use[3]["wall_sec"] = 900
+    g_use[11]["wall_sec"] = 400
+    uq_s, up_s, aq_s, ap_s, g_s = (np.zeros(n, np.uint32) for n in (U * Q, U * Pn, A * Q, A * Pn, Q))
+    uq_s[15 * Q + 10] = 20
+    aq_s[2 * Q + 12] = 4
+    ap_s[10 * Pn + 0] = 3
+    uex, aex, qex = np.ones(U, np.uint8), np.ones(A, np.uint8), np.ones(Q, np.uint8)
+    uex[17] = 0
+    qex[3] = 0
+    t = sb.SubmitTables(layout=LAYOUT, num_users=U, num_user_accts=U, num_partitions=Pn, qos=np.array(q), acct_parent=parent, part_limits=np.array(pl),
+                        user_part_limit=upl, acct_part_limit=apl, user_qos=uq_use, acct_qos=aq_use, qos_usage=g_use, user_qos_submit=uq_s,
+                        user_part_submit=up_s, acct_qos_submit=aq_s, acct_part_submit=ap_s, qos_submit=g_s, user_exists=uex, acct_exists=aex, qos_exists=qex)
+
+    C = abi
+    rows = [
+        # user acct qos  fields                                            expected code                        time limit out
+        (0, 8, 0, dict(skip=1), C.SUBMIT_NOT_CANDIDATE, 600),                                   # 0: the caller's skip: nothing read or added
+        (0, 8, 0, dict(count=0), C.SUBMIT_BAD_COUNT, 600),                                      # 1: JobScheduler.cpp:3466
+        (2, 8, 0, dict(task_cpu_raw=1 << 62, ntasks=4), C.SUBMIT_BAD_REQUEST, 600),             # 2: 2^62 * 4 leaves int64
+        (3, 8, 1, dict(count=4), C.SUBMIT_MAX_JOB_COUNT_PER_USER, 600),                         # 3: :99  4 > 3
+        (4, 8, 4, dict(count=3), C.SUBMIT_MAX_JOB_COUNT_PER_ACCOUNT, 600),                      # 4: :102 3 > 2
+        (5, 8, 5, dict(count=3), C.SUBMIT_QOS_JOB_COUNT_EXCEEDED, 600),                         # 5: :105 3 > 2
+        (6, 8, 6, dict(count=3, task_cpu_raw=768), C.SUBMIT_CPUS_PER_TASK_BEYOND, 600),         # 6: :108 3 cores x 3 = 9 > 8
+        (6, 8, 6, dict(count=2, task_cpu_raw=768), C.SUBMIT_OK, 600),                           # 7: :108 3 x 2 = 6 <= 8; :401 3 x 1 + 4 used = 7 <= 8 (x 2: 10)
+        (8, 8, 7, dict(count=5), C.SUBMIT_TRES_PER_JOB_BEYOND, 600),                            # 8: :112 1 GiB x 5 > 4 GiB per account
+        (9, 8, 1, dict(time_limit_sec=7200), C.SUBMIT_TIME_LIMIT_BEYOND, 7200),                 # 9: :120 7200 > 3600
+        (10, 8, 0, dict(user_acct=NONE), C.SUBMIT_USER_ACCOUNT_MISMATCH, 600),                  # 10: :703
+        (11, 8, 0, dict(partition=1, gres_total=[3, 0, 0, 0]), C.SUBMIT_PARTITION_TRES_PER_JOB_BEYOND, 600),   # 11: :716 pl0: 3 > 2 of name 0
+        (12, 8, 8, dict(time_limit_sec=KMAX + 5), C.SUBMIT_PARTITION_TIME_BEYOND, KMAX),        # 12: :118 rewrite to q8's KMAX, :727-728 KMAX > 86400 (pl1)
+        (13, 8, 0, dict(count=2), C.SUBMIT_PARTITION_MAX_SUBMIT_JOBS_PER_USER, 600),            # 13: :739-741 pl2: 2 > 1, q0 sets no per-user cap
+        (14, 8, 9, dict(count=2), C.SUBMIT_OK, 600),                                            # 14: pl2 again, but q9 sets max_submit_jobs_per_user: :739 and :423 skip it
+        (15, 8, 10, dict(count=50), C.SUBMIT_MAX_JOB_COUNT_PER_USER, 600),                      # 15: :384 20 + 50 > 60
+        (15, 8, 10, dict(), C.SUBMIT_OK, 600),                                                  # 16: :384 20 + 1 <= 60: job 15 added nothing
+        (17, 8, 2, dict(), C.SUBMIT_OK, 600),                                                   # 17: user 17 has no record: :751 skips the user checks; creates it
+        (17, 8, 2, dict(), C.SUBMIT_MAX_JOB_COUNT_PER_USER, 600),                               # 18: the record exists now: :392 0 + 1 > max_jobs_per_user = 0
+        (19, 8, 3, dict(), C.SUBMIT_OK, 600),                                                   # 19: QoS 3 has no record: :841 skips; creates it
+        (20, 8, 3, dict(), C.SUBMIT_TIME_LIMIT_BEYOND, 600),                                    # 20: :863-864 900 + 600 > 1000
+        (21, 8, 11, dict(time_limit_sec=KMAX), C.SUBMIT_OK, 500),                               # 21: :118 rewrite to 500; :864 400 + 500 <= 1000
+        (22, 7, 12, dict(), C.SUBMIT_MAX_JOB_COUNT_PER_ACCOUNT, 600),                           # 22: accounts 7, 6, 5, 4, 3 pass (0 + 1 <= 4), the root 2: 4 + 1 > 4
+        (23, 8, 0, dict(partition=1, gres_total=[5, 9, 0, 0]), C.SUBMIT_OK, 600),               # 23: pl3 lacks name 0: :1034 returns true before name 1 (9 > 0)
+        (24, 8, 13, dict(), C.SUBMIT_MAX_TRES_PER_USER_BEYOND, 600),                            # 24: :403 1 GiB + 7.5 GiB used > 8 GiB
+        (25, 9, 14, dict(gres_total=[1, 0, 0, 0], gres_spec=[0, 1, 0]), C.SUBMIT_MAX_TRES_PER_ACCOUNT_BEYOND, 600),   # 25: :406 class 1: 1 + 2 used > 2 (:1045)
+        (26, 10, 0, dict(), C.SUBMIT_PARTITION_MAX_SUBMIT_JOBS_PER_ACCOUNT, 600),               # 26: :469 pl4: 3 + 1 > 3 (static :811: 1 <= 3)
+        (0, 1, 0, dict(count=3), C.SUBMIT_OK, 600),                                             # 27: adds 3 along the chain 1 -> 0
+    ]
+    J = len(rows)
+    gt, gs = np.zeros((J, 4), np.uint8), np.zeros((J, 8), np.uint8)
+    f = {k: [] for k in ("partition", "time_limit_sec", "task_cpu_raw", "ntasks", "count", "skip", "user_acct")}
+    for j, (u, a, qi, kw, code, tlo) in enumerate(rows):
+        f["partition"].append(kw.get("partition", 0)); f["time_limit_sec"].append(kw.get("time_limit_sec", 600))
+        f["task_cpu_raw"].append(kw.get("task_cpu_raw", 256)); f["ntasks"].append(kw.get("ntasks", 1))
+        f["count"].append(kw.get("count", 1)); f["skip"].append(kw.get("skip", 0)); f["user_acct"].append(kw.get("user_acct", u))
+        gt[j, :] = kw.get("gres_total", [0, 0, 0, 0])
+        gs[j, :3] = kw.get("gres_spec", [0, 0, 0])
+    jobs = make_jobs(J, partition=f["partition"], time_limit_sec=f["time_limit_sec"], task_cpu_raw=f["task_cpu_raw"], ntasks=f["ntasks"],
+                     gres_total=gt, gres_spec=gs)
+    keys = sb.SubmitKeys([r[0] for r in rows], f["user_acct"], [r[1] for r in rows], [r[2] for r in rows], f["count"], f["skip"])
+    codes = np.array([r[4] for r in rows], np.uint8)
+    tlo = np.array([r[5] for r in rows], np.int64)
+    # what MallocMetaSubmitResource adds (:1086-1123), job by job, for the admitted jobs 7, 14, 16, 17, 19, 21, 23, 27
+    admitted = [(6, 6, 6, [8], 0, 2), (14, 14, 9, [8], 0, 2), (15, 15, 10, [8], 0, 1), (17, 17, 2, [8], 0, 1), (19, 19, 3, [8], 0, 1),
+                (21, 21, 11, [8], 0, 1), (23, 23, 0, [8], 1, 1), (0, 0, 0, [1, 0], 0, 3)]
+    created = ([17], [], [3])
+    return t, jobs, keys, codes, tlo, admitted, created
+
+
+def expected_state(t, admitted, created):
+    """The tables' state plus the hand-listed additions."""
+    s = t.state()
+    Q, Pn = t.num_qos, t.num_partitions
+    for u, x, q, chain, p, c in admitted:
+        s.user_qos_submit[u * Q + q] += c; s.user_part_submit[x * Pn + p] += c; s.qos_submit[q] += c
+        for a in chain:
+            s.acct_qos_submit[a * Q + q] += c; s.acct_part_submit[a * Pn + p] += c
+    for arr, idx in zip((s.user_exists, s.acct_exists, s.qos_exists), created):
+        for i in idx:
+            arr[i] = 1
+    return s
+
+
+def random_case(seed, J, U=200, A=64, Q=4, Pn=8, array_frac=0.10):
+    """About U users, A accounts in a tree, Q QoS, Pn partitions, mixed limits, DenyOnLimit / max_jobs == 0 QoS, a mix of exists bits,
+    array_frac of the jobs with counts 2..199."""
+    r = np.random.default_rng(seed)
+    parent = np.full(A, NONE, np.uint32)
+    depth = np.ones(A, np.int64)
+    for a in range(4, A):                                     # 4 roots; a chain never holds more than 6 accounts
+        p = int(r.integers(0, a))
+        while depth[p] >= 6:
+            p = int(r.integers(0, a))
+        parent[a], depth[a] = p, depth[p] + 1
+    cap = max(J // 8, 4)
+    q = [sb.submit_qos(),
+         sb.submit_qos(max_submit_jobs_per_user=max(cap // 20, 2), max_submit_jobs_per_account=cap, max_time_limit_per_job_sec=86400),
+         sb.submit_qos(deny_on_limit=True, max_jobs_per_user=0, max_submit_jobs=cap * 2, max_wall_sec=10 ** 7),
+         sb.submit_qos(deny_on_limit=True, max_jobs_per_account=3, max_submit_jobs_per_account=cap // 2 + 1,
+                       max_tres_per_user=lm.tres(cpu=64, names={0: 6}, classes={1: 2}), max_tres=lm.tres(mem=4096 * GIB))][:Q]
+    while len(q) < Q:
+        q.append(sb.submit_qos())
+    pl = [sb.submit_part_limit(max_submit_jobs=max(cap // 30, 1)), sb.submit_part_limit(max_submit_jobs=cap // 3 + 1, max_wall_duration_per_job_sec=7200),
+          sb.submit_part_limit(max_tres_per_job=lm.tres(cpu=16, names={1: 1}))]
+    UA = U
+    ua_acct = r.integers(0, A, UA).astype(np.uint32)          # user_acct i = (user i, account ua_acct[i])
+    upl = np.where(r.random(UA * Pn) < 0.3, r.integers(0, len(pl), UA * Pn), NONE).astype(np.uint32)
+    apl = np.where(r.random(A * Pn) < 0.3, r.integers(0, len(pl), A * Pn), NONE).astype(np.uint32)
+    uq_use, aq_use, g_use = np.zeros(U * Q, lm.USAGE_DT), np.zeros(A * Q, lm.USAGE_DT), np.zeros(Q, lm.USAGE_DT)
+    uq_use["cpu_raw"] = r.integers(0, 60, U * Q) * 256
+    uq_use["name_total"][:, 0] = r.integers(0, 6, U * Q)
+    uq_use["class_count"][:, 1] = np.minimum(uq_use["name_total"][:, 0], r.integers(0, 3, U * Q))
+    aq_use["jobs_count"] = r.integers(0, 5, A * Q)
+    g_use["wall_sec"] = r.integers(0, 10 ** 7, Q)
+    g_use["mem"] = r.integers(0, 4096, Q).astype(np.uint64) * GIB
+    t = sb.SubmitTables(layout=LAYOUT, num_users=U, num_user_accts=UA, num_partitions=Pn, qos=np.array(q), acct_parent=parent, part_limits=np.array(pl),
+                        user_part_limit=upl, acct_part_limit=apl, user_qos=uq_use, acct_qos=aq_use, qos_usage=g_use,
+                        user_qos_submit=r.integers(0, 3, U * Q), user_part_submit=r.integers(0, 3, UA * Pn), acct_qos_submit=r.integers(0, 5, A * Q),
+                        acct_part_submit=r.integers(0, 5, A * Pn), qos_submit=r.integers(0, 9, Q), user_exists=r.random(U) < 0.5,
+                        acct_exists=r.random(A) < 0.5, qos_exists=r.random(Q) < 0.5)
+    user = r.integers(0, U, J).astype(np.uint32)
+    count = np.where(r.random(J) < array_frac, r.integers(2, 200, J), 1).astype(np.uint32)
+    count[r.random(J) < 0.005] = 0
+    gt, gs = np.zeros((J, 4), np.uint8), np.zeros((J, 8), np.uint8)
+    g = r.random(J) < 0.2
+    gt[g, 0] = r.integers(1, 4, int(g.sum()))
+    gs[g, 1] = np.minimum(gt[g, 0], r.integers(0, 3, int(g.sum())))
+    gt[r.random(J) < 0.03, 1] = 1
+    tl = r.integers(60, 100000, J).astype(np.int64)
+    tl[r.random(J) < 0.05] = KMAX
+    jobs = make_jobs(J, partition=r.integers(0, Pn, J), time_limit_sec=tl, task_cpu_raw=r.integers(1, 9, J) * 256, task_mem=r.integers(1, 9, J).astype(np.uint64) * GIB,
+                     node_num=1, ntasks=r.integers(1, 4, J), gres_total=gt, gres_spec=gs)
+    ua = user.copy()
+    ua[r.random(J) < 0.005] = NONE
+    keys = sb.SubmitKeys(user, ua, ua_acct[user], r.integers(0, Q, J), count, (r.random(J) < 0.02).astype(np.uint8))
+    return t, jobs, keys
+
+
+def domino_chain(n):
+    """n unit jobs; consecutive jobs share one record with a cap of 1, alternately an (account, qos) and a (user, qos) record: job 2k is
+    (user k, account k), job 2k + 1 is (user k + 1, account k).  Every entity exists.  Job i is admitted exactly when job i - 1 is not, and
+    nothing else decides it: the bracketing rounds decide exactly one job each."""
+    U = A = n // 2 + 2
+    t = sb.SubmitTables(layout=LAYOUT, num_users=U, num_user_accts=U, num_partitions=1,
+                        qos=np.array([sb.submit_qos(max_submit_jobs_per_user=1, max_submit_jobs_per_account=1)]),
+                        acct_parent=np.full(A, NONE, np.uint32), user_exists=np.ones(U, np.uint8), acct_exists=np.ones(A, np.uint8),
+                        qos_exists=np.ones(1, np.uint8))
+    i = np.arange(n)
+    user, acct = (i + 1) // 2, i // 2
+    return t, make_jobs(n), sb.SubmitKeys(user, user, acct, np.zeros(n, np.uint32))
