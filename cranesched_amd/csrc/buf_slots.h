@@ -1,0 +1,33 @@
+// The slots of cns_engine's per-feature device buffer sets: one enum per set, its *_COUNT sizes the array.
+#pragma once
+
+// cns_engine::d_pb (probe_host.inc)
+enum { PB_RAW0 = 0 /* .. 15: the caller's arrays, as cns_engine::d_raw */, PB_JOBS = 16, PB_INCL, PB_EXCL, PB_REASON, PB_RESULTS, PB_PARAMS, PB_PART, PB_CTR,
+       PB_HEAP, PB_JTAG, PB_FAULT, PB_COUNT };
+
+// cns_engine::d_rq (resvq_host.inc)
+enum { RQ_LATEST = 0, RQ_RVOFF, RQ_RVST, RQ_RVED, RQ_RAW_END, RQ_RAW_OFF, RQ_RAW_NODE,                              // state
+       RQ_START, RQ_DUR, RQ_K, RQ_FLAGS, RQ_CANDOFF, RQ_CAND, RQ_CHOFF,                                              // queries
+       RQ_EVOFF, RQ_SEGOFF, RQ_KA, RQ_KB, RQ_KC, RQ_VA, RQ_VB, RQ_SORTED, RQ_HIST, RQ_BEST,                              // earliest mode
+       RQ_CODE, RQ_CHOSEN, RQ_STATUS, RQ_OSTART, RQ_NFREE, RQ_COUNT };                                               // results
+
+// cns_engine::d_vd (valid_host.inc)
+enum { VD_NCPU = 0, VD_NMEM, VD_NGRES, VD_NUNSUP, VD_NODE, VD_POFF, VD_PNODES, VD_TOTAL, VD_RVOFF, VD_RVNODES,              // tables
+       VD_JNCPU, VD_JNMEM, VD_JTCPU, VD_JTMEM, VD_JK, VD_JNT, VD_JGT, VD_JGS, VD_JRSV, VD_IOFF, VD_INCL, VD_EOFF, VD_EXCL,    // jobs
+       VD_ORDER, VD_CHUNKS, VD_CODE, VD_ELIG, VD_COUNT };                                                                     // the call
+
+// cns_engine::d_cc (commit_host.inc)
+enum { CC_CHANGE = 0, CC_EVTIME, CC_EVOFF, CC_EVNODES, CC_SLOT, CC_AREX, CC_AREND, CC_AROFF, CC_ARNODES,   // events
+       CC_LIMIT, CC_RESV, CC_GONE, CC_PREOFF, CC_PRE, CC_ALIVE,                                             // jobs
+       CC_CODE, CC_COUNTS, CC_COUNT };                                                                      // results
+
+// cns_engine::d_sub (submit_host.inc)
+enum { SB_QOS = 0, SB_PL, SB_PARENT, SB_UPL, SB_APL, SB_UQ, SB_AQ, SB_G, SB_ST_SET, SB_ST,                                    // tables
+       SB_JPART, SB_JTL, SB_JNCPU, SB_JNMEM, SB_JTCPU, SB_JTMEM, SB_JK, SB_JNT, SB_JGT, SB_JGS,                                // jobs
+       SB_KUSER, SB_KUA, SB_KACCT, SB_KQOS, SB_KCOUNT, SB_KSKIP,                                                                // keys
+       SB_PRE, SB_STATE, SB_STAT, SB_COND, SB_IKEY, SB_ITHR, SB_CODE, SB_TLO, SB_CTR,                                           // per job
+       SB_SK0, SB_SK1, SB_SV0, SB_SV1, SB_HIST, SB_SKEY, SB_SITEM, SB_SADD, SB_VAL, SB_TAILS, SB_HEADS, SB_CARRY, SB_COUNT };   // the parallel pass
+
+// cns_engine::d_pre (engine.hip: a cycle with preemption)
+enum { B_QPOFF, B_QP, B_PJQOS, B_PJQP, B_PJPRIO, B_PJREC0, B_PJK, B_PJEND, B_RNJOB, B_ENTSLOT, B_ENTGONE, B_RJQOS, B_RJQP,
+       B_RJSTART, B_RJEND, B_RJPRE, B_RJOFF, B_RJENT, B_HEAD, B_RECNEXT, B_RECORIG, B_RECSLOT, B_RECGONE, B_MISC, B_COUNT };

@@ -5,12 +5,6 @@
 // cycle's results where they are: cns_engine::d_results (start, reason, the node of every record) and d_raw[14] (the place offsets),
 // both read only.  Everything the call writes lives in cns_engine::d_cc.  No CPU fallback.
 
-// cns_engine::d_cc
-enum { CC_CHANGE = 0, CC_EVTIME, CC_EVOFF, CC_EVNODES, CC_SLOT, CC_AREX, CC_AREND, CC_AROFF, CC_ARNODES,   // events
-       CC_LIMIT, CC_RESV, CC_GONE, CC_PREOFF, CC_PRE, CC_ALIVE,                                             // jobs
-       CC_CODE, CC_COUNTS, CC_COUNT };                                                                      // results
-static_assert(CC_COUNT <= sizeof(cns_engine::d_cc) / sizeof(DevBuf), "cns_engine::d_cc holds every buffer of the commit check");
-
 static int commit_impl(cns_handle* h, const cns_commit_events* ev, const cns_commit_jobs* jb, const cns_commit_out* out, double* kernel_ms) {
   const u64 J = jb->num_jobs;
   const u32 N = h->N, V = h->V;
@@ -21,8 +15,8 @@ static int commit_impl(cns_handle* h, const cns_commit_events* ev, const cns_com
   u64 entries = 0;
   if (E) {
     if (!ev->ev_time_sec || !ev->ev_offsets) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: node events without times or offsets");
-    for (u32 e = 0; e < E; ++e)
-      if (ev->ev_offsets[e + 1] < ev->ev_offsets[e]) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: ev_offsets decrease at event " + std::to_string(e));
+    if (const u64 e = cns_csr::first_decrease(ev->ev_offsets, E); e < E)   // (this call reports a decrease before the first offset)
+      return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: ev_offsets decrease at event " + std::to_string(e));
     if (ev->ev_offsets[0] != 0) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: ev_offsets[0] != 0");
     entries = ev->ev_offsets[E];
     if (entries && !ev->ev_nodes) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: ev_offsets without ev_nodes");
@@ -34,9 +28,9 @@ static int commit_impl(cns_handle* h, const cns_commit_events* ev, const cns_com
   std::vector<u32> slot, ar_sorted;
   if (A) {
     if (!ev->ar_resv || !ev->ar_exists || !ev->ar_end_sec || !ev->ar_offsets) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: affected reservations with a missing array");
-    if (ev->ar_offsets[0] != 0) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: ar_offsets[0] != 0");
-    for (u32 a = 0; a < A; ++a)
-      if (ev->ar_offsets[a + 1] < ev->ar_offsets[a]) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: ar_offsets decrease at entry " + std::to_string(a));
+    const auto ao = cns_csr::check_offsets(ev->ar_offsets, A);
+    if (ao.what == cns_csr::Offsets::FirstNot0) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: ar_offsets[0] != 0");
+    if (ao.what == cns_csr::Offsets::Decreases) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: ar_offsets decrease at entry " + std::to_string(ao.index));
     const u64 L = ev->ar_offsets[A];
     if (L && !ev->ar_nodes) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: ar_offsets without ar_nodes");
     slot.assign(V, kCcNoSlot);
@@ -46,24 +40,20 @@ static int commit_impl(cns_handle* h, const cns_commit_events* ev, const cns_com
       if (slot[v] != kCcNoSlot) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: reservation " + std::to_string(v) + " is named twice in ar_resv");
       slot[v] = a;
     }
-    ar_sorted.assign(ev->ar_nodes, ev->ar_nodes + L);
-    for (u32 a = 0; a < A; ++a) {
-      const u64 b = ev->ar_offsets[a], e = ev->ar_offsets[a + 1];
-      std::sort(ar_sorted.begin() + b, ar_sorted.begin() + e);
-      for (u64 x = b; x < e; ++x) {
-        if (ar_sorted[x] >= N) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: the node list of ar_resv[" + std::to_string(a) + "] names a node outside the snapshot");
-        if (x > b && ar_sorted[x] == ar_sorted[x - 1])
-          return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: the node list of ar_resv[" + std::to_string(a) + "] names node " + std::to_string(ar_sorted[x]) + " twice");
-      }
-    }
+    ar_sorted.resize(L);
+    const auto al = cns_csr::sort_lists(ev->ar_offsets, ev->ar_nodes, ar_sorted.data(), 0, A, N);
+    if (al.what == cns_csr::Lists::OutOfBound)
+      return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: the node list of ar_resv[" + std::to_string(al.list) + "] names a node outside the snapshot");
+    if (al.what == cns_csr::Lists::Repeated)
+      return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: the node list of ar_resv[" + std::to_string(al.list) + "] names node " + std::to_string(al.value) + " twice");
   }
   // ---- preempted lists: offsets ascending, running references inside the running table ----
   const bool has_pre = J && jb->preempt_offsets != nullptr;
   u64 PL = 0;
   if (has_pre) {
-    if (jb->preempt_offsets[0] != 0) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: preempt_offsets[0] != 0");
-    for (u64 j = 0; j < J; ++j)
-      if (jb->preempt_offsets[j + 1] < jb->preempt_offsets[j]) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: preempt_offsets decrease at job " + std::to_string(j));
+    const auto po = cns_csr::check_offsets(jb->preempt_offsets, J);
+    if (po.what == cns_csr::Offsets::FirstNot0) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: preempt_offsets[0] != 0");
+    if (po.what == cns_csr::Offsets::Decreases) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: preempt_offsets decrease at job " + std::to_string(po.index));
     PL = jb->preempt_offsets[J];
     if (PL && !jb->preempted) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: preempt_offsets without preempted");
     for (u64 x = 0; x < PL; ++x) {
@@ -76,35 +66,30 @@ static int commit_impl(cns_handle* h, const cns_commit_events* ev, const cns_com
 
   HIPCHK(h, hipSetDevice(h->device));
   DevBuf* B = h->d_cc;
-  auto up = [&](int b, const void* src, size_t bytes) -> int {
-    HIPCHK(h, B[b].ensure(bytes));
-    if (bytes && src) HIPCHK(h, hipMemcpyAsync(B[b].p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    return 0;
-  };
   HIPCHK(h, B[CC_COUNTS].ensure(8 * sizeof(u64)));
   HIPCHK(h, hipMemsetAsync(B[CC_COUNTS].p, 0, 8 * sizeof(u64), h->stream));
   float ms = 0;
   if (J) {
     if (entries) {
-      if (int rc = up(CC_EVTIME, ev->ev_time_sec, (size_t)E * 8)) return rc;
-      if (int rc = up(CC_EVOFF, ev->ev_offsets, ((size_t)E + 1) * 8)) return rc;
-      if (int rc = up(CC_EVNODES, ev->ev_nodes, (size_t)entries * 4)) return rc;
+      if (int rc = stage(h, B[CC_EVTIME], ev->ev_time_sec, (size_t)E * 8)) return rc;
+      if (int rc = stage(h, B[CC_EVOFF], ev->ev_offsets, ((size_t)E + 1) * 8)) return rc;
+      if (int rc = stage(h, B[CC_EVNODES], ev->ev_nodes, (size_t)entries * 4)) return rc;
       HIPCHK(h, B[CC_CHANGE].ensure((size_t)N * 8));
     }
     if (A) {
-      if (int rc = up(CC_SLOT, slot.data(), (size_t)V * 4)) return rc;
-      if (int rc = up(CC_AREX, ev->ar_exists, (size_t)A)) return rc;
-      if (int rc = up(CC_AREND, ev->ar_end_sec, (size_t)A * 8)) return rc;
-      if (int rc = up(CC_AROFF, ev->ar_offsets, ((size_t)A + 1) * 8)) return rc;
-      if (int rc = up(CC_ARNODES, ar_sorted.data(), ar_sorted.size() * 4)) return rc;
+      if (int rc = stage(h, B[CC_SLOT], slot.data(), (size_t)V * 4)) return rc;
+      if (int rc = stage(h, B[CC_AREX], ev->ar_exists, (size_t)A)) return rc;
+      if (int rc = stage(h, B[CC_AREND], ev->ar_end_sec, (size_t)A * 8)) return rc;
+      if (int rc = stage(h, B[CC_AROFF], ev->ar_offsets, ((size_t)A + 1) * 8)) return rc;
+      if (int rc = stage(h, B[CC_ARNODES], ar_sorted.data(), ar_sorted.size() * 4)) return rc;
     }
-    if (int rc = up(CC_LIMIT, jb->time_limit_sec, (size_t)J * 8)) return rc;
-    if (jb->reservation) { if (int rc = up(CC_RESV, jb->reservation, (size_t)J * 4)) return rc; }
-    if (jb->gone) { if (int rc = up(CC_GONE, jb->gone, (size_t)J)) return rc; }
+    if (int rc = stage(h, B[CC_LIMIT], jb->time_limit_sec, (size_t)J * 8)) return rc;
+    if (jb->reservation) { if (int rc = stage(h, B[CC_RESV], jb->reservation, (size_t)J * 4)) return rc; }
+    if (jb->gone) { if (int rc = stage(h, B[CC_GONE], jb->gone, (size_t)J)) return rc; }
     if (has_pre) {
-      if (int rc = up(CC_PREOFF, jb->preempt_offsets, ((size_t)J + 1) * 8)) return rc;
-      if (int rc = up(CC_PRE, jb->preempted, (size_t)PL * 4)) return rc;
-      if (int rc = up(CC_ALIVE, jb->running_alive, jb->running_alive ? (size_t)jb->num_running : 0)) return rc;
+      if (int rc = stage(h, B[CC_PREOFF], jb->preempt_offsets, ((size_t)J + 1) * 8)) return rc;
+      if (int rc = stage(h, B[CC_PRE], jb->preempted, (size_t)PL * 4)) return rc;
+      if (int rc = stage(h, B[CC_ALIVE], jb->running_alive, jb->running_alive ? (size_t)jb->num_running : 0)) return rc;
     }
     HIPCHK(h, B[CC_CODE].ensure((size_t)J));
     const char* rb = h->d_results.as<char>();
@@ -122,7 +107,7 @@ static int commit_impl(cns_handle* h, const cns_commit_events* ev, const cns_com
     P.code = B[CC_CODE].as<uint8_t>(); P.counts = B[CC_COUNTS].as<unsigned long long>();
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     if (entries) {
-      hipLaunchKernelGGL(k_cc_fill, dim3((N + kCcBlock - 1) / kCcBlock), dim3(kCcBlock), 0, h->stream, B[CC_CHANGE].as<i64>(), N, kCcNever);
+      hipLaunchKernelGGL(k_fill_i64, dim3((N + kCcBlock - 1) / kCcBlock), dim3(kCcBlock), 0, h->stream, B[CC_CHANGE].as<i64>(), N, kCcNever);
       HIPCHK(h, hipGetLastError());
       hipLaunchKernelGGL(k_cc_fold, dim3((unsigned)((entries + kCcBlock - 1) / kCcBlock)), dim3(kCcBlock), 0, h->stream, (const i64*)B[CC_EVTIME].as<i64>(),
                          (const u64*)B[CC_EVOFF].as<u64>(), (const u32*)B[CC_EVNODES].as<u32>(), E, (u32)entries, N, B[CC_CHANGE].as<i64>());
@@ -149,7 +134,7 @@ int cns_commit_check(cns_handle* h, const cns_commit_events* ev, const cns_commi
   if (jobs->num_jobs != h->J)
     return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: num_jobs " + std::to_string(jobs->num_jobs) + " is not the last cycle's " + std::to_string(h->J));
   const int rc = commit_impl(h, ev, jobs, out, kernel_ms);
-  if (rc != 0) resvq_drain(h);   // nothing of the call is left in flight, the message survives
+  if (rc != 0) drain(h);   // nothing of the call is left in flight, the message survives
   return rc;
 }
 

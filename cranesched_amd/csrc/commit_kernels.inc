@@ -2,7 +2,7 @@
 // JobScheduler.cpp:1464-1555, for every job of the last cycle at once).  Included by engine.hip; host side: commit_host.inc.
 //
 // A call:
-//   k_cc_fill   change[N] = INT64_MAX                                   (only when the call has node events)
+//   k_fill_i64  change[N] = INT64_MAX                                   (only when the call has node events)
 //   k_cc_fold   one thread per (event, node) entry: change[node] = min(change[node], the event's time) — :1479-1483
 //   k_cc_check  one workgroup per kCcChunk consecutive jobs of the queue, one lane per job: the first failing check in the reference's
 //               order.  The cycle's results are read where they are (start, reason, the node of every placement record).  A job of at
@@ -10,6 +10,8 @@
 //               a time and decides with one ballot.  The code byte is written once per job; counts: a ballot per wave and code, one
 //               atomic per wave and non-empty code.
 // No workgroup waits for another, no LDS; every store is a plain vector store or a returnless vector atomic.
+
+#include "csr_dev.h"
 
 namespace cns {
 
@@ -44,40 +46,14 @@ struct CcParams {
   unsigned long long* counts; // [8]
 };
 
-// the event of flat entry i: the last e with off[e] <= i (off[E] > i; empty events repeat an offset and are skipped)
-__device__ __forceinline__ u32 cc_owner(const u64* __restrict__ off, u32 E, u64 i) {
-  u32 lo = 0, hi = E;
-  while (hi - lo > 1) {
-    const u32 mid = lo + ((hi - lo) >> 1);
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(256) void k_cc_fill(i64* __restrict__ p, u32 n, i64 v) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
-}
-
 __global__ __launch_bounds__(256) void k_cc_fold(const i64* __restrict__ ev_time, const u64* __restrict__ ev_off, const u32* __restrict__ ev_nodes,
                                                  u32 E, u32 entries, u32 N, i64* __restrict__ change) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= entries) return;
   const u32 n = ev_nodes[i];
   if (n >= N) return;                         // (the host refused the call already)
-  const u32 e = cc_owner(ev_off, E, i);
+  const u32 e = csr_owner(ev_off, E, (u64)i);
   (void)__hip_atomic_fetch_min((long long*)&change[n], (long long)ev_time[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// is node n in the ascending list nodes[b, e)?
-__device__ __forceinline__ bool cc_member(const u32* __restrict__ nodes, u64 b, u64 e, u32 n) {
-  while (b < e) {
-    const u64 mid = b + ((e - b) >> 1);
-    const u32 v = nodes[mid];
-    if (v == n) return true;
-    if (v < n) b = mid + 1; else e = mid;
-  }
-  return false;
 }
 
 // one placement record against the job's test.  mode 1: outside every reservation, change[n] < end (:1516-1517).  mode 2: inside an
@@ -85,7 +61,7 @@ __device__ __forceinline__ bool cc_member(const u32* __restrict__ nodes, u64 b, 
 __device__ __forceinline__ bool cc_record_fails(const CcParams& P, u32 mode, u32 n, i64 end, u64 lb, u64 le) {
   if (n == CNS_NODE_NONE) return false;
   if (mode == 1) return n < P.N && P.change[n] < end;
-  return !cc_member(P.ar_nodes, lb, le, n);
+  return !sorted_contains(P.ar_nodes, lb, le, n);
 }
 
 __global__ __launch_bounds__(256) void k_cc_check(const CcParams P) {

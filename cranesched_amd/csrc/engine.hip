@@ -42,6 +42,8 @@
 #include "submit_kernels.inc" // the submit limits over a batch of submissions (include/crane_gpu_submit/submit_limits.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 #include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
+#include "csr_host.inc"        // the CSR rules of the callers' lists: offsets, sorted lists without a repeat (no HIP in there either)
+#include "buf_slots.h"         // the slots of cns_engine's per-feature buffer sets
 
 using namespace cns;
 
@@ -64,6 +66,10 @@ std::string g_create_error;
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap && p) return hipSuccess;
     if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
@@ -82,6 +88,10 @@ struct DevBuf {
 struct PinBuf {
   void* p = nullptr;
   size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { release(); }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap && p) return hipSuccess;
     if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
@@ -153,7 +163,7 @@ struct cns_engine {
   struct ResOff { size_t start, cpu, mem, clo, chi, gres, node, ntasks, reason, c2, c3, total; } ro{};
   bool wide_cores = false;   // a node of the snapshot has a core id above 127: the results carry the core_w2 / core_w3 planes
   // what-if probes against the final state of the last cycle (probe_host.inc): table, results and scratch in buffers of their own
-  DevBuf d_pb[28];
+  DevBuf d_pb[PB_COUNT];
   ResOff pro{};
   u64 pJ = 0, pJg = 0, pplaces = 0;             // probes of the last cns_probe_upload, those that reach a walk, their placement records
   u32 pkmax = 1;                                // ... and their widest node_num
@@ -163,13 +173,13 @@ struct cns_engine {
   bool run_preempt = false;                     // the last successful cycle was such a call (probes are not served behind it)
   double probe_ms = 0.0;
   // reservation what-ifs (resvq_host.inc): per-node tables, queries, event times and results in buffers of their own
-  DevBuf d_rq[32];
+  DevBuf d_rq[RQ_COUNT];
   u32 rq_N = 0;                                 // the node count the tables were built for
   std::vector<u32> rq_rv_cnt;                   // node -> reservations that list it
   bool rq_have = false;
   // the validity check of a batch of submissions (valid_host.inc): the caller's node arrays as cns_set_nodes got them, derived tables,
   // the call's job arrays and results in buffers of their own
-  DevBuf d_vd[28];
+  DevBuf d_vd[VD_COUNT];
   std::vector<i64> vd_cpu;
   std::vector<u64> vd_mem, vd_gres;
   std::vector<uint8_t> vd_unsup;
@@ -177,7 +187,7 @@ struct cns_engine {
   u32 vd_V = 0;                                 // reservations of the device's membership table
   bool vd_tab_have = false, vd_rv_have = false; // the tables derived from the node arrays / from the reservations are built
   // the commit loop's checks behind a cycle (commit_host.inc): the call's events, job arrays and results in buffers of their own
-  DevBuf d_cc[18];
+  DevBuf d_cc[CC_COUNT];
   cns_timing timing{};
   std::string last_kernel;
   i64 last_now = 0;
@@ -212,7 +222,7 @@ struct cns_engine {
   std::set<void*> host_bufs;                    // page-locked host buffers handed out by cns_host_alloc
   bool pre_active = false;                      // the next run is a cycle with preemption (general path of k_select only)
   PreParams pre_params{};
-  DevBuf d_pre[24];
+  DevBuf d_pre[B_COUNT];
   bool lim_have_tables = false, lim_have_jobs = false, lim_have_run = false;
   bool lim_has_upl = false, lim_has_apl = false, lim_has_sel = false, lim_has_skip = false;
   u32 lim_U = 0, lim_UA = 0, lim_A = 0, lim_Q = 0, lim_Pn = 0, lim_base[5] = {0, 0, 0, 0, 0};
@@ -220,7 +230,7 @@ struct cns_engine {
   std::vector<u32> lim_level;
   cns_limit_timing lim_timing{};
   // the submit limits over a batch of submissions (submit_host.inc): tables, the call's job arrays, items and results in buffers of their own
-  DevBuf d_sub[48];
+  DevBuf d_sub[SB_COUNT];
   bool sub_have = false, sub_has_upl = false, sub_has_apl = false, sub_has_uq = false, sub_has_aq = false, sub_has_g = false;
   u32 sub_U = 0, sub_UA = 0, sub_A = 0, sub_Q = 0, sub_Pn = 0, sub_NR = 0, sub_NE = 0, sub_base[5] = {0, 0, 0, 0, 0}, sub_ent[3] = {0, 0, 0};
   u32 sub_max_set = 0, sub_max_cur = 0;         // the largest submit count of the tables as set / as the last call left them
@@ -241,12 +251,22 @@ int fail(cns_engine* h, int code, const std::string& msg) {
       return fail(h, CNS_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e));           \
   } while (0)
 
-template <class T>
-int upload(cns_engine* h, DevBuf& b, const std::vector<T>& v) {
-  HIPCHK(h, b.ensure(v.size() * sizeof(T)));
-  if (!v.empty()) HIPCHK(h, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
+// after a failure nothing of the call is left in flight, and the message survives
+void drain(cns_engine* h) {
+  const std::string keep = h->err;
+  if (hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
+  (void)hipGetLastError();
+  h->err = keep;
+}
+
+// room for `bytes` in b, then the copy on the engine's stream (nothing to copy: a null source or no bytes)
+int stage(cns_engine* h, DevBuf& b, const void* src, size_t bytes) {
+  HIPCHK(h, b.ensure(bytes));
+  if (bytes && src) HIPCHK(h, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, h->stream));
   return 0;
 }
+template <class T>
+int upload(cns_engine* h, DevBuf& b, const std::vector<T>& v) { return stage(h, b, v.data(), v.size() * sizeof(T)); }
 
 size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
 
@@ -689,35 +709,14 @@ int cns_create(const cns_config* cfg, cns_handle** out) {
 void cns_destroy(cns_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  for (DevBuf* b : {&h->d_part_off, &h->d_slot_node, &h->d_type_total,
-                    &h->d_blocks, &h->d_cost, &h->d_fcpu, &h->d_fmem, &h->d_fcnt, &h->d_dipt, &h->d_dipcm, &h->d_dipg, &h->d_rn_off,
-                    &h->d_rn_end, &h->d_rn_res, &h->d_heap, &h->d_bfj, &h->d_gupd, &h->d_fault, &h->d_pj_off, &h->d_jobs,
-                    &h->d_incl, &h->d_excl, &h->d_reason_init, &h->d_results, &h->d_params, &h->d_prof, &h->d_wide, &h->d_slot_total,
-                    &h->d_slot_end, &h->d_slot_type, &h->d_rv_off, &h->d_rv_start, &h->d_rv_end, &h->d_rv_res,
-                    &h->d_first_resv, &h->d_resv_se})
-    b->release();
-  for (DevBuf* b : {&h->d_slot_block, &h->d_sib_off, &h->d_sib, &h->d_type_tag, &h->d_jtag, &h->d_params2, &h->d_pmap_a, &h->d_pmap_b, &h->d_wide_last, &h->d_params3, &h->d_pmap_c, &h->d_wide_mem, &h->d_giant, &h->d_flen, &h->d_tag_off, &h->d_tag_base}) b->release();
-  for (PinBuf* b : {&h->h_place, &h->h_grouped, &h->h_reason, &h->h_jtag}) b->release();
   for (void* p : h->host_bufs) (void)hipHostFree(p);   // cns_host_alloc
   h->host_bufs.clear();
-  for (DevBuf& b : h->d_prio) b.release();
-  for (DevBuf& b : h->d_lim) b.release();
-  for (DevBuf& b : h->d_raw) b.release();
-  for (DevBuf& b : h->d_limpar) b.release();
-  for (DevBuf& b : h->d_step) b.release();
-  for (DevBuf& b : h->d_pre) b.release();
-  for (DevBuf& b : h->d_pb) b.release();
-  for (DevBuf& b : h->d_rq) b.release();
-  for (DevBuf& b : h->d_vd) b.release();
-  for (DevBuf& b : h->d_cc) b.release();
-  for (DevBuf& b : h->d_sub) b.release();
-  h->d_gather.release();
   if (h->comm) (void)ncclCommDestroy((ncclComm_t)h->comm);
   for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : h->ev2) if (ev) (void)hipEventDestroy(ev);
   if (h->stream2) (void)hipStreamDestroy(h->stream2);
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;   // every DevBuf and PinBuf releases itself
 }
 
 static void valid_keep_nodes(cns_handle* h, const cns_node_soa* nd);   // valid_host.inc
@@ -1061,33 +1060,28 @@ static int upload_jobs_impl(cns_handle* h, const cns_job_soa* jb) {
   // The caller's arrays go to the device as they are (k_pack_jobs builds the 32-dword job records there); from page-locked arrays
   // (cns_host_alloc) these are DMA transfers the thread does not wait for, and both host passes below run in their shadow.  A queue
   // that fails validation returns only after the transfers have drained: the caller owns its arrays again when the call is back.
-  // (offsets without their node list are reported below, after the checks that come first: raw() issues no copy from a null source)
-  auto raw = [&](DevBuf& d, const void* src, size_t bytes) -> int {
-    HIPCHK(h, d.ensure(bytes));
-    if (src && bytes) HIPCHK(h, hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    return 0;
-  };
+  // (offsets without their node list are reported below, after the checks that come first: stage() issues no copy from a null source)
   DevBuf* rb_ = h->d_raw;  // 0 L, 1 ncpu, 2 nmem, 3 tcpu, 4 tmem, 5 k, 6 ntasks, 7 tmin, 8 tmax, 9 excl, 10 gtot, 11 gspec, 12 incl_off,
                            // 13 excl_off, 14 place_off, 15 grouped
-  if (int rc = raw(rb_[0], jb->time_limit_sec, J * 8)) return rc;
-  if (jb->node_cpu_raw) { if (int rc = raw(rb_[1], jb->node_cpu_raw, J * 8)) return rc; }
-  if (int rc = raw(rb_[2], jb->node_mem, J * 8)) return rc;
-  if (int rc = raw(rb_[3], jb->task_cpu_raw, J * 8)) return rc;
-  if (int rc = raw(rb_[4], jb->task_mem, J * 8)) return rc;
-  if (int rc = raw(rb_[5], jb->node_num, J * 4)) return rc;
-  if (int rc = raw(rb_[6], jb->ntasks, J * 4)) return rc;
-  if (int rc = raw(rb_[7], jb->ntasks_per_node_min, J * 4)) return rc;
-  if (int rc = raw(rb_[8], jb->ntasks_per_node_max, J * 4)) return rc;
-  if (jb->exclusive) { if (int rc = raw(rb_[9], jb->exclusive, J)) return rc; }
-  if (jb->gres_total) { if (int rc = raw(rb_[10], jb->gres_total, J * CNS_MAX_GRES_NAMES)) return rc; }
-  if (jb->gres_spec) { if (int rc = raw(rb_[11], jb->gres_spec, J * CNS_MAX_GRES_CLASSES)) return rc; }
-  if (jb->incl_offsets) { if (int rc = raw(rb_[12], jb->incl_offsets, (J + 1) * 8)) return rc; }
-  if (jb->excl_offsets) { if (int rc = raw(rb_[13], jb->excl_offsets, (J + 1) * 8)) return rc; }
+  if (int rc = stage(h, rb_[0], jb->time_limit_sec, J * 8)) return rc;
+  if (jb->node_cpu_raw) { if (int rc = stage(h, rb_[1], jb->node_cpu_raw, J * 8)) return rc; }
+  if (int rc = stage(h, rb_[2], jb->node_mem, J * 8)) return rc;
+  if (int rc = stage(h, rb_[3], jb->task_cpu_raw, J * 8)) return rc;
+  if (int rc = stage(h, rb_[4], jb->task_mem, J * 8)) return rc;
+  if (int rc = stage(h, rb_[5], jb->node_num, J * 4)) return rc;
+  if (int rc = stage(h, rb_[6], jb->ntasks, J * 4)) return rc;
+  if (int rc = stage(h, rb_[7], jb->ntasks_per_node_min, J * 4)) return rc;
+  if (int rc = stage(h, rb_[8], jb->ntasks_per_node_max, J * 4)) return rc;
+  if (jb->exclusive) { if (int rc = stage(h, rb_[9], jb->exclusive, J)) return rc; }
+  if (jb->gres_total) { if (int rc = stage(h, rb_[10], jb->gres_total, J * CNS_MAX_GRES_NAMES)) return rc; }
+  if (jb->gres_spec) { if (int rc = stage(h, rb_[11], jb->gres_spec, J * CNS_MAX_GRES_CLASSES)) return rc; }
+  if (jb->incl_offsets) { if (int rc = stage(h, rb_[12], jb->incl_offsets, (J + 1) * 8)) return rc; }
+  if (jb->excl_offsets) { if (int rc = stage(h, rb_[13], jb->excl_offsets, (J + 1) * 8)) return rc; }
   const u64 n_incl = jb->incl_offsets ? jb->incl_offsets[J] : 0, n_excl = jb->excl_offsets ? jb->excl_offsets[J] : 0;
   HIPCHK(h, h->d_incl.ensure(std::max<u64>(n_incl, 1) * 4));
   HIPCHK(h, h->d_excl.ensure(std::max<u64>(n_excl, 1) * 4));
-  if (int rc = raw(h->d_incl, jb->incl_nodes, n_incl * 4)) return rc;
-  if (int rc = raw(h->d_excl, jb->excl_nodes, n_excl * 4)) return rc;
+  if (int rc = stage(h, h->d_incl, jb->incl_nodes, n_incl * 4)) return rc;
+  if (int rc = stage(h, h->d_excl, jb->excl_nodes, n_excl * 4)) return rc;
   // BasicPriority (JobScheduler.h:185-200) + per-job pre-checks of the ordered loop (cpp:6744-6761): jobs_host.inc, pass 1 — on a few host threads
   namespace jh = cns_jobs_host;
   HIPCHK(h, h->h_reason.ensure(std::max<u64>(J, 1)));
@@ -1122,9 +1116,9 @@ static int upload_jobs_impl(cns_handle* h, const cns_job_soa* jb) {
   jh::pass2(jb, O, chunks);
   if (J == 0) { O.reason[0] = CNS_REASON_NONE; if (O.jtag) O.jtag[0] = 0; }   // (the one-element stand-ins of an empty queue)
   if (Jg == 0) O.grouped[0] = 0;
-  if (int rc = raw(rb_[14], h->h_place.p, (J + 1) * 8)) return rc;
-  if (int rc = raw(rb_[15], h->h_grouped.p, std::max<u64>(Jg, 1) * 4)) return rc;
-  if (h->shared) { if (int rc = raw(h->d_jtag, h->h_jtag.p, std::max<u64>(J, 1))) return rc; }
+  if (int rc = stage(h, rb_[14], h->h_place.p, (J + 1) * 8)) return rc;
+  if (int rc = stage(h, rb_[15], h->h_grouped.p, std::max<u64>(Jg, 1) * 4)) return rc;
+  if (h->shared) { if (int rc = stage(h, h->d_jtag, h->h_jtag.p, std::max<u64>(J, 1))) return rc; }
   HIPCHK(h, h->d_jobs.ensure((size_t)std::max<u64>(Jg, 1) * kJobRecDwords * 4));
   if (Jg) {
     PackParams K{};
@@ -1142,7 +1136,7 @@ static int upload_jobs_impl(cns_handle* h, const cns_job_soa* jb) {
   }
 
   if (int rc = upload(h, h->d_pj_off, pj_off)) return rc;
-  if (int rc = raw(h->d_reason_init, h->h_reason.p, std::max<u64>(J, 1))) return rc;
+  if (int rc = stage(h, h->d_reason_init, h->h_reason.p, std::max<u64>(J, 1))) return rc;
   // results: one contiguous HBM buffer (also what an RCCL allgather ships)
   cns_engine::ResOff& r = h->ro;
   size_t ro = 0;
@@ -1164,10 +1158,6 @@ static int upload_jobs_impl(cns_handle* h, const cns_job_soa* jb) {
   h->have_jobs = true;
   return CNS_OK;
 }
-
-// device buffers of a cycle with preemption (cns_engine::d_pre)
-enum { B_QPOFF, B_QP, B_PJQOS, B_PJQP, B_PJPRIO, B_PJREC0, B_PJK, B_PJEND, B_RNJOB, B_ENTSLOT, B_ENTGONE, B_RJQOS, B_RJQP,
-       B_RJSTART, B_RJEND, B_RJPRE, B_RJOFF, B_RJENT, B_HEAD, B_RECNEXT, B_RECORIG, B_RECSLOT, B_RECGONE, B_MISC };
 
 // One pass of the cycle on the device.  *fault_code: the device fault it ended with (0: none).
 // `protocol_off`: the retry — no kernel whose workgroups wait for each other.

@@ -184,7 +184,7 @@ int cns_group_create(const cns_config* cfg, const int32_t* devices, uint32_t n, 
   *out = nullptr;
   cns_group* g = new (std::nothrow) cns_group;
   if (!g) return gfail(nullptr, CNS_ERR_HIP, "cns_group_create: out of memory");
-  g->eng.assign(n, nullptr); g->d_gather.resize(n); g->shard.resize(n);
+  g->eng.assign(n, nullptr); g->d_gather = std::vector<DevBuf>(n); g->shard.resize(n);
   g->devices.assign(devices, devices + n);
   std::set<int> seen(g->devices.begin(), g->devices.end());
   g->distinct = seen.size() == n;

@@ -176,21 +176,16 @@ int cns_upload_limit_jobs(cns_handle* h, const cns_limit_job_soa* jb) {
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
   DevBuf* b = h->d_lim;  // 10 sel, 11 user, 12 ua, 13 account, 14 qos, 15 part, 16 tl, 17 skip, 18 place_off, 19.. scratch
-  auto up = [&](DevBuf& d, const void* src, size_t bytes) -> int {
-    HIPCHK(h, d.ensure(bytes));
-    if (bytes) HIPCHK(h, hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    return 0;
-  };
   // job keys of skipped jobs may be anything: they are never dereferenced on the device
-  if (jb->select_index) { if (int rc = up(b[10], jb->select_index, J * 8)) return rc; }
-  if (int rc = up(b[11], jb->user, J * 4)) return rc;
-  if (int rc = up(b[12], jb->user_acct, J * 4)) return rc;
-  if (int rc = up(b[13], jb->account, J * 4)) return rc;
-  if (int rc = up(b[14], jb->qos, J * 4)) return rc;
-  if (int rc = up(b[15], jb->partition, J * 4)) return rc;
-  if (int rc = up(b[16], jb->time_limit_sec, J * 8)) return rc;
-  if (jb->skip) { if (int rc = up(b[17], jb->skip, J)) return rc; }
-  if (int rc = up(b[18], h->place_off, h->place_off ? (size_t)(h->J + 1) * 8 : 0)) return rc;
+  if (jb->select_index) { if (int rc = stage(h, b[10], jb->select_index, J * 8)) return rc; }
+  if (int rc = stage(h, b[11], jb->user, J * 4)) return rc;
+  if (int rc = stage(h, b[12], jb->user_acct, J * 4)) return rc;
+  if (int rc = stage(h, b[13], jb->account, J * 4)) return rc;
+  if (int rc = stage(h, b[14], jb->qos, J * 4)) return rc;
+  if (int rc = stage(h, b[15], jb->partition, J * 4)) return rc;
+  if (int rc = stage(h, b[16], jb->time_limit_sec, J * 8)) return rc;
+  if (jb->skip) { if (int rc = stage(h, b[17], jb->skip, J)) return rc; }
+  if (int rc = stage(h, b[18], h->place_off, h->place_off ? (size_t)(h->J + 1) * 8 : 0)) return rc;
   h->lim_has_sel = jb->select_index != nullptr;
   h->lim_has_skip = jb->skip != nullptr;
   const u64 nb = (J + 255) / 256, Jc = std::max<u64>(J, 1);

@@ -40,33 +40,28 @@ int cns_priority_order(cns_handle* h, int64_t now_sec, const cns_priority_config
   }
 
   // ---- upload ----
-  auto up = [&](DevBuf& b, const void* src, size_t bytes) -> int {
-    HIPCHK(h, b.ensure(bytes));
-    if (bytes) HIPCHK(h, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    return 0;
-  };
   DevBuf* pb = h->d_prio;  // 0..7 pending, 8..14 running, 15 acc_off, 16 acc_jobs, 17 present, 18 bounds, 19 acc_val,
                            // 20 prio, 21/22 keys ping-pong, 23/24 vals ping-pong, 25 hist
-  if (int rc = up(pb[0], pd->submit_sec, (size_t)J * 8)) return rc;
-  if (int rc = up(pb[1], pd->qos_priority, (size_t)J * 4)) return rc;
-  if (int rc = up(pb[2], pd->partition_priority, (size_t)J * 4)) return rc;
-  if (int rc = up(pb[3], pd->node_num, (size_t)J * 4)) return rc;
-  if (int rc = up(pb[4], pd->total_cpu_raw, (size_t)J * 8)) return rc;
-  if (int rc = up(pb[5], pd->total_mem, (size_t)J * 8)) return rc;
-  if (int rc = up(pb[6], pd->account, (size_t)J * 4)) return rc;
-  if (pd->cached_priority) { if (int rc = up(pb[7], pd->cached_priority, (size_t)J * 8)) return rc; }
+  if (int rc = stage(h, pb[0], pd->submit_sec, (size_t)J * 8)) return rc;
+  if (int rc = stage(h, pb[1], pd->qos_priority, (size_t)J * 4)) return rc;
+  if (int rc = stage(h, pb[2], pd->partition_priority, (size_t)J * 4)) return rc;
+  if (int rc = stage(h, pb[3], pd->node_num, (size_t)J * 4)) return rc;
+  if (int rc = stage(h, pb[4], pd->total_cpu_raw, (size_t)J * 8)) return rc;
+  if (int rc = stage(h, pb[5], pd->total_mem, (size_t)J * 8)) return rc;
+  if (int rc = stage(h, pb[6], pd->account, (size_t)J * 4)) return rc;
+  if (pd->cached_priority) { if (int rc = stage(h, pb[7], pd->cached_priority, (size_t)J * 8)) return rc; }
   if (R) {
-    if (int rc = up(pb[8], rn->start_sec, (size_t)R * 8)) return rc;
-    if (int rc = up(pb[9], rn->qos_priority, (size_t)R * 4)) return rc;
-    if (int rc = up(pb[10], rn->partition_priority, (size_t)R * 4)) return rc;
-    if (int rc = up(pb[11], rn->node_num, (size_t)R * 4)) return rc;
-    if (int rc = up(pb[12], rn->alloc_cpu_raw, (size_t)R * 8)) return rc;
-    if (int rc = up(pb[13], rn->alloc_mem, (size_t)R * 8)) return rc;
-    if (int rc = up(pb[14], rn->account, (size_t)R * 4)) return rc;
+    if (int rc = stage(h, pb[8], rn->start_sec, (size_t)R * 8)) return rc;
+    if (int rc = stage(h, pb[9], rn->qos_priority, (size_t)R * 4)) return rc;
+    if (int rc = stage(h, pb[10], rn->partition_priority, (size_t)R * 4)) return rc;
+    if (int rc = stage(h, pb[11], rn->node_num, (size_t)R * 4)) return rc;
+    if (int rc = stage(h, pb[12], rn->alloc_cpu_raw, (size_t)R * 8)) return rc;
+    if (int rc = stage(h, pb[13], rn->alloc_mem, (size_t)R * 8)) return rc;
+    if (int rc = stage(h, pb[14], rn->account, (size_t)R * 4)) return rc;
   }
-  if (int rc = up(pb[15], acc_off.data(), acc_off.size() * 4)) return rc;
-  if (int rc = up(pb[16], acc_jobs.data(), (size_t)R * 4)) return rc;
-  if (int rc = up(pb[17], present.data(), present.size())) return rc;
+  if (int rc = stage(h, pb[15], acc_off.data(), acc_off.size() * 4)) return rc;
+  if (int rc = stage(h, pb[16], acc_jobs.data(), (size_t)R * 4)) return rc;
+  if (int rc = stage(h, pb[17], present.data(), present.size())) return rc;
   PrioBounds B0{};
   B0.age_max = 0; B0.age_min = ~0ull; B0.mem_max = 0; B0.mem_min = ~0ull;
   B0.cpus_max_bits = 0;  // bits of 0.0
@@ -76,7 +71,7 @@ int cns_priority_order(cns_handle* h, int64_t now_sec, const cns_priority_config
   }
   B0.sv_max = 0.0; B0.sv_min = 4294967295.0;
   B0.qos_max = 0; B0.qos_min = ~0u; B0.part_max = 0; B0.part_min = ~0u; B0.nn_max = 0; B0.nn_min = ~0u;
-  if (int rc = up(pb[18], &B0, sizeof B0)) return rc;
+  if (int rc = stage(h, pb[18], &B0, sizeof B0)) return rc;
   HIPCHK(h, pb[19].ensure((size_t)std::max<u32>(A, 1) * 8));
   HIPCHK(h, pb[20].ensure((size_t)J * 8));
   HIPCHK(h, pb[21].ensure((size_t)J * 8));

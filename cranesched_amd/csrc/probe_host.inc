@@ -4,11 +4,6 @@
 // (probe_kernel.inc).  Everything a probe call writes on the device lies in buffers of its own (cns_engine::d_pb): the cycle's job
 // table, result buffer, fault word and timing are not touched.  No CPU fallback.
 
-// cns_engine::d_pb
-enum { PB_RAW0 = 0 /* .. 15: the caller's arrays, as cns_engine::d_raw */, PB_JOBS = 16, PB_INCL, PB_EXCL, PB_REASON, PB_RESULTS, PB_PARAMS, PB_PART, PB_CTR,
-       PB_HEAP, PB_JTAG, PB_FAULT, PB_COUNT };
-static_assert(PB_COUNT <= sizeof(cns_engine::d_pb) / sizeof(DevBuf), "cns_engine::d_pb holds every probe buffer");
-
 static int probe_state(cns_handle* h, const char* who) {
   if (!h->have_run) return fail(h, CNS_ERR_STATE, std::string(who) + " before a successful cycle (cns_select / cns_run_resident), or after the snapshot or the queue changed");
   if (h->run_preempt)
@@ -24,32 +19,27 @@ static int probe_upload_impl(cns_handle* h, const cns_job_soa* jb) {
   if (J > 0xFFFFFFF0ull) return fail(h, CNS_ERR_UNSUPPORTED, "more than 2^32-16 probes");
   HIPCHK(h, hipSetDevice(h->device));
   DevBuf* B = h->d_pb;
-  auto raw = [&](DevBuf& d, const void* src, size_t bytes) -> int {
-    HIPCHK(h, d.ensure(bytes));
-    if (src && bytes) HIPCHK(h, hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    return 0;
-  };
   DevBuf* rb_ = B + PB_RAW0;
-  if (int rc = raw(rb_[0], jb->time_limit_sec, J * 8)) return rc;
-  if (jb->node_cpu_raw) { if (int rc = raw(rb_[1], jb->node_cpu_raw, J * 8)) return rc; }
-  if (int rc = raw(rb_[2], jb->node_mem, J * 8)) return rc;
-  if (int rc = raw(rb_[3], jb->task_cpu_raw, J * 8)) return rc;
-  if (int rc = raw(rb_[4], jb->task_mem, J * 8)) return rc;
-  if (int rc = raw(rb_[5], jb->node_num, J * 4)) return rc;
-  if (int rc = raw(rb_[6], jb->ntasks, J * 4)) return rc;
-  if (int rc = raw(rb_[7], jb->ntasks_per_node_min, J * 4)) return rc;
-  if (int rc = raw(rb_[8], jb->ntasks_per_node_max, J * 4)) return rc;
-  if (jb->exclusive) { if (int rc = raw(rb_[9], jb->exclusive, J)) return rc; }
-  if (jb->gres_total) { if (int rc = raw(rb_[10], jb->gres_total, J * CNS_MAX_GRES_NAMES)) return rc; }
-  if (jb->gres_spec) { if (int rc = raw(rb_[11], jb->gres_spec, J * CNS_MAX_GRES_CLASSES)) return rc; }
-  if (jb->incl_offsets) { if (int rc = raw(rb_[12], jb->incl_offsets, (J + 1) * 8)) return rc; }
-  if (jb->excl_offsets) { if (int rc = raw(rb_[13], jb->excl_offsets, (J + 1) * 8)) return rc; }
+  if (int rc = stage(h, rb_[0], jb->time_limit_sec, J * 8)) return rc;
+  if (jb->node_cpu_raw) { if (int rc = stage(h, rb_[1], jb->node_cpu_raw, J * 8)) return rc; }
+  if (int rc = stage(h, rb_[2], jb->node_mem, J * 8)) return rc;
+  if (int rc = stage(h, rb_[3], jb->task_cpu_raw, J * 8)) return rc;
+  if (int rc = stage(h, rb_[4], jb->task_mem, J * 8)) return rc;
+  if (int rc = stage(h, rb_[5], jb->node_num, J * 4)) return rc;
+  if (int rc = stage(h, rb_[6], jb->ntasks, J * 4)) return rc;
+  if (int rc = stage(h, rb_[7], jb->ntasks_per_node_min, J * 4)) return rc;
+  if (int rc = stage(h, rb_[8], jb->ntasks_per_node_max, J * 4)) return rc;
+  if (jb->exclusive) { if (int rc = stage(h, rb_[9], jb->exclusive, J)) return rc; }
+  if (jb->gres_total) { if (int rc = stage(h, rb_[10], jb->gres_total, J * CNS_MAX_GRES_NAMES)) return rc; }
+  if (jb->gres_spec) { if (int rc = stage(h, rb_[11], jb->gres_spec, J * CNS_MAX_GRES_CLASSES)) return rc; }
+  if (jb->incl_offsets) { if (int rc = stage(h, rb_[12], jb->incl_offsets, (J + 1) * 8)) return rc; }
+  if (jb->excl_offsets) { if (int rc = stage(h, rb_[13], jb->excl_offsets, (J + 1) * 8)) return rc; }
   const u64 n_incl = jb->incl_offsets ? jb->incl_offsets[J] : 0, n_excl = jb->excl_offsets ? jb->excl_offsets[J] : 0;
   if ((n_incl && !jb->incl_nodes) || (n_excl && !jb->excl_nodes)) return fail(h, CNS_ERR_INVALID_ARG, "cns_probe_upload: include / exclude offsets without node lists");
   HIPCHK(h, B[PB_INCL].ensure(std::max<u64>(n_incl, 1) * 4));
   HIPCHK(h, B[PB_EXCL].ensure(std::max<u64>(n_excl, 1) * 4));
-  if (int rc = raw(B[PB_INCL], jb->incl_nodes, n_incl * 4)) return rc;
-  if (int rc = raw(B[PB_EXCL], jb->excl_nodes, n_excl * 4)) return rc;
+  if (int rc = stage(h, B[PB_INCL], jb->incl_nodes, n_incl * 4)) return rc;
+  if (int rc = stage(h, B[PB_EXCL], jb->excl_nodes, n_excl * 4)) return rc;
   // the pre-checks and the routing of the ordered loop (JobScheduler.cpp:6744-6761), as for the cycle's queue — but no probe is cut
   namespace jh = cns_jobs_host;
   std::vector<uint8_t> reason(std::max<u64>(J, 1), 0), jtag(std::max<u64>(J, 1), 0);
@@ -76,11 +66,11 @@ static int probe_upload_impl(cns_handle* h, const cns_job_soa* jb) {
   std::vector<u32> part_of((size_t)std::max<u64>(Jg, 1), 0);
   u32 kmax = 1;
   for (u64 i = 0; i < Jg; ++i) { part_of[(size_t)i] = job_part[grouped[(size_t)i]]; kmax = std::max(kmax, jb->node_num[grouped[(size_t)i]]); }
-  if (int rc = raw(rb_[14], place_off.data(), (J + 1) * 8)) return rc;
-  if (int rc = raw(rb_[15], grouped.data(), grouped.size() * 4)) return rc;
-  if (h->shared) { if (int rc = raw(B[PB_JTAG], jtag.data(), jtag.size())) return rc; }
-  if (int rc = raw(B[PB_PART], part_of.data(), part_of.size() * 4)) return rc;
-  if (int rc = raw(B[PB_REASON], reason.data(), reason.size())) return rc;
+  if (int rc = stage(h, rb_[14], place_off.data(), (J + 1) * 8)) return rc;
+  if (int rc = stage(h, rb_[15], grouped.data(), grouped.size() * 4)) return rc;
+  if (h->shared) { if (int rc = stage(h, B[PB_JTAG], jtag.data(), jtag.size())) return rc; }
+  if (int rc = stage(h, B[PB_PART], part_of.data(), part_of.size() * 4)) return rc;
+  if (int rc = stage(h, B[PB_REASON], reason.data(), reason.size())) return rc;
   HIPCHK(h, B[PB_JOBS].ensure((size_t)std::max<u64>(Jg, 1) * kJobRecDwords * 4));
   if (Jg) {
     PackParams K{};
@@ -120,12 +110,7 @@ int cns_probe_upload(cns_handle* h, const cns_job_soa* jb) {
   if (int rc = probe_state(h, "cns_probe_upload")) return rc;
   h->have_probes = h->probes_answered = false;
   const int rc = probe_upload_impl(h, jb);
-  if (rc != 0) {
-    const std::string keep = h->err;
-    if (hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
-    (void)hipGetLastError();
-    h->err = keep;
-  }
+  if (rc != 0) drain(h);
   return rc;
 }
 

@@ -4,13 +4,6 @@
 // lives in cns_engine::d_rq: no flag and no buffer of the cycle or of the probes is read or written, only the node count of cns_set_nodes
 // (cns_engine::N together with have_nodes).  No CPU fallback.
 
-// cns_engine::d_rq
-enum { RQ_LATEST = 0, RQ_RVOFF, RQ_RVST, RQ_RVED, RQ_RAW_END, RQ_RAW_OFF, RQ_RAW_NODE,                              // state
-       RQ_START, RQ_DUR, RQ_K, RQ_FLAGS, RQ_CANDOFF, RQ_CAND, RQ_CHOFF,                                              // queries
-       RQ_EVOFF, RQ_SEGOFF, RQ_KA, RQ_KB, RQ_KC, RQ_VA, RQ_VB, RQ_SORTED, RQ_HIST, RQ_BEST,                              // earliest mode
-       RQ_CODE, RQ_CHOSEN, RQ_STATUS, RQ_OSTART, RQ_NFREE, RQ_COUNT };                                               // results
-static_assert(RQ_COUNT <= sizeof(cns_engine::d_rq) / sizeof(DevBuf), "cns_engine::d_rq holds every buffer of the reservation what-ifs");
-
 constexpr u64 kRqMaxCandidates = 0x7FFFFFFFull;   // of one call
 constexpr u64 kRqMaxIntervals = 1ull << 26;       // of one call (DESIGN.md 8): two event times each, 40 bytes per time while they are sorted: 5 GiB at the cap
 
@@ -65,7 +58,7 @@ static int resvq_set_state_impl(cns_handle* h, const cns_running_soa* rn, const 
   if (int rc = upload(h, B[RQ_RVST], st)) return rc;
   if (int rc = upload(h, B[RQ_RVED], ed)) return rc;
   HIPCHK(h, B[RQ_LATEST].ensure((size_t)N * 8));
-  hipLaunchKernelGGL(k_rq_fill, dim3((N + 255) / 256), dim3(256), 0, h->stream, B[RQ_LATEST].as<i64>(), N, (i64)INT64_MIN);
+  hipLaunchKernelGGL(k_fill_i64, dim3((N + 255) / 256), dim3(256), 0, h->stream, B[RQ_LATEST].as<i64>(), N, (i64)INT64_MIN);
   HIPCHK(h, hipGetLastError());
   if (RA) {
     HIPCHK(h, B[RQ_RAW_END].ensure((size_t)RJ * 8));
@@ -85,20 +78,12 @@ static int resvq_set_state_impl(cns_handle* h, const cns_running_soa* rn, const 
   return CNS_OK;
 }
 
-// after a failure nothing of the call is left in flight, and the message survives (as cns_probe_upload)
-static void resvq_drain(cns_handle* h) {
-  const std::string keep = h->err;
-  if (hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
-  (void)hipGetLastError();
-  h->err = keep;
-}
-
 int cns_resvq_set_state(cns_handle* h, const cns_running_soa* running, const cns_resv_soa* resv) {
   if (!h) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: null handle");
   if (!h->have_nodes) return fail(h, CNS_ERR_STATE, "cns_resvq_set_state before cns_set_nodes");
   h->rq_have = false;
   const int rc = resvq_set_state_impl(h, running, resv);
-  if (rc != 0) resvq_drain(h);
+  if (rc != 0) drain(h);
   return rc;
 }
 
@@ -107,9 +92,9 @@ static int resvq_run_impl(cns_handle* h, i64 now, const cns_resvq_soa* q, cns_re
   if (!q->start_sec || !q->duration_sec || !q->node_num || !q->cand_offsets) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_run: missing array");
   if (Q64 > 0x7FFFFFFFull) return fail(h, CNS_ERR_UNSUPPORTED, "cns_resvq_run: more than 2^31-1 queries");
   const u32 Q = (u32)Q64, N = h->rq_N;
-  if (q->cand_offsets[0] != 0) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_run: cand_offsets does not start at 0");
-  for (u32 i = 0; i < Q; ++i)
-    if (q->cand_offsets[i] > q->cand_offsets[i + 1]) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_run: cand_offsets decrease");
+  const auto co = cns_csr::check_offsets(q->cand_offsets, Q);
+  if (co.what == cns_csr::Offsets::FirstNot0) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_run: cand_offsets does not start at 0");
+  if (co.what == cns_csr::Offsets::Decreases) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_run: cand_offsets decrease");
   const u64 L64 = q->cand_offsets[Q];
   if (L64 > kRqMaxCandidates) return fail(h, CNS_ERR_UNSUPPORTED, "cns_resvq_run: more than 2^31-1 candidates in one call");
   const u32 L = (u32)L64;
@@ -158,18 +143,13 @@ static int resvq_run_impl(cns_handle* h, i64 now, const cns_resvq_soa* q, cns_re
 
   HIPCHK(h, hipSetDevice(h->device));
   DevBuf* B = h->d_rq;
-  auto up = [&](int b, const void* src, size_t bytes) -> int {
-    HIPCHK(h, B[b].ensure(bytes));
-    if (bytes) HIPCHK(h, hipMemcpyAsync(B[b].p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    return 0;
-  };
-  if (int rc = up(RQ_START, q->start_sec, (size_t)Q * 8)) return rc;
-  if (int rc = up(RQ_DUR, q->duration_sec, (size_t)Q * 8)) return rc;
-  if (int rc = up(RQ_K, kq.data(), (size_t)Q * 4)) return rc;
-  if (int rc = up(RQ_FLAGS, flags.data(), (size_t)Q * 4)) return rc;
-  if (int rc = up(RQ_CANDOFF, coff.data(), ((size_t)Q + 1) * 4)) return rc;
-  if (int rc = up(RQ_CAND, q->cand_nodes, (size_t)L * 4)) return rc;
-  if (int rc = up(RQ_CHOFF, choff.data(), ((size_t)Q + 1) * 4)) return rc;
+  if (int rc = stage(h, B[RQ_START], q->start_sec, (size_t)Q * 8)) return rc;
+  if (int rc = stage(h, B[RQ_DUR], q->duration_sec, (size_t)Q * 8)) return rc;
+  if (int rc = stage(h, B[RQ_K], kq.data(), (size_t)Q * 4)) return rc;
+  if (int rc = stage(h, B[RQ_FLAGS], flags.data(), (size_t)Q * 4)) return rc;
+  if (int rc = stage(h, B[RQ_CANDOFF], coff.data(), ((size_t)Q + 1) * 4)) return rc;
+  if (int rc = stage(h, B[RQ_CAND], q->cand_nodes, (size_t)L * 4)) return rc;
+  if (int rc = stage(h, B[RQ_CHOFF], choff.data(), ((size_t)Q + 1) * 4)) return rc;
   HIPCHK(h, B[RQ_BEST].ensure((size_t)Q * 8));
   HIPCHK(h, B[RQ_CODE].ensure(L));
   HIPCHK(h, B[RQ_CHOSEN].ensure((size_t)chosen_slots * 4));
@@ -177,8 +157,8 @@ static int resvq_run_impl(cns_handle* h, i64 now, const cns_resvq_soa* q, cns_re
   HIPCHK(h, B[RQ_OSTART].ensure((size_t)Q * 8));
   HIPCHK(h, B[RQ_NFREE].ensure((size_t)Q * 4));
   if (EV) {
-    if (int rc = up(RQ_EVOFF, ev_off.data(), ((size_t)L + 1) * 4)) return rc;
-    if (int rc = up(RQ_SEGOFF, seg_off.data(), ((size_t)Q + 1) * 4)) return rc;
+    if (int rc = stage(h, B[RQ_EVOFF], ev_off.data(), ((size_t)L + 1) * 4)) return rc;
+    if (int rc = stage(h, B[RQ_SEGOFF], seg_off.data(), ((size_t)Q + 1) * 4)) return rc;
     for (int b : {RQ_KA, RQ_KB, RQ_KC, RQ_SORTED}) HIPCHK(h, B[b].ensure((size_t)EV2 * 8));
     for (int b : {RQ_VA, RQ_VB}) HIPCHK(h, B[b].ensure((size_t)EV2 * 4));
     HIPCHK(h, B[RQ_HIST].ensure(((size_t)256 * ntiles + 256) * 4));
@@ -195,7 +175,7 @@ static int resvq_run_impl(cns_handle* h, i64 now, const cns_resvq_soa* q, cns_re
   const dim3 blk(kRqBlock);
   auto grid = [](u64 n) { return dim3((unsigned)((n + kRqBlock - 1) / kRqBlock)); };
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  hipLaunchKernelGGL(k_rq_fill, grid(Q), blk, 0, h->stream, P.best, Q, kRqNever);
+  hipLaunchKernelGGL(k_fill_i64, grid(Q), blk, 0, h->stream, P.best, Q, kRqNever);
   HIPCHK(h, hipGetLastError());
   if (EV) {
     hipLaunchKernelGGL(k_rq_emit, grid(L), blk, 0, h->stream, P);
@@ -265,6 +245,6 @@ int cns_resvq_run(cns_handle* h, int64_t now_sec, const cns_resvq_soa* q, cns_re
   if (q->num_queries == 0) return CNS_OK;   // nothing asked, nothing written
   if (!out) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_run: null result");
   const int rc = resvq_run_impl(h, now_sec, q, out, kernel_ms);
-  if (rc != 0) resvq_drain(h);
+  if (rc != 0) drain(h);
   return rc;
 }

@@ -13,6 +13,8 @@
 //                        k_rq_pick      one workgroup per query: the first k free candidates in list order, num_free, status
 // No workgroup waits for another; every store is a plain vector store or a returnless vector atomic.
 
+#include "csr_dev.h"
+
 namespace cns {
 
 constexpr i64 kRqNever = INT64_MAX;   // a time that is never reached (an infinite end), and the filler of unused event slots
@@ -50,16 +52,6 @@ struct RqParams {
   uint8_t* status; i64* o_start; u32* num_free;
 };
 
-// the query of flat index i: the last q with off[q] <= i (off[Q] > i; empty lists repeat an offset and are skipped)
-__device__ __forceinline__ u32 rq_owner(const u32* __restrict__ off, u32 Q, u32 i) {
-  u32 lo = 0, hi = Q;   // answer in [lo, hi)
-  while (hi - lo > 1) {
-    const u32 mid = lo + ((hi - lo) >> 1);
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 __device__ __forceinline__ i64 rq_add_sat(i64 t, i64 d) { return t > kRqNever - d ? kRqNever : t + d; }   // d > 0
 __device__ __forceinline__ i64 rq_sub_sat(i64 t, i64 d) { return t < INT64_MIN + d ? INT64_MIN : t - d; } // d >= 0
 
@@ -70,13 +62,8 @@ __global__ __launch_bounds__(256) void k_rq_latest(const i64* __restrict__ end_s
   if (a >= num_allocs) return;
   const u32 n = alloc_node[a];
   if (n >= N) return;                       // (the host refused the call already)
-  const u32 j = rq_owner(alloc_off, num_jobs, a);
+  const u32 j = csr_owner(alloc_off, num_jobs, a);
   (void)__hip_atomic_fetch_max((long long*)&latest[n], (long long)end_sec[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__global__ __launch_bounds__(256) void k_rq_fill(i64* __restrict__ p, u32 n, i64 v) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
 }
 
 __device__ __forceinline__ u64 rq_key(i64 t) { return (u64)t ^ 0x8000000000000000ull; }   // signed order -> unsigned order
@@ -90,7 +77,7 @@ __global__ __launch_bounds__(256) void k_rq_emit(const RqParams P) {
   if (i >= P.L) return;
   const u32 o = P.ev_off[i], slots = P.ev_off[i + 1] - o;
   if (slots == 0) return;
-  const u32 q = rq_owner(P.cand_off, P.Q, i);
+  const u32 q = csr_owner(P.cand_off, P.Q, i);
   const u32 n = P.cand[i];
   const i64 start = P.q_start[q], d = P.q_dur[q];
   u32 np = 0, nm = 0;
@@ -132,7 +119,7 @@ __global__ __launch_bounds__(256) void k_rq_first(const RqParams P, u32 total) {
   if (i >= total) return;
   const i64 t = P.plus_s[i];
   if (t == kRqNever) return;
-  const u32 q = rq_owner(P.seg_off, P.Q, i);
+  const u32 q = csr_owner(P.seg_off, P.Q, i);
   const u32 b = P.seg_off[q], e = P.seg_off[q + 1];
   if (i + 1 < e && P.plus_s[i + 1] == t) return;
   const u32 k = P.q_k[q];
@@ -149,7 +136,7 @@ __global__ __launch_bounds__(256) void k_rq_first(const RqParams P, u32 total) {
 __global__ __launch_bounds__(256) void k_rq_classify(const RqParams P) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P.L) return;
-  const u32 q = rq_owner(P.cand_off, P.Q, i);
+  const u32 q = csr_owner(P.cand_off, P.Q, i);
   uint8_t c = CNS_RESVQ_FREE;
   if (!(P.q_flags[q] & 2u)) {
     const u32 n = P.cand[i];

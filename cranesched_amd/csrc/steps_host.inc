@@ -54,20 +54,15 @@ int cns_schedule_steps(cns_handle* h, const cns_step_job_soa* jb, const cns_step
   }
   HIPCHK(h, hipSetDevice(h->device));
   DevBuf* b = h->d_step;  // 0 node_off, 1 node_idx, 2 avail, 3 step_off, 4 steps, 5 incl, 6 excl, 7 scheduled, 8 o_node, 9 o_nt, 10 o_alloc, 11 t_node, 12 t_alloc
-  auto up = [&](DevBuf& d, const void* src, size_t bytes) -> int {
-    HIPCHK(h, d.ensure(bytes));
-    if (src && bytes) HIPCHK(h, hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    return 0;
-  };
   const u32 n_incl = st->incl_offsets ? st->incl_offsets[S] : 0, n_excl = st->excl_offsets ? st->excl_offsets[S] : 0;
   if ((n_incl && !st->incl_nodes) || (n_excl && !st->excl_nodes)) return fail(h, CNS_ERR_INVALID_ARG, "cns_schedule_steps: include / exclude offsets without node lists");
-  if (int rc = up(b[0], jb->node_offsets, ((size_t)Jn + 1) * 4)) return rc;
-  if (int rc = up(b[1], jb->node_idx, (size_t)Nn * 4)) return rc;
+  if (int rc = stage(h, b[0], jb->node_offsets, ((size_t)Jn + 1) * 4)) return rc;
+  if (int rc = stage(h, b[1], jb->node_idx, (size_t)Nn * 4)) return rc;
   if (int rc = upload(h, b[2], avail)) return rc;
-  if (int rc = up(b[3], jb->step_offsets, ((size_t)Jn + 1) * 4)) return rc;
+  if (int rc = stage(h, b[3], jb->step_offsets, ((size_t)Jn + 1) * 4)) return rc;
   if (int rc = upload(h, b[4], recs)) return rc;
-  if (int rc = up(b[5], st->incl_nodes, (size_t)n_incl * 4)) return rc;
-  if (int rc = up(b[6], st->excl_nodes, (size_t)n_excl * 4)) return rc;
+  if (int rc = stage(h, b[5], st->incl_nodes, (size_t)n_incl * 4)) return rc;
+  if (int rc = stage(h, b[6], st->excl_nodes, (size_t)n_excl * 4)) return rc;
   const size_t pl = std::max<u64>(places, 1), tk = std::max<u64>(tasks, 1);
   HIPCHK(h, b[7].ensure(std::max<u32>(S, 1))); HIPCHK(h, b[8].ensure(pl * 4)); HIPCHK(h, b[9].ensure(pl * 4)); HIPCHK(h, b[10].ensure(pl * sizeof(Res)));
   HIPCHK(h, b[11].ensure(tk * 4)); HIPCHK(h, b[12].ensure(tk * sizeof(Res)));

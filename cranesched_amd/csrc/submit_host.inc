@@ -4,14 +4,6 @@
 // (submit_kernels.inc).  Everything lives in cns_engine::d_sub: no buffer of a cycle, of the validity check or of the run limits is read or
 // written.  No CPU fallback.
 
-// cns_engine::d_sub
-enum { SB_QOS = 0, SB_PL, SB_PARENT, SB_UPL, SB_APL, SB_UQ, SB_AQ, SB_G, SB_ST_SET, SB_ST,                                    // tables
-       SB_JPART, SB_JTL, SB_JNCPU, SB_JNMEM, SB_JTCPU, SB_JTMEM, SB_JK, SB_JNT, SB_JGT, SB_JGS,                                // jobs
-       SB_KUSER, SB_KUA, SB_KACCT, SB_KQOS, SB_KCOUNT, SB_KSKIP,                                                                // keys
-       SB_PRE, SB_STATE, SB_STAT, SB_COND, SB_IKEY, SB_ITHR, SB_CODE, SB_TLO, SB_CTR,                                           // per job
-       SB_SK0, SB_SK1, SB_SV0, SB_SV1, SB_HIST, SB_SKEY, SB_SITEM, SB_SADD, SB_VAL, SB_TAILS, SB_HEADS, SB_CARRY, SB_COUNT };   // the parallel pass
-static_assert(SB_COUNT <= sizeof(cns_engine::d_sub) / sizeof(DevBuf), "cns_engine::d_sub holds every buffer of the submit check");
-
 int cns_set_submit_limits(cns_handle* h, const cns_submit_tables* t) {
   if (!h || !t) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: null argument");
   h->sub_have = false;
@@ -73,18 +65,13 @@ int cns_set_submit_limits(cns_handle* h, const cns_submit_tables* t) {
   }
   HIPCHK(h, hipSetDevice(h->device));
   DevBuf* B = h->d_sub;
-  auto up = [&](int b, const void* src, size_t bytes) -> int {
-    HIPCHK(h, B[b].ensure(bytes));
-    if (bytes && src) HIPCHK(h, hipMemcpyAsync(B[b].p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    return 0;
-  };
   int rc = 0;
-  if ((rc = up(SB_QOS, t->qos, (size_t)Q * sizeof(cns_submit_qos))) || (rc = up(SB_PL, t->part_limits, (size_t)L * sizeof(cns_submit_part_limit))) ||
-      (rc = up(SB_PARENT, t->acct_parent, (size_t)A * 4)) || (rc = up(SB_UPL, t->user_part_limit, (size_t)n_up * 4)) ||
-      (rc = up(SB_APL, t->acct_part_limit, (size_t)n_ap * 4)) || (rc = up(SB_UQ, t->user_qos, (size_t)n_uq * sizeof(cns_usage))) ||
-      (rc = up(SB_AQ, t->acct_qos, (size_t)n_aq * sizeof(cns_usage))) || (rc = up(SB_G, t->qos_usage, (size_t)Q * sizeof(cns_usage))) ||
-      (rc = up(SB_ST_SET, st.data(), st.size() * 4)) || (rc = up(SB_ST, st.data(), st.size() * 4))) {
-    resvq_drain(h);
+  if ((rc = stage(h, B[SB_QOS], t->qos, (size_t)Q * sizeof(cns_submit_qos))) || (rc = stage(h, B[SB_PL], t->part_limits, (size_t)L * sizeof(cns_submit_part_limit))) ||
+      (rc = stage(h, B[SB_PARENT], t->acct_parent, (size_t)A * 4)) || (rc = stage(h, B[SB_UPL], t->user_part_limit, (size_t)n_up * 4)) ||
+      (rc = stage(h, B[SB_APL], t->acct_part_limit, (size_t)n_ap * 4)) || (rc = stage(h, B[SB_UQ], t->user_qos, (size_t)n_uq * sizeof(cns_usage))) ||
+      (rc = stage(h, B[SB_AQ], t->acct_qos, (size_t)n_aq * sizeof(cns_usage))) || (rc = stage(h, B[SB_G], t->qos_usage, (size_t)Q * sizeof(cns_usage))) ||
+      (rc = stage(h, B[SB_ST_SET], st.data(), st.size() * 4)) || (rc = stage(h, B[SB_ST], st.data(), st.size() * 4))) {
+    drain(h);
     return rc;
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -120,11 +107,6 @@ static int submit_impl(cns_handle* h, const cns_job_soa* jb, const cns_submit_ke
 
   HIPCHK(h, hipSetDevice(h->device));
   DevBuf* B = h->d_sub;
-  auto up = [&](int b, const void* src, size_t bytes) -> int {
-    HIPCHK(h, B[b].ensure(bytes));
-    if (bytes && src) HIPCHK(h, hipMemcpyAsync(B[b].p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    return 0;
-  };
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
   {
     const struct { int b; const void* p; size_t sz; } ups[] = {
@@ -133,7 +115,7 @@ static int submit_impl(cns_handle* h, const cns_job_soa* jb, const cns_submit_ke
         {SB_JGT, jb->gres_total, CNS_MAX_GRES_NAMES}, {SB_JGS, jb->gres_spec, CNS_MAX_GRES_CLASSES}, {SB_KUSER, ky->user, 4}, {SB_KUA, ky->user_acct, 4},
         {SB_KACCT, ky->account, 4}, {SB_KQOS, ky->qos, 4}, {SB_KCOUNT, ky->count, 4}, {SB_KSKIP, ky->skip, 1}};
     for (const auto& u : ups)
-      if (int rc = up(u.b, u.p, (size_t)J * u.sz)) return rc;
+      if (int rc = stage(h, B[u.b], u.p, (size_t)J * u.sz)) return rc;
   }
   const u32 NK = h->sub_NR + h->sub_NE;
   const size_t n = (size_t)J * kSubItems;
@@ -261,7 +243,7 @@ int cns_check_submissions(cns_handle* h, const cns_job_soa* jobs, const cns_subm
   if (jobs->num_jobs > CNS_SUBMIT_MAX_JOBS) return fail(h, CNS_ERR_UNSUPPORTED, "cns_check_submissions: more than 2^24 jobs in one call");
   if (!out) return fail(h, CNS_ERR_INVALID_ARG, "cns_check_submissions: null result");
   const int rc = submit_impl(h, jobs, keys, flags, out);
-  if (rc != 0) resvq_drain(h);   // nothing of the call is left in flight, the message survives
+  if (rc != 0) drain(h);   // nothing of the call is left in flight, the message survives
   return rc;
 }
 

@@ -5,12 +5,6 @@
 // the caller's node arrays that cns_set_nodes keeps: no flag and no buffer of a cycle, a probe or a reservation what-if is read or
 // written, except the node lists of the reservations (cns_engine::resv_node_slot, read).  No CPU fallback.
 
-// cns_engine::d_vd
-enum { VD_NCPU = 0, VD_NMEM, VD_NGRES, VD_NUNSUP, VD_NODE, VD_POFF, VD_PNODES, VD_TOTAL, VD_RVOFF, VD_RVNODES,              // tables
-       VD_JNCPU, VD_JNMEM, VD_JTCPU, VD_JTMEM, VD_JK, VD_JNT, VD_JGT, VD_JGS, VD_JRSV, VD_IOFF, VD_INCL, VD_EOFF, VD_EXCL,    // jobs
-       VD_ORDER, VD_CHUNKS, VD_CODE, VD_ELIG, VD_COUNT };                                                                     // the call
-static_assert(VD_COUNT <= sizeof(cns_engine::d_vd) / sizeof(DevBuf), "cns_engine::d_vd holds every buffer of the validity check");
-
 constexpr u64 kVdMaxJobs = 0xFFFFFFF0ull;   // 2^32 - 16 jobs of one call (DESIGN.md 8): job indices and grouped positions are 32-bit
 
 // what cns_set_nodes keeps for this call: the caller's arrays as they came (every listed node, schedulable or not)
@@ -31,12 +25,9 @@ static int valid_build_tables(cns_handle* h) {
   for (u32 n = 0; n < N; ++n)
     if (h->vd_cpu[n] < 0) return fail(h, CNS_ERR_INVALID_ARG, "cns_validate_jobs: node " + std::to_string(n) + ": cpu_total_raw < 0");
   if ((u64)h->vd_poff[P] > 0xFFFFFFFFull - 2 * kVdTile) return fail(h, CNS_ERR_UNSUPPORTED, "cns_validate_jobs: more than 2^32 - 513 (partition, node) entries");
-  std::vector<u32> pn = h->vd_pnodes;   // craned_ids is a set (:7354): ascending here, which is also the membership table of the list paths
-  for (u32 p = 0; p < P; ++p) {
-    std::sort(pn.begin() + h->vd_poff[p], pn.begin() + h->vd_poff[p + 1]);
-    for (u32 i = h->vd_poff[p] + 1; i < h->vd_poff[p + 1]; ++i)
-      if (pn[i] == pn[i - 1]) return fail(h, CNS_ERR_INVALID_ARG, "cns_validate_jobs: partition " + std::to_string(p) + " lists node " + std::to_string(pn[i]) + " twice");
-  }
+  std::vector<u32> pn(h->vd_pnodes.size());   // craned_ids is a set (:7354): ascending here, which is also the membership table of the list paths
+  if (const auto v = cns_csr::sort_lists(h->vd_poff.data(), h->vd_pnodes.data(), pn.data(), 0, P); v.what != cns_csr::Lists::Ok)
+    return fail(h, CNS_ERR_INVALID_ARG, "cns_validate_jobs: partition " + std::to_string(v.list) + " lists node " + std::to_string(v.value) + " twice");
   DevBuf* B = h->d_vd;
   if (int rc = upload(h, B[VD_NCPU], h->vd_cpu)) return rc;
   if (int rc = upload(h, B[VD_NMEM], h->vd_mem)) return rc;
@@ -74,18 +65,9 @@ static int valid_build_resv(cns_handle* h) {
   return CNS_OK;
 }
 
-// one list CSR of the call: offsets checked, every job's entries copied sorted, a node twice refused
-static bool valid_sort_lists(const u64* off, const u32* src, u32* dst, u64 beg, u64 end) {
-  for (u64 j = beg; j < end; ++j) {
-    const u64 b = off[j], e = off[j + 1];
-    if (e < b) return false;
-    if (e == b) continue;
-    memcpy(dst + b, src + b, (size_t)(e - b) * 4);
-    std::sort(dst + b, dst + e);
-    for (u64 x = b + 1; x < e; ++x)
-      if (dst[x] == dst[x - 1]) return false;
-  }
-  return true;
+// the jobs [beg, end) of one list CSR of the call: offsets checked, every job's entries copied sorted, a node twice refused
+static bool valid_lists_ok(const u64* off, const u32* src, u32* dst, u64 beg, u64 end) {
+  return cns_csr::first_decrease(off + beg, end - beg) == end - beg && cns_csr::sort_lists(off, src, dst, beg, end).what == cns_csr::Lists::Ok;
 }
 
 static int validate_impl(cns_handle* h, const cns_job_soa* jb, const cns_validity_out* out, double* kernel_ms) {
@@ -111,8 +93,8 @@ static int validate_impl(cns_handle* h, const cns_job_soa* jb, const cns_validit
   cns_jobs_host::for_chunks(chunks, [&](cns_jobs_host::Chunk& c, uint32_t) {
     c.cnt.assign((size_t)P + 1, 0);
     for (u64 j = c.beg; j < c.end; ++j) c.cnt[std::min<u32>(jb->partition[j], P)]++;
-    if ((has_incl && !valid_sort_lists(jb->incl_offsets, jb->incl_nodes, incl_sorted.data(), c.beg, c.end)) ||
-        (has_excl && !valid_sort_lists(jb->excl_offsets, jb->excl_nodes, excl_sorted.data(), c.beg, c.end)))
+    if ((has_incl && !valid_lists_ok(jb->incl_offsets, jb->incl_nodes, incl_sorted.data(), c.beg, c.end)) ||
+        (has_excl && !valid_lists_ok(jb->excl_offsets, jb->excl_nodes, excl_sorted.data(), c.beg, c.end)))
       c.bad_job = c.beg;
   });
   for (const auto& c : chunks)
@@ -136,30 +118,25 @@ static int validate_impl(cns_handle* h, const cns_job_soa* jb, const cns_validit
 
   // ---- the caller's job arrays as they are, the call's tables, the results ----
   DevBuf* B = h->d_vd;
-  auto up = [&](int b, const void* src, size_t bytes) -> int {
-    HIPCHK(h, B[b].ensure(bytes));
-    if (bytes && src) HIPCHK(h, hipMemcpyAsync(B[b].p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    return 0;
-  };
-  if (int rc = up(VD_JNCPU, jb->node_cpu_raw, (size_t)J * 8)) return rc;
-  if (int rc = up(VD_JNMEM, jb->node_mem, (size_t)J * 8)) return rc;
-  if (int rc = up(VD_JTCPU, jb->task_cpu_raw, (size_t)J * 8)) return rc;
-  if (int rc = up(VD_JTMEM, jb->task_mem, (size_t)J * 8)) return rc;
-  if (int rc = up(VD_JK, jb->node_num, (size_t)J * 4)) return rc;
-  if (int rc = up(VD_JNT, jb->ntasks, (size_t)J * 4)) return rc;
-  if (int rc = up(VD_JGT, jb->gres_total, (size_t)J * CNS_MAX_GRES_NAMES)) return rc;
-  if (int rc = up(VD_JGS, jb->gres_spec, (size_t)J * CNS_MAX_GRES_CLASSES)) return rc;
-  if (int rc = up(VD_JRSV, jb->reservation, (size_t)J * 4)) return rc;
+  if (int rc = stage(h, B[VD_JNCPU], jb->node_cpu_raw, (size_t)J * 8)) return rc;
+  if (int rc = stage(h, B[VD_JNMEM], jb->node_mem, (size_t)J * 8)) return rc;
+  if (int rc = stage(h, B[VD_JTCPU], jb->task_cpu_raw, (size_t)J * 8)) return rc;
+  if (int rc = stage(h, B[VD_JTMEM], jb->task_mem, (size_t)J * 8)) return rc;
+  if (int rc = stage(h, B[VD_JK], jb->node_num, (size_t)J * 4)) return rc;
+  if (int rc = stage(h, B[VD_JNT], jb->ntasks, (size_t)J * 4)) return rc;
+  if (int rc = stage(h, B[VD_JGT], jb->gres_total, (size_t)J * CNS_MAX_GRES_NAMES)) return rc;
+  if (int rc = stage(h, B[VD_JGS], jb->gres_spec, (size_t)J * CNS_MAX_GRES_CLASSES)) return rc;
+  if (int rc = stage(h, B[VD_JRSV], jb->reservation, (size_t)J * 4)) return rc;
   if (has_incl) {
-    if (int rc = up(VD_IOFF, jb->incl_offsets, ((size_t)J + 1) * 8)) return rc;
-    if (int rc = up(VD_INCL, incl_sorted.data(), incl_sorted.size() * 4)) return rc;
+    if (int rc = stage(h, B[VD_IOFF], jb->incl_offsets, ((size_t)J + 1) * 8)) return rc;
+    if (int rc = stage(h, B[VD_INCL], incl_sorted.data(), incl_sorted.size() * 4)) return rc;
   }
   if (has_excl) {
-    if (int rc = up(VD_EOFF, jb->excl_offsets, ((size_t)J + 1) * 8)) return rc;
-    if (int rc = up(VD_EXCL, excl_sorted.data(), excl_sorted.size() * 4)) return rc;
+    if (int rc = stage(h, B[VD_EOFF], jb->excl_offsets, ((size_t)J + 1) * 8)) return rc;
+    if (int rc = stage(h, B[VD_EXCL], excl_sorted.data(), excl_sorted.size() * 4)) return rc;
   }
-  if (int rc = up(VD_ORDER, order.data(), (size_t)J * 4)) return rc;
-  if (int rc = up(VD_CHUNKS, recs.data(), recs.size() * sizeof(VdChunkRec))) return rc;
+  if (int rc = stage(h, B[VD_ORDER], order.data(), (size_t)J * 4)) return rc;
+  if (int rc = stage(h, B[VD_CHUNKS], recs.data(), recs.size() * sizeof(VdChunkRec))) return rc;
   HIPCHK(h, B[VD_CODE].ensure((size_t)J));
   HIPCHK(h, B[VD_ELIG].ensure((size_t)J * 4));
   VdParams A{};
@@ -195,7 +172,7 @@ int cns_validate_jobs(cns_handle* h, const cns_job_soa* jobs, const cns_validity
   if (jobs->num_jobs > kVdMaxJobs) return fail(h, CNS_ERR_UNSUPPORTED, "cns_validate_jobs: more than 2^32 - 16 jobs in one call");
   if (!out) return fail(h, CNS_ERR_INVALID_ARG, "cns_validate_jobs: null result");
   const int rc = validate_impl(h, jobs, out, kernel_ms);
-  if (rc != 0) resvq_drain(h);   // nothing of the call is left in flight, the message survives
+  if (rc != 0) drain(h);   // nothing of the call is left in flight, the message survives
   return rc;
 }
 

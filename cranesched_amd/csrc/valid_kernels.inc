@@ -14,6 +14,8 @@
 // One workgroup finishes its jobs: no atomics, no workgroup waits for another.  Nothing here knows the cycle's node types, its slots or its
 // width limits.  Every store is a plain vector store.
 
+#include "csr_dev.h"
+
 namespace cns {
 
 constexpr u32 kVdBlock = 256;
@@ -123,18 +125,6 @@ __global__ __launch_bounds__(256) void k_valid_totals(u32 P, const u32* __restri
   }
 }
 
-// is x in the ascending a[b, e)?
-template <class Off>
-__device__ __forceinline__ bool vd_contains(const u32* __restrict__ a, Off b, Off e, u32 x) {
-  while (b < e) {
-    const Off mid = b + ((e - b) >> 1);
-    const u32 v = a[mid];
-    if (v == x) return true;
-    if (v < x) b = mid + 1; else e = mid;
-  }
-  return false;
-}
-
 struct VdNeed { i64 cpu; u64 mem; u64 spec; u32 tot; };   // req_node_res_view + req_task_res_view (:7356); count bytes clamped to 65
 
 // PublicHeader.cpp:619-646 on counts.  A byte of `spec` / `tot` is at most 65, a byte of the node at most 64: (node | 0x80) - need keeps
@@ -217,20 +207,20 @@ __global__ __launch_bounds__(256) void k_valid_walk(const VdParams A) {
       if (rsv != CNS_RESV_NONE) {                                              // :7338-7349
         const u32 rb = A.rv_off[rsv], re = A.rv_off[rsv + 1];
         for (u64 x = ib; x < ie && code == kPending; ++x)
-          if (!vd_contains(A.rv_nodes, rb, re, A.incl[x])) code = CNS_VALID_RESV_NODE;
+          if (!sorted_contains(A.rv_nodes, rb, re, A.incl[x])) code = CNS_VALID_RESV_NODE;
       }
       // the included nodes the partition lists, that fit and are not excluded (:7356-7361)
       cnt = 0;
       if (code == kPending)
         for (u64 x = ib; x < ie; ++x) {
           const u32 n = A.incl[x];
-          if (n < A.N && vd_contains(A.part_nodes, pb, pe, n) && vd_fits(q, A.node[n]) && !vd_contains(A.excl, eb, ee, n)) ++cnt;
+          if (n < A.N && sorted_contains(A.part_nodes, pb, pe, n) && vd_fits(q, A.node[n]) && !sorted_contains(A.excl, eb, ee, n)) ++cnt;
         }
     } else {
       // every excluded node the partition lists and that fits was counted above (a list names a node once)
       for (u64 x = eb; x < ee; ++x) {
         const u32 n = A.excl[x];
-        if (n < A.N && vd_contains(A.part_nodes, pb, pe, n) && vd_fits(q, A.node[n])) --cnt;
+        if (n < A.N && sorted_contains(A.part_nodes, pb, pe, n) && vd_fits(q, A.node[n])) --cnt;
       }
     }
     if (code == kPending) code = cnt < k ? CNS_VALID_NOT_ENOUGH_NODES : CNS_VALID_OK;   // :7368

@@ -197,6 +197,16 @@ struct GpuNodeSelectionAlgo::Impl {
           inodes(PinAlloc<uint32_t>(c)), enodes(PinAlloc<uint32_t>(c)), jresv(PinAlloc<uint32_t>(c)), L(PinAlloc<int64_t>(c)), ncpu(PinAlloc<int64_t>(c)),
           tcpu(PinAlloc<int64_t>(c)), nmem(PinAlloc<uint64_t>(c)), tmem(PinAlloc<uint64_t>(c)), ioff(PinAlloc<uint64_t>(c)), eoff(PinAlloc<uint64_t>(c)),
           excl(PinAlloc<uint8_t>(c)), skip(PinAlloc<uint8_t>(c)), gtot(PinAlloc<uint8_t>(c)), gspec(PinAlloc<uint8_t>(c)) {}
+    cns_job_soa soa(size_t n) const {   // the table of n packed jobs as the ABI reads it
+      cns_job_soa js{};
+      js.num_jobs = n;
+      js.partition = part.data(); js.time_limit_sec = L.data(); js.node_cpu_raw = ncpu.data(); js.node_mem = nmem.data();
+      js.task_cpu_raw = tcpu.data(); js.task_mem = tmem.data(); js.node_num = k.data(); js.ntasks = nt.data();
+      js.ntasks_per_node_min = tmin.data(); js.ntasks_per_node_max = tmax.data(); js.exclusive = excl.data();
+      js.gres_total = gtot.data(); js.gres_spec = gspec.data(); js.incl_offsets = ioff.data(); js.incl_nodes = inodes.data();
+      js.excl_offsets = eoff.data(); js.excl_nodes = enodes.data(); js.skip = skip.data(); js.reservation = jresv.data();
+      return js;
+    }
   };
   PackedJobs packed{&pin};   // the job table of the cycle: page-locked, reused
   double t_pack_ms = 0, t_engine_ms = 0, t_write_ms = 0;   // the last NodeSelect: pack | cns_select (H2D + kernels + D2H) | write-back
@@ -594,7 +604,24 @@ struct GpuNodeSelectionAlgo::Impl {
         : start(PinAlloc<int64_t>(c)), cpu(PinAlloc<int64_t>(c)), reason(PinAlloc<uint8_t>(c)), off(PinAlloc<uint64_t>(c)), mem(PinAlloc<uint64_t>(c)),
           lo(PinAlloc<uint64_t>(c)), hi(PinAlloc<uint64_t>(c)), g(PinAlloc<uint64_t>(c)), w2(PinAlloc<uint64_t>(c)), w3(PinAlloc<uint64_t>(c)),
           node(PinAlloc<uint32_t>(c)), nt(PinAlloc<uint32_t>(c)) {}
+    cns_placement_soa soa(uint64_t places) {   // the result arrays (sized by the caller: jobs + 1, places + 1) as the ABI writes them
+      cns_placement_soa out{};
+      out.place_capacity = places;
+      out.start_sec = start.data(); out.reason = reason.data(); out.place_offsets = off.data();
+      out.node_idx = node.data(); out.ntasks = nt.data(); out.cpu_raw = cpu.data(); out.mem = mem.data();
+      out.core_lo = lo.data(); out.core_hi = hi.data(); out.gres = g.data(); out.core_w2 = w2.data(); out.core_w3 = w3.data();
+      return out;
+    }
   } last{&pin};
+  cns_running_soa running_soa() const {   // the packed running set (r_*) as the ABI reads it
+    cns_running_soa rs{};
+    rs.num_jobs = (uint32_t)r_end.size(); rs.num_allocs = (uint32_t)r_node.size();
+    rs.end_sec = r_end.data(); rs.alloc_offsets = r_off.data(); rs.alloc_node = r_node.data();
+    rs.alloc_cpu_raw = r_cpu.data(); rs.alloc_mem = r_mem.data(); rs.alloc_core_lo = r_lo.data();
+    rs.alloc_core_hi = r_hi.data(); rs.alloc_gres = r_g.data(); rs.reservation = r_resv.data();
+    rs.alloc_core_w2 = r_w2.data(); rs.alloc_core_w3 = r_w3.data();
+    return rs;
+  }
   uint64_t mem_sw_of(size_t j, uint64_t q) const {   // what write_back puts into memory_sw_bytes
     return last.excl[j] ? node_mem_sw[last.node[q]] : last.msw_node[j] + last.msw_task[j] * last.nt[q];
   }
@@ -1142,15 +1169,7 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
   }
   if (I.packed_from_mirror ? I.mirror_ovf != 0 : I.run_overflow)   // (judged on the records of THIS cycle's running set, cached or fresh)
     return fail_all(CNS_ERR_UNSUPPORTED, "a running job holds a core id >= 256");
-  const auto &r_end = I.r_end, &r_cpu = I.r_cpu;
-  const auto &r_off = I.r_off, &r_node = I.r_node, &r_resv = I.r_resv;
-  const auto &r_mem = I.r_mem, &r_lo = I.r_lo, &r_hi = I.r_hi, &r_g = I.r_g;
-  cns_running_soa rs{};
-  rs.num_jobs = (uint32_t)r_end.size(); rs.num_allocs = (uint32_t)r_node.size();
-  rs.end_sec = r_end.data(); rs.alloc_offsets = r_off.data(); rs.alloc_node = r_node.data();
-  rs.alloc_cpu_raw = r_cpu.data(); rs.alloc_mem = r_mem.data(); rs.alloc_core_lo = r_lo.data();
-  rs.alloc_core_hi = r_hi.data(); rs.alloc_gres = r_g.data(); rs.reservation = r_resv.data();
-  rs.alloc_core_w2 = I.r_w2.data(); rs.alloc_core_w3 = I.r_w3.data();
+  const cns_running_soa rs = I.running_soa();
   int st = I.grp ? cns_group_set_running(I.grp, rs.num_jobs ? &rs : nullptr) : cns_set_running(I.h, rs.num_jobs ? &rs : nullptr);
   if (st != 0) return fail_all(st, I.grp ? cns_group_last_error(I.grp) : cns_last_error(I.h));
 
@@ -1171,28 +1190,14 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
   S.jobs = 0;
   uint64_t places = 0;
   I.pack_pending(ord, B, &S, &places);
-  auto &part = B.part, &k = B.k, &nt = B.nt, &tmin = B.tmin, &tmax = B.tmax, &inodes = B.inodes, &enodes = B.enodes, &jresv = B.jresv;
-  auto &L = B.L, &ncpu = B.ncpu, &tcpu = B.tcpu;
-  auto &nmem = B.nmem, &tmem = B.tmem, &ioff = B.ioff, &eoff = B.eoff;
-  auto &excl = B.excl, &skip = B.skip, &gtot = B.gtot, &gspec = B.gspec;
-  cns_job_soa js{};
-  js.num_jobs = J;
-  js.partition = part.data(); js.time_limit_sec = L.data(); js.node_cpu_raw = ncpu.data(); js.node_mem = nmem.data();
-  js.task_cpu_raw = tcpu.data(); js.task_mem = tmem.data(); js.node_num = k.data(); js.ntasks = nt.data();
-  js.ntasks_per_node_min = tmin.data(); js.ntasks_per_node_max = tmax.data(); js.exclusive = excl.data();
-  js.gres_total = gtot.data(); js.gres_spec = gspec.data(); js.incl_offsets = ioff.data(); js.incl_nodes = inodes.data();
-  js.excl_offsets = eoff.data(); js.excl_nodes = enodes.data(); js.skip = skip.data(); js.reservation = jresv.data();
+  const cns_job_soa js = B.soa(J);
 
   // (sized, not zero-filled: cns_download / cns_group_select write every job's start and reason and every placement record of the cycle)
   S.start.resize(J + 1); S.cpu.resize(places + 1); S.reason.resize(J + 1); S.off.resize(J + 1);
   S.mem.resize(places + 1); S.lo.resize(places + 1); S.hi.resize(places + 1); S.g.resize(places + 1);
   S.w2.resize(places + 1); S.w3.resize(places + 1);
   S.node.resize(places + 1); S.nt.resize(places + 1);
-  cns_placement_soa out{};
-  out.place_capacity = places;
-  out.start_sec = S.start.data(); out.reason = S.reason.data(); out.place_offsets = S.off.data();
-  out.node_idx = S.node.data(); out.ntasks = S.nt.data(); out.cpu_raw = S.cpu.data(); out.mem = S.mem.data();
-  out.core_lo = S.lo.data(); out.core_hi = S.hi.data(); out.gres = S.g.data(); out.core_w2 = S.w2.data(); out.core_w3 = S.w3.data();
+  cns_placement_soa out = S.soa(places);
   I.last_index.clear();
   I.last_ord.clear();
   I.cancelled.clear();
@@ -1280,22 +1285,13 @@ void GpuNodeSelectionAlgo::ProbeStart(const std::vector<PdJobInScheduler*>& jobs
   I.pack_pending(jobs, B);
   uint64_t places = 0;
   for (const PdJobInScheduler* j : jobs) places += j->node_num;
-  cns_job_soa js{};
-  js.num_jobs = Q;
-  js.partition = B.part.data(); js.time_limit_sec = B.L.data(); js.node_cpu_raw = B.ncpu.data(); js.node_mem = B.nmem.data();
-  js.task_cpu_raw = B.tcpu.data(); js.task_mem = B.tmem.data(); js.node_num = B.k.data(); js.ntasks = B.nt.data();
-  js.ntasks_per_node_min = B.tmin.data(); js.ntasks_per_node_max = B.tmax.data(); js.exclusive = B.excl.data();
-  js.gres_total = B.gtot.data(); js.gres_spec = B.gspec.data(); js.incl_offsets = B.ioff.data(); js.incl_nodes = B.inodes.data();
-  js.excl_offsets = B.eoff.data(); js.excl_nodes = B.enodes.data(); js.skip = B.skip.data(); js.reservation = B.jresv.data();
-  std::vector<int64_t> start(Q + 1, 0), cpu(places + 1, 0);
-  std::vector<uint8_t> reason(Q + 1, 0);
-  std::vector<uint64_t> off(Q + 1, 0), mem(places + 1, 0), lo(places + 1, 0), hi(places + 1, 0), g(places + 1, 0), w2(places + 1, 0), w3(places + 1, 0);
-  std::vector<uint32_t> node(places + 1, CNS_NODE_NONE), nt(places + 1, 0);
-  cns_placement_soa out{};
-  out.place_capacity = places;
-  out.start_sec = start.data(); out.reason = reason.data(); out.place_offsets = off.data();
-  out.node_idx = node.data(); out.ntasks = nt.data(); out.cpu_raw = cpu.data(); out.mem = mem.data();
-  out.core_lo = lo.data(); out.core_hi = hi.data(); out.gres = g.data(); out.core_w2 = w2.data(); out.core_w3 = w3.data();
+  const cns_job_soa js = B.soa(Q);
+  Impl::PlacementStore S(nullptr);   // zero-filled, no node named: a probe the engine does not reach reads as unplaced
+  S.start.assign(Q + 1, 0); S.reason.assign(Q + 1, 0); S.off.assign(Q + 1, 0);
+  for (auto* v : {&S.mem, &S.lo, &S.hi, &S.g, &S.w2, &S.w3}) v->assign(places + 1, 0);
+  S.cpu.assign(places + 1, 0); S.nt.assign(places + 1, 0);
+  S.node.assign(places + 1, CNS_NODE_NONE);
+  cns_placement_soa out = S.soa(places);
   const int st = cns_probe(I.h, &js, &out, nullptr);
   if (st != 0) return fail_all(st, cns_last_error(I.h));
   status_ = 0;
@@ -1322,9 +1318,7 @@ std::vector<GpuNodeSelectionAlgo::ResvAnswer> GpuNodeSelectionAlgo::QueryReserva
   // rebuilt only when one of the two was packed anew since the last call
   int st = 0;
   if (I.resvq_stale) {
-    cns_running_soa rs{};
-    rs.num_jobs = (uint32_t)I.r_end.size(); rs.num_allocs = (uint32_t)I.r_node.size();
-    rs.end_sec = I.r_end.data(); rs.alloc_offsets = I.r_off.data(); rs.alloc_node = I.r_node.data();
+    const cns_running_soa rs = I.running_soa();   // (cns_resvq_set_state reads the end times and the allocations' nodes only)
     cns_resv_soa rv{};
     rv.num_resv = (uint32_t)I.v_start.size(); rv.num_allocs = (uint32_t)I.v_node.size();
     rv.start_sec = I.v_start.data(); rv.end_sec = I.v_end.data(); rv.alloc_offsets = I.v_off.data(); rv.alloc_node = I.v_node.data();
@@ -1411,13 +1405,7 @@ bool GpuNodeSelectionAlgo::CheckJobValidity(const std::vector<const PdJobInSched
     for (uint64_t x = B.ioff[j]; x < B.ioff[j + 1]; ++x)
       if (B.inodes[x] >= N) B.inodes[x] = N + unknown++;
   }
-  cns_job_soa js{};
-  js.num_jobs = Q;
-  js.partition = B.part.data(); js.time_limit_sec = B.L.data(); js.node_cpu_raw = B.ncpu.data(); js.node_mem = B.nmem.data();
-  js.task_cpu_raw = B.tcpu.data(); js.task_mem = B.tmem.data(); js.node_num = B.k.data(); js.ntasks = B.nt.data();
-  js.ntasks_per_node_min = B.tmin.data(); js.ntasks_per_node_max = B.tmax.data(); js.exclusive = B.excl.data();
-  js.gres_total = B.gtot.data(); js.gres_spec = B.gspec.data(); js.incl_offsets = B.ioff.data(); js.incl_nodes = B.inodes.data();
-  js.excl_offsets = B.eoff.data(); js.excl_nodes = B.enodes.data(); js.skip = B.skip.data(); js.reservation = B.jresv.data();
+  const cns_job_soa js = B.soa(Q);
   std::vector<uint8_t> code(Q);
   std::vector<uint32_t> elig(Q);
   cns_validity_out vo{code.data(), elig.data()};
@@ -1639,6 +1627,96 @@ const char* kLimitReasonStr[] = {"", "QosEntryNotFound", "QosCpuResourceLimit", 
                                  "UserPartitionJobsLimit", "UserPartitionWallTimeLimit", "AccPartitionJobsLimit",
                                  "AccPartitionWallTimeLimit", "PartitionCpuResourceLimit", "PartitionMemResourceLimit",
                                  "PartitionGresResourceLimit"};
+// What CheckAndMallocMetaResource and CheckSubmitLimits share of an AccountMetaSnapshot: the dense numbering of users, (user, account)
+// pairs, accounts and QoS that decides which table row a name owns, the partition names by index, the parent table, and the conversions
+// into the ABI's records.  (A template: Impl is a private member of the class.)
+template <class ImplT>
+struct AccountIndex {
+  const ImplT& I;
+  std::map<std::string, uint32_t> qos_ix, acct_ix, user_ix;
+  std::map<std::pair<std::string, std::string>, uint32_t> ua_ix;  // (user, account) pairs of User::account_to_attrs_map
+  uint32_t Q, A, U, UA, Pn;
+  std::vector<std::string> part_name;
+  std::vector<uint32_t> parent;
+
+  // sorted names: deterministic
+  template <class Map>
+  static std::map<std::string, uint32_t> index_of(const Map& m) {
+    std::map<std::string, uint32_t> ix;
+    for (const auto& kv : m) ix.emplace(kv.first, 0);
+    uint32_t n = 0;
+    for (auto& kv : ix) kv.second = n++;
+    return ix;
+  }
+  AccountIndex(const ImplT& impl, const AccountMetaSnapshot& meta)
+      : I(impl), qos_ix(index_of(meta.qos)), acct_ix(index_of(meta.account_parent)), user_ix(index_of(meta.user_accounts)) {
+    for (const auto& [u, accts] : meta.user_accounts)
+      for (const auto& [a, lims] : accts) ua_ix.emplace(std::make_pair(u, a), 0);
+    { uint32_t n = 0; for (auto& kv : ua_ix) kv.second = n++; }
+    Q = (uint32_t)qos_ix.size(); A = (uint32_t)acct_ix.size(); U = (uint32_t)user_ix.size(); UA = (uint32_t)ua_ix.size();
+    Pn = (uint32_t)I.part_idx.size();
+    part_name.resize(Pn);
+    for (const auto& [name, ix] : I.part_idx) part_name[ix] = name;
+    parent.assign(A, CNS_LIM_NONE);
+    for (const auto& [name, ix] : acct_ix) {
+      const std::string& p = meta.account_parent.at(name);
+      if (!p.empty()) { auto it = acct_ix.find(p); if (it != acct_ix.end()) parent[ix] = it->second; }
+    }
+  }
+  cns_tres to_tres(const ResourceView& v) const {
+    cns_tres t{};
+    t.cpu_raw = v.cpu_count.raw;
+    t.mem = v.memory_bytes;
+    for (const auto& [name, gc] : v.gres_map) {
+      auto nit = I.name_id.find(name);
+      if (nit == I.name_id.end()) continue;
+      t.name_mask |= 1u << nit->second;
+      t.name_total[nit->second] = gc.total;
+      for (const auto& [type, cnt] : gc.specified) {
+        const int c = I.class_of(name, type);
+        if (c < 0) continue;
+        t.class_mask |= 1u << c;
+        t.class_count[c] = cnt;
+      }
+    }
+    return t;
+  }
+  cns_usage to_usage(const MetaResource& m) const {
+    cns_usage u{};
+    u.cpu_raw = m.resource.cpu_count.raw;
+    u.mem = m.resource.memory_bytes;
+    u.wall_sec = m.wall_time;
+    u.jobs_count = m.jobs_count;
+    for (const auto& [name, gc] : m.resource.gres_map) {
+      auto nit = I.name_id.find(name);
+      if (nit == I.name_id.end()) continue;
+      u.name_total[nit->second] = gc.total;
+      for (const auto& [type, cnt] : gc.specified) {
+        const int c = I.class_of(name, type);
+        if (c >= 0) u.class_count[c] = cnt;
+      }
+    }
+    return u;
+  }
+  // (user, account) x partition and account x partition -> the number of the record `add_plim` builds of a limit, CNS_LIM_NONE: no limit
+  template <class AddPlim>
+  void fill_part_limits(const AccountMetaSnapshot& meta, std::vector<uint32_t>& upl, std::vector<uint32_t>& apl, AddPlim add_plim) const {
+    upl.assign((size_t)UA * Pn, CNS_LIM_NONE); apl.assign((size_t)A * Pn, CNS_LIM_NONE);
+    for (const auto& [key, x] : ua_ix)
+      for (const auto& [pname, lim] : meta.user_accounts.at(key.first).at(key.second)) {
+        auto pit = I.part_idx.find(pname);
+        if (pit != I.part_idx.end()) upl[(size_t)x * Pn + pit->second] = add_plim(lim);
+      }
+    for (const auto& [aname, lims] : meta.account_partition_limits) {
+      auto ait = acct_ix.find(aname);
+      if (ait == acct_ix.end()) continue;
+      for (const auto& [pname, lim] : lims) {
+        auto pit = I.part_idx.find(pname);
+        if (pit != I.part_idx.end()) apl[(size_t)ait->second * Pn + pit->second] = add_plim(lim);
+      }
+    }
+  }
+};
 }  // namespace
 
 Qos::Qos() : max_tres(UnlimitedTres()), max_tres_per_user(UnlimitedTres()), max_tres_per_account(UnlimitedTres()) {}
@@ -1656,60 +1734,15 @@ void GpuNodeSelectionAlgo::CheckAndMallocMetaResource(AccountMetaSnapshot& meta,
   if (!I.h) return fail_all(status_ ? status_ : CNS_ERR_NO_DEVICE, error_);
   if (!I.have_snapshot) return fail_all(CNS_ERR_STATE, "CheckAndMallocMetaResource before SetClusterSnapshot / NodeSelect");
 
-  // ---- dense indices (sorted names: deterministic) ----
-  auto index_of = [](const auto& m) {
-    std::map<std::string, uint32_t> ix;
-    for (const auto& kv : m) ix.emplace(kv.first, 0);
-    uint32_t n = 0;
-    for (auto& kv : ix) kv.second = n++;
-    return ix;
-  };
-  const std::map<std::string, uint32_t> qos_ix = index_of(meta.qos), acct_ix = index_of(meta.account_parent), user_ix = index_of(meta.user_accounts);
-  std::map<std::pair<std::string, std::string>, uint32_t> ua_ix;  // (user, account) pairs of User::account_to_attrs_map
-  for (const auto& [u, accts] : meta.user_accounts)
-    for (const auto& [a, lims] : accts) ua_ix.emplace(std::make_pair(u, a), 0);
-  { uint32_t n = 0; for (auto& kv : ua_ix) kv.second = n++; }
-  const uint32_t Q = (uint32_t)qos_ix.size(), A = (uint32_t)acct_ix.size(), U = (uint32_t)user_ix.size(), UA = (uint32_t)ua_ix.size();
-  const uint32_t Pn = (uint32_t)I.part_idx.size();
-  std::vector<std::string> part_name(Pn);
-  for (const auto& [name, ix] : I.part_idx) part_name[ix] = name;
+  // ---- dense indices (sorted names: deterministic), the conversions and the parent table ----
+  const AccountIndex ax(I, meta);
+  const auto &qos_ix = ax.qos_ix, &acct_ix = ax.acct_ix, &user_ix = ax.user_ix;
+  const auto& ua_ix = ax.ua_ix;
+  const uint32_t Q = ax.Q, A = ax.A, U = ax.U, UA = ax.UA, Pn = ax.Pn;
+  const std::vector<std::string>& part_name = ax.part_name;
+  const std::vector<uint32_t>& parent = ax.parent;
   if (!Q) return fail_all(CNS_ERR_INVALID_ARG, "AccountMetaSnapshot without QoS");
 
-  auto to_tres = [&](const ResourceView& v) {
-    cns_tres t{};
-    t.cpu_raw = v.cpu_count.raw;
-    t.mem = v.memory_bytes;
-    for (const auto& [name, gc] : v.gres_map) {
-      auto nit = I.name_id.find(name);
-      if (nit == I.name_id.end()) continue;
-      t.name_mask |= 1u << nit->second;
-      t.name_total[nit->second] = gc.total;
-      for (const auto& [type, cnt] : gc.specified) {
-        const int c = I.class_of(name, type);
-        if (c < 0) continue;
-        t.class_mask |= 1u << c;
-        t.class_count[c] = cnt;
-      }
-    }
-    return t;
-  };
-  auto to_usage = [&](const MetaResource& m) {
-    cns_usage u{};
-    u.cpu_raw = m.resource.cpu_count.raw;
-    u.mem = m.resource.memory_bytes;
-    u.wall_sec = m.wall_time;
-    u.jobs_count = m.jobs_count;
-    for (const auto& [name, gc] : m.resource.gres_map) {
-      auto nit = I.name_id.find(name);
-      if (nit == I.name_id.end()) continue;
-      u.name_total[nit->second] = gc.total;
-      for (const auto& [type, cnt] : gc.specified) {
-        const int c = I.class_of(name, type);
-        if (c >= 0) u.class_count[c] = cnt;
-      }
-    }
-    return u;
-  };
   auto from_usage = [&](const cns_usage& u) {
     MetaResource m;
     m.resource.cpu_count = cpu_t::from_raw(u.cpu_raw);
@@ -1737,34 +1770,17 @@ void GpuNodeSelectionAlgo::CheckAndMallocMetaResource(AccountMetaSnapshot& meta,
     cns_qos_limits& d = qos[ix];
     d.max_jobs_per_user = s.max_jobs_per_user; d.max_jobs_per_account = s.max_jobs_per_account; d.max_jobs = s.max_jobs;
     d.max_cpus_per_user_raw = s.max_cpus_per_user.raw; d.max_wall_sec = s.max_wall;
-    d.max_tres = to_tres(s.max_tres); d.max_tres_per_user = to_tres(s.max_tres_per_user); d.max_tres_per_account = to_tres(s.max_tres_per_account);
-  }
-  std::vector<uint32_t> parent(A, CNS_LIM_NONE);
-  for (const auto& [name, ix] : acct_ix) {
-    const std::string& p = meta.account_parent.at(name);
-    if (!p.empty()) { auto it = acct_ix.find(p); if (it != acct_ix.end()) parent[ix] = it->second; }
+    d.max_tres = ax.to_tres(s.max_tres); d.max_tres_per_user = ax.to_tres(s.max_tres_per_user); d.max_tres_per_account = ax.to_tres(s.max_tres_per_account);
   }
   std::vector<cns_part_limit> plims;
   auto add_plim = [&](const PartitionResourceLimit& s) {
     cns_part_limit d{};
-    d.max_jobs = s.max_jobs; d.max_wall_sec = s.max_wall; d.max_tres = to_tres(s.max_tres);
+    d.max_jobs = s.max_jobs; d.max_wall_sec = s.max_wall; d.max_tres = ax.to_tres(s.max_tres);
     plims.push_back(d);
     return (uint32_t)plims.size() - 1;
   };
-  std::vector<uint32_t> upl((size_t)UA * Pn, CNS_LIM_NONE), apl((size_t)A * Pn, CNS_LIM_NONE);
-  for (const auto& [key, x] : ua_ix)
-    for (const auto& [pname, lim] : meta.user_accounts.at(key.first).at(key.second)) {
-      auto pit = I.part_idx.find(pname);
-      if (pit != I.part_idx.end()) upl[(size_t)x * Pn + pit->second] = add_plim(lim);
-    }
-  for (const auto& [aname, lims] : meta.account_partition_limits) {
-    auto ait = acct_ix.find(aname);
-    if (ait == acct_ix.end()) continue;
-    for (const auto& [pname, lim] : lims) {
-      auto pit = I.part_idx.find(pname);
-      if (pit != I.part_idx.end()) apl[(size_t)ait->second * Pn + pit->second] = add_plim(lim);
-    }
-  }
+  std::vector<uint32_t> upl, apl;
+  ax.fill_part_limits(meta, upl, apl, add_plim);
   // ---- usage maps -> tables (an absent map entry = exists 0) ----
   std::vector<cns_usage> uq((size_t)U * Q), up((size_t)UA * Pn), aq((size_t)A * Q), ap((size_t)A * Pn), qu(Q);
   std::vector<uint8_t> uqe(uq.size(), 0), upe(up.size(), 0), aqe(aq.size(), 0), ape(ap.size(), 0);
@@ -1773,14 +1789,14 @@ void GpuNodeSelectionAlgo::CheckAndMallocMetaResource(AccountMetaSnapshot& meta,
     if (uit == user_ix.end()) continue;
     for (const auto& [qname, m] : stat.qos_to_resource_map) {
       auto qit = qos_ix.find(qname);
-      if (qit != qos_ix.end()) { uq[(size_t)uit->second * Q + qit->second] = to_usage(m); uqe[(size_t)uit->second * Q + qit->second] = 1; }
+      if (qit != qos_ix.end()) { uq[(size_t)uit->second * Q + qit->second] = ax.to_usage(m); uqe[(size_t)uit->second * Q + qit->second] = 1; }
     }
     for (const auto& [aname, pm] : stat.account_to_partition_to_resource_map) {
       auto x = ua_ix.find({uname, aname});
       if (x == ua_ix.end()) continue;
       for (const auto& [pname, m] : pm) {
         auto pit = I.part_idx.find(pname);
-        if (pit != I.part_idx.end()) { up[(size_t)x->second * Pn + pit->second] = to_usage(m); upe[(size_t)x->second * Pn + pit->second] = 1; }
+        if (pit != I.part_idx.end()) { up[(size_t)x->second * Pn + pit->second] = ax.to_usage(m); upe[(size_t)x->second * Pn + pit->second] = 1; }
       }
     }
   }
@@ -1789,16 +1805,16 @@ void GpuNodeSelectionAlgo::CheckAndMallocMetaResource(AccountMetaSnapshot& meta,
     if (ait == acct_ix.end()) continue;
     for (const auto& [qname, m] : stat.qos_to_resource_map) {
       auto qit = qos_ix.find(qname);
-      if (qit != qos_ix.end()) { aq[(size_t)ait->second * Q + qit->second] = to_usage(m); aqe[(size_t)ait->second * Q + qit->second] = 1; }
+      if (qit != qos_ix.end()) { aq[(size_t)ait->second * Q + qit->second] = ax.to_usage(m); aqe[(size_t)ait->second * Q + qit->second] = 1; }
     }
     for (const auto& [pname, m] : stat.partition_to_resource_map) {
       auto pit = I.part_idx.find(pname);
-      if (pit != I.part_idx.end()) { ap[(size_t)ait->second * Pn + pit->second] = to_usage(m); ape[(size_t)ait->second * Pn + pit->second] = 1; }
+      if (pit != I.part_idx.end()) { ap[(size_t)ait->second * Pn + pit->second] = ax.to_usage(m); ape[(size_t)ait->second * Pn + pit->second] = 1; }
     }
   }
   for (const auto& [qname, m] : meta.qos_meta) {
     auto qit = qos_ix.find(qname);
-    if (qit != qos_ix.end()) qu[qit->second] = to_usage(m);
+    if (qit != qos_ix.end()) qu[qit->second] = ax.to_usage(m);
   }
   cns_limit_tables t{};
   t.num_users = U; t.num_user_accts = UA; t.num_accounts = A; t.num_qos = Q; t.num_partitions = Pn; t.num_part_limits = (uint32_t)plims.size();
@@ -1898,59 +1914,13 @@ bool GpuNodeSelectionAlgo::CheckSubmitLimits(const std::vector<SubmitRequest>& r
   const size_t J = requests.size();
   if (J == 0) { status_ = 0; error_.clear(); return true; }
 
-  // ---- dense indices (sorted names: deterministic), as CheckAndMallocMetaResource ----
-  auto index_of = [](const auto& m) {
-    std::map<std::string, uint32_t> ix;
-    for (const auto& kv : m) ix.emplace(kv.first, 0);
-    uint32_t n = 0;
-    for (auto& kv : ix) kv.second = n++;
-    return ix;
-  };
-  const std::map<std::string, uint32_t> qos_ix = index_of(meta.qos), acct_ix = index_of(meta.account_parent), user_ix = index_of(meta.user_accounts);
-  std::map<std::pair<std::string, std::string>, uint32_t> ua_ix;
-  for (const auto& [u, accts] : meta.user_accounts)
-    for (const auto& [a, lims] : accts) ua_ix.emplace(std::make_pair(u, a), 0);
-  { uint32_t n = 0; for (auto& kv : ua_ix) kv.second = n++; }
-  const uint32_t Q = (uint32_t)qos_ix.size(), A = (uint32_t)acct_ix.size(), U = (uint32_t)user_ix.size(), UA = (uint32_t)ua_ix.size();
-  const uint32_t Pn = (uint32_t)I.part_idx.size();
-  std::vector<std::string> part_name(Pn);
-  for (const auto& [name, ix] : I.part_idx) part_name[ix] = name;
-
-  auto to_tres = [&](const ResourceView& v) {
-    cns_tres t{};
-    t.cpu_raw = v.cpu_count.raw;
-    t.mem = v.memory_bytes;
-    for (const auto& [name, gc] : v.gres_map) {
-      auto nit = I.name_id.find(name);
-      if (nit == I.name_id.end()) continue;
-      t.name_mask |= 1u << nit->second;
-      t.name_total[nit->second] = gc.total;
-      for (const auto& [type, cnt] : gc.specified) {
-        const int c = I.class_of(name, type);
-        if (c < 0) continue;
-        t.class_mask |= 1u << c;
-        t.class_count[c] = cnt;
-      }
-    }
-    return t;
-  };
-  auto to_usage = [&](const MetaResource& m) {
-    cns_usage u{};
-    u.cpu_raw = m.resource.cpu_count.raw;
-    u.mem = m.resource.memory_bytes;
-    u.wall_sec = m.wall_time;
-    u.jobs_count = m.jobs_count;
-    for (const auto& [name, gc] : m.resource.gres_map) {
-      auto nit = I.name_id.find(name);
-      if (nit == I.name_id.end()) continue;
-      u.name_total[nit->second] = gc.total;
-      for (const auto& [type, cnt] : gc.specified) {
-        const int c = I.class_of(name, type);
-        if (c >= 0) u.class_count[c] = cnt;
-      }
-    }
-    return u;
-  };
+  // ---- dense indices (sorted names: deterministic), the conversions and the parent table ----
+  const AccountIndex ax(I, meta);
+  const auto &qos_ix = ax.qos_ix, &acct_ix = ax.acct_ix, &user_ix = ax.user_ix;
+  const auto& ua_ix = ax.ua_ix;
+  const uint32_t Q = ax.Q, A = ax.A, U = ax.U, UA = ax.UA, Pn = ax.Pn;
+  const std::vector<std::string>& part_name = ax.part_name;
+  const std::vector<uint32_t>& parent = ax.parent;
 
   // ---- limits ----
   std::vector<cns_submit_qos> qos(Q);
@@ -1961,34 +1931,17 @@ bool GpuNodeSelectionAlgo::CheckSubmitLimits(const std::vector<SubmitRequest>& r
     d.max_jobs_per_user = s.max_jobs_per_user; d.max_jobs_per_account = s.max_jobs_per_account; d.max_jobs = s.max_jobs;
     d.deny_on_limit = s.deny_on_limit ? 1u : 0u;
     d.max_cpus_per_user_raw = s.max_cpus_per_user.raw; d.max_wall_sec = s.max_wall; d.max_time_limit_per_job_sec = s.max_time_limit_per_job;
-    d.max_tres = to_tres(s.max_tres); d.max_tres_per_user = to_tres(s.max_tres_per_user); d.max_tres_per_account = to_tres(s.max_tres_per_account);
-  }
-  std::vector<uint32_t> parent(A, CNS_LIM_NONE);
-  for (const auto& [name, ix] : acct_ix) {
-    const std::string& p = meta.account_parent.at(name);
-    if (!p.empty()) { auto it = acct_ix.find(p); if (it != acct_ix.end()) parent[ix] = it->second; }
+    d.max_tres = ax.to_tres(s.max_tres); d.max_tres_per_user = ax.to_tres(s.max_tres_per_user); d.max_tres_per_account = ax.to_tres(s.max_tres_per_account);
   }
   std::vector<cns_submit_part_limit> plims;
   auto add_plim = [&](const PartitionResourceLimit& s) {
     cns_submit_part_limit d{};
-    d.max_submit_jobs = s.max_submit_jobs; d.max_wall_duration_per_job_sec = s.max_wall_duration_per_job; d.max_tres_per_job = to_tres(s.max_tres_per_job);
+    d.max_submit_jobs = s.max_submit_jobs; d.max_wall_duration_per_job_sec = s.max_wall_duration_per_job; d.max_tres_per_job = ax.to_tres(s.max_tres_per_job);
     plims.push_back(d);
     return (uint32_t)plims.size() - 1;
   };
-  std::vector<uint32_t> upl((size_t)UA * Pn, CNS_LIM_NONE), apl((size_t)A * Pn, CNS_LIM_NONE);
-  for (const auto& [key, x] : ua_ix)
-    for (const auto& [pname, lim] : meta.user_accounts.at(key.first).at(key.second)) {
-      auto pit = I.part_idx.find(pname);
-      if (pit != I.part_idx.end()) upl[(size_t)x * Pn + pit->second] = add_plim(lim);
-    }
-  for (const auto& [aname, lims] : meta.account_partition_limits) {
-    auto ait = acct_ix.find(aname);
-    if (ait == acct_ix.end()) continue;
-    for (const auto& [pname, lim] : lims) {
-      auto pit = I.part_idx.find(pname);
-      if (pit != I.part_idx.end()) apl[(size_t)ait->second * Pn + pit->second] = add_plim(lim);
-    }
-  }
+  std::vector<uint32_t> upl, apl;
+  ax.fill_part_limits(meta, upl, apl, add_plim);
   // ---- usage, submit counts, exists (an entity is in its map or not; a missing nested entry is a zero entry) ----
   std::vector<cns_usage> uq((size_t)U * Q), aq((size_t)A * Q), qu(Q);
   std::vector<uint32_t> uqs((size_t)U * Q, 0), ups((size_t)UA * Pn, 0), aqs((size_t)A * Q, 0), aps((size_t)A * Pn, 0), qs(Q, 0);
@@ -1999,7 +1952,7 @@ bool GpuNodeSelectionAlgo::CheckSubmitLimits(const std::vector<SubmitRequest>& r
     uex[uit->second] = 1;
     for (const auto& [qname, m] : stat.qos_to_resource_map) {
       auto qit = qos_ix.find(qname);
-      if (qit != qos_ix.end()) { uq[(size_t)uit->second * Q + qit->second] = to_usage(m); uqs[(size_t)uit->second * Q + qit->second] = m.submit_jobs_count; }
+      if (qit != qos_ix.end()) { uq[(size_t)uit->second * Q + qit->second] = ax.to_usage(m); uqs[(size_t)uit->second * Q + qit->second] = m.submit_jobs_count; }
     }
     for (const auto& [aname, pm] : stat.account_to_partition_to_resource_map) {
       auto x = ua_ix.find({uname, aname});
@@ -2016,7 +1969,7 @@ bool GpuNodeSelectionAlgo::CheckSubmitLimits(const std::vector<SubmitRequest>& r
     aex[ait->second] = 1;
     for (const auto& [qname, m] : stat.qos_to_resource_map) {
       auto qit = qos_ix.find(qname);
-      if (qit != qos_ix.end()) { aq[(size_t)ait->second * Q + qit->second] = to_usage(m); aqs[(size_t)ait->second * Q + qit->second] = m.submit_jobs_count; }
+      if (qit != qos_ix.end()) { aq[(size_t)ait->second * Q + qit->second] = ax.to_usage(m); aqs[(size_t)ait->second * Q + qit->second] = m.submit_jobs_count; }
     }
     for (const auto& [pname, m] : stat.partition_to_resource_map) {
       auto pit = I.part_idx.find(pname);
@@ -2025,7 +1978,7 @@ bool GpuNodeSelectionAlgo::CheckSubmitLimits(const std::vector<SubmitRequest>& r
   }
   for (const auto& [qname, m] : meta.qos_meta) {
     auto qit = qos_ix.find(qname);
-    if (qit != qos_ix.end()) { qu[qit->second] = to_usage(m); qs[qit->second] = m.submit_jobs_count; qex[qit->second] = 1; }
+    if (qit != qos_ix.end()) { qu[qit->second] = ax.to_usage(m); qs[qit->second] = m.submit_jobs_count; qex[qit->second] = 1; }
   }
   cns_submit_tables t{};
   t.num_users = U; t.num_user_accts = UA; t.num_accounts = A; t.num_qos = Q; t.num_partitions = Pn; t.num_part_limits = (uint32_t)plims.size();
@@ -2062,11 +2015,7 @@ bool GpuNodeSelectionAlgo::CheckSubmitLimits(const std::vector<SubmitRequest>& r
     user[i] = uit->second; acct[i] = ait->second; qosv[i] = qit->second;
     if (xit != ua_ix.end()) ua[i] = xit->second;                           // else :703-708 decides, in its place
   }
-  cns_job_soa js{};
-  js.num_jobs = J;
-  js.partition = B.part.data(); js.time_limit_sec = B.L.data(); js.node_cpu_raw = B.ncpu.data(); js.node_mem = B.nmem.data();
-  js.task_cpu_raw = B.tcpu.data(); js.task_mem = B.tmem.data(); js.node_num = B.k.data(); js.ntasks = B.nt.data();
-  js.gres_total = B.gtot.data(); js.gres_spec = B.gspec.data();
+  const cns_job_soa js = B.soa(J);   // (cns_check_submissions reads the partition, the time limit, the requests and the GRES counts only)
   cns_submit_keys ks{user.data(), ua.data(), acct.data(), qosv.data(), count.data(), skip.data()};
   std::vector<uint8_t> code(J);
   std::vector<int64_t> tlo(J);

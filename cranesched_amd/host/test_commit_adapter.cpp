@@ -16,16 +16,13 @@
 #include <string>
 
 #include "NodeSelectionAlgo.h"
+#include "adapter_test.h"
 #include "../../include/crane_gpu_commit/commit_check.h"
 
 using namespace crane;
 using Event = GpuNodeSelectionAlgo::ResReduceEvent;
 using ResvNow = GpuNodeSelectionAlgo::ResvMetaNow;
 
-static int g_fail = 0;
-#define CHECK(c) do { if (!(c)) { printf("CHECK failed line %d: %s\n", __LINE__, #c); ++g_fail; } } while (0)
-
-static const uint64_t G = 1ull << 30;
 static const TimeSec NOW = 1000000;
 
 static CranedMeta node(const std::string& id, int cores, uint64_t mem_gib) {
@@ -166,13 +163,6 @@ static int hand_cases(GpuNodeSelectionAlgo& algo) {
   printf("hand cases: %d failures\n", g_fail);
   return g_fail;
 }
-
-struct Rng {
-  uint64_t x;
-  uint64_t operator()() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; }
-};
-
-static double median(std::vector<double> v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; }
 
 static int bench(GpuNodeSelectionAlgo& algo, size_t J, int N) {
   const int P = 8;

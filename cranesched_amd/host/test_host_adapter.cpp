@@ -14,12 +14,10 @@
 #include <string>
 
 #include "NodeSelectionAlgo.h"
+#include "adapter_test.h"
 #include "../../include/crane_gpu/node_select.h"   // cns_group_info (several devices)
 
 using namespace crane;
-
-static int g_fail = 0;
-#define CHECK(c) do { if (!(c)) { printf("CHECK failed line %d: %s\n", __LINE__, #c); ++g_fail; } } while (0)
 
 static CranedMeta node(const std::string& id, int cores, uint64_t mem_gib) {
   CranedMeta m;

@@ -10,12 +10,10 @@
 #include <string>
 
 #include "NodeSelectionAlgo.h"
+#include "adapter_test.h"
 #include "../../include/crane_gpu/node_select.h"
 
 using namespace crane;
-
-static int g_fail = 0;
-#define CHECK(c) do { if (!(c)) { printf("CHECK failed line %d: %s\n", __LINE__, #c); ++g_fail; } } while (0)
 
 static CranedMeta node(const std::string& id, int cores, uint64_t mem_gib) {
   CranedMeta m;
@@ -25,11 +23,6 @@ static CranedMeta node(const std::string& id, int cores, uint64_t mem_gib) {
   m.res_total.memory_bytes = m.res_total.memory_sw_bytes = mem_gib << 30;
   return m;
 }
-
-struct Rng {
-  uint64_t x;
-  uint64_t operator()() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; }
-};
 
 static const char* const kParts[3] = {"P0", "P1", "ALL"};
 // job `id` of the stream `r`: the same call sequence gives the same job (the queue is built twice: once per algorithm object)

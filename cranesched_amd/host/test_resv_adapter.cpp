@@ -13,14 +13,12 @@
 #include <string>
 
 #include "NodeSelectionAlgo.h"
+#include "adapter_test.h"
 #include "../../include/crane_gpu_resv/resv_probe.h"
 
 using namespace crane;
 using Algo = GpuNodeSelectionAlgo;
 using Names = std::vector<CranedId>;
-
-static int g_fail = 0;
-#define CHECK(c) do { if (!(c)) { printf("CHECK failed line %d: %s\n", __LINE__, #c); ++g_fail; } } while (0)
 
 static CranedMeta node(const std::string& id, int cores = 8) {
   CranedMeta m;

@@ -16,14 +16,10 @@
 #include <string>
 
 #include "NodeSelectionAlgo.h"
+#include "adapter_test.h"
 #include "../../include/crane_gpu_submit/submit_limits.h"
 
 using namespace crane;
-
-static int g_fail = 0;
-#define CHECK(c) do { if (!(c)) { printf("CHECK failed line %d: %s\n", __LINE__, #c); ++g_fail; } } while (0)
-
-static const uint64_t G = 1ull << 30;
 
 static CranedMeta node(const std::string& id, int cores, uint64_t mem_gib) {
   CranedMeta m;
@@ -125,11 +121,6 @@ static int hand_cases(GpuNodeSelectionAlgo& algo) {
 }
 
 // ---- --bench: the dense arrays, the loop that restates the reference, the device call ------------------------------------------------------
-struct Rng {
-  uint64_t x;
-  uint64_t operator()() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; }
-};
-static double median(std::vector<double> v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; }
 
 struct View { int64_t cpu; uint64_t mem; uint64_t nt[CNS_MAX_GRES_NAMES]; uint64_t cc[CNS_MAX_GRES_CLASSES]; };
 

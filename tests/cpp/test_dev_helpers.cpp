@@ -2,7 +2,9 @@
 // pq_emul.h) against the oracle's MaskAlgebra and the real std::priority_queue.  feasible / feasible_counts run over the GRES
 // layouts of tests/gres_wide.py (a 64-slot class, 8 classes under 4 names, uneven widths ending at bit 63) and random ones,
 // with requests around 15 / 16 / the class width / 64 / 127 / 128 / 255.
+// csr_owner / sorted_contains (csr_dev.h) run against std::upper_bound / std::binary_search, with 32-bit and 64-bit offsets.
 // Build: g++ -O1 -std=c++20 tests/cpp/test_dev_helpers.cpp -o tests/cpp/test_dev_helpers
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <queue>
@@ -11,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "../../cranesched_amd/csrc/csr_dev.h"
 #include "../../cranesched_amd/csrc/pq_emul.h"
 #include "../../oracle/res_algebra.hpp"
 
@@ -85,7 +88,50 @@ static u32 edge_count(std::mt19937_64& rng, u32 w) {
   }
 }
 
+// every flat index of an offsets table (list lengths given) against std::upper_bound over the first n offsets
+template <class Off>
+static bool owner_ok(const std::vector<u32>& len) {
+  std::vector<Off> off(len.size() + 1, 0);
+  for (size_t l = 0; l < len.size(); ++l) off[l + 1] = off[l] + len[l];
+  const u32 n = (u32)len.size();
+  for (Off i = 0; i < off[n]; ++i) {
+    const u32 want = (u32)(std::upper_bound(off.begin(), off.begin() + n, i) - off.begin()) - 1;
+    if (csr_owner(off.data(), n, i) != want || off[want] > i || off[want + 1] <= i) return false;
+  }
+  return true;
+}
+
+// every x from below the least to above the largest element of the ascending a[b, e), inside a longer array
+template <class Off>
+static bool contains_ok(const std::vector<u32>& a, Off b, Off e) {
+  const u32 lo = b < e ? a[b] - 1 : 0, hi = b < e ? a[e - 1] + 1 : 4;
+  for (u32 x = lo; x <= hi; ++x)
+    if (sorted_contains(a.data(), b, e, x) != std::binary_search(a.begin() + b, a.begin() + e, x)) return false;
+  return true;
+}
+
+static int test_csr() {
+  std::mt19937_64 rng(20250612);
+  std::vector<std::vector<u32>> tables = {
+      {5}, {1}, {4, 0, 0, 0}, {0, 0, 0, 4}, {0, 0, 3, 2}, {2, 0, 0, 0, 3}, {2, 3, 0, 0}, {0, 0, 1, 0, 0, 2, 0, 0}, {1, 1, 1, 1, 1, 1, 1, 1, 1}};
+  for (int it = 0; it < 500; ++it) {
+    std::vector<u32> len(1 + rng() % 9);
+    for (u32& l : len) l = rng() % 3 ? (u32)(rng() % 21) : 0;
+    tables.push_back(len);
+  }
+  for (size_t t = 0; t < tables.size(); ++t)
+    if (!owner_ok<u32>(tables[t]) || !owner_ok<u64>(tables[t])) { printf("FAIL csr_owner table=%zu\n", t); return 1; }
+  for (u32 len : {0u, 1u, 2u, 3u, 4u, 7u, 8u}) {
+    std::vector<u32> a = {1, 3};   // two entries in front of the range and two behind it that the search must not see
+    for (u32 i = 0; i < len; ++i) a.push_back(10 + 3 * i + (u32)(rng() % 3));
+    a.push_back(10); a.push_back(11);
+    if (!contains_ok<u32>(a, 2u, 2u + len) || !contains_ok<u64>(a, (u64)2, (u64)2 + len)) { printf("FAIL sorted_contains len=%u\n", len); return 1; }
+  }
+  return 0;
+}
+
 int main() {
+  if (test_csr()) return 1;
   std::mt19937_64 rng(12345);
   std::vector<std::pair<ora::GresLayout, int>> layouts = {
       {layout_of({0, 0, 1}, {0, 4, 8}, {4, 4, 8}), 400000},                                         // tests/helpers.py: 16 slots
