@@ -256,7 +256,7 @@ int cns_run_limits_resident(cns_handle* h) {
   bool used_seq = false;
   if (nb) {
     hipLaunchKernelGGL(k_lim_flags, dim3(nb), dim3(256), 0, h->stream, P);
-    hipLaunchKernelGGL(k_lim_scan, dim3(1), dim3(1024), 0, h->stream, P, nb);
+    hipLaunchKernelGGL(k_lim_scan, dim3(1), dim3(kLimScanThreads), 0, h->stream, P, nb);
     HIPCHK(h, hipMemcpyAsync(res, b[21].p, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));   // M sizes the item stream of the parallel pass
   }
@@ -315,7 +315,7 @@ int cns_run_limits_resident(cns_handle* h) {
       ++rounds;
       HIPCHK(h, hipMemsetAsync(ctr + 3, 0, 8, h->stream));
       hipLaunchKernelGGL(k_par_tails, cg, dim3(256), 0, h->stream, R);
-      hipLaunchKernelGGL(k_par_carry, dim3(1), dim3(1024), 0, h->stream, R);
+      hipLaunchKernelGGL(k_par_carry, dim3(1), dim3(kParRowGroups * 16), 0, h->stream, R);
       hipLaunchKernelGGL(k_par_eval<false>, cg, dim3(256), 0, h->stream, R);
       hipLaunchKernelGGL(k_par_update, jg, dim3(256), 0, h->stream, R);
       HIPCHK(h, hipMemcpyAsync(&und, ctr + 3, 8, hipMemcpyDeviceToHost, h->stream));
@@ -323,7 +323,7 @@ int cns_run_limits_resident(cns_handle* h) {
     }
     if (und == 0) {  // every job decided: exact sums -> reasons and the usage tables after the pass
       hipLaunchKernelGGL(k_par_tails, cg, dim3(256), 0, h->stream, R);
-      hipLaunchKernelGGL(k_par_carry, dim3(1), dim3(1024), 0, h->stream, R);
+      hipLaunchKernelGGL(k_par_carry, dim3(1), dim3(kParRowGroups * 16), 0, h->stream, R);
       hipLaunchKernelGGL(k_par_eval<true>, cg, dim3(256), 0, h->stream, R);
       hipLaunchKernelGGL(k_par_finish, jg, dim3(256), 0, h->stream, R);
     } else {
@@ -375,6 +375,17 @@ int cns_apply_run_limits(cns_handle* h, const cns_limit_job_soa* jobs, uint8_t* 
 int cns_get_limit_timing(const cns_handle* h, cns_limit_timing* t) {
   if (!h || !t) return CNS_ERR_INVALID_ARG;
   *t = h->lim_timing;
+  return CNS_OK;
+}
+
+int cns_limits_shape(uint32_t* min_item_chunk, uint32_t* num_chunks, uint32_t* batch, uint32_t* carry_row_chunks, uint32_t* max_rounds,
+                     uint32_t* scan_jobs) {
+  if (min_item_chunk) *min_item_chunk = kParMinChunk;
+  if (num_chunks) *num_chunks = kParChunks;
+  if (batch) *batch = kParBatch;
+  if (carry_row_chunks) *carry_row_chunks = kParRowChunks;
+  if (max_rounds) *max_rounds = kLimMaxRounds;
+  if (scan_jobs) *scan_jobs = kLimScanJobs;
   return CNS_OK;
 }
 

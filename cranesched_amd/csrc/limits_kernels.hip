@@ -38,6 +38,8 @@ enum LimQosFlag : u32 { kLqUserJobsUnl = 1, kLqAcctJobsUnl = 2, kLqWallZero = 4,
 constexpr u32 kLimNeedExists = 1u << 16;   // slot flag: the usage entry must exist (QosEntryNotFound / PartitionEntryNotFound)
 constexpr u32 kLimTresComps = 0xFFF9u;     // components of CheckTres_: cpu, mem, GRES
 constexpr u32 kLimNotCandidate = 255;
+constexpr u32 kLimScanThreads = 1024;                      // k_lim_scan: one workgroup
+constexpr u32 kLimScanJobs = kLimScanThreads * 256;         // jobs it covers with one block count per thread; past it a thread sums several
 
 struct LimRec {
   i64 lim[16];
@@ -101,16 +103,16 @@ __global__ __launch_bounds__(256) void k_lim_flags(const LimParams P) {
 }
 
 // exclusive scan of the per-block candidate counts (one workgroup; nb = J / 256 entries)
-__global__ __launch_bounds__(1024) void k_lim_scan(const LimParams P, u32 nb) {
-  __shared__ u64 s_sum[1024];
+__global__ __launch_bounds__(kLimScanThreads) void k_lim_scan(const LimParams P, u32 nb) {
+  __shared__ u64 s_sum[kLimScanThreads];
   const u32 t = threadIdx.x;
-  const u32 per = (nb + 1023) / 1024;
+  const u32 per = (nb + kLimScanThreads - 1) / kLimScanThreads;
   const u32 lo = t * per, hi = lo + per < nb ? lo + per : nb;
   u64 sum = 0;
   for (u32 b = lo; b < hi; ++b) sum += P.blk_cnt[b];
   s_sum[t] = sum;
   __syncthreads();
-  for (u32 d = 1; d < 1024; d <<= 1) {  // Hillis-Steele inclusive scan
+  for (u32 d = 1; d < kLimScanThreads; d <<= 1) {  // Hillis-Steele inclusive scan
     const u64 v = t >= d ? s_sum[t - d] : 0;
     __syncthreads();
     s_sum[t] += v;
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(1024) void k_lim_scan(const LimParams P, u32 nb) {
   }
   u64 run = s_sum[t] - sum;
   for (u32 b = lo; b < hi; ++b) { P.blk_off[b] = run; run += P.blk_cnt[b]; }
-  if (t == 1023) *P.total = s_sum[1023];
+  if (t == kLimScanThreads - 1) *P.total = s_sum[kLimScanThreads - 1];
 }
 
 __global__ __launch_bounds__(256) void k_lim_build(const LimParams P) {
@@ -354,6 +356,8 @@ __global__ __launch_bounds__(64) void k_lim_admit(const LimParams P) {
 constexpr u32 kParChunks = 8192;     // chunks of the sorted item stream (16 lanes walk one chunk)
 constexpr u32 kParMinChunk = 64;
 constexpr u32 kParBatch = 8;         // items loaded together by a chunk walker
+constexpr u32 kParRowGroups = 64;    // k_par_carry: row groups of 16 lanes in its one workgroup
+constexpr u32 kParRowChunks = kParChunks / kParRowGroups;   // consecutive chunks per row group
 constexpr u32 kLimMaxRounds = 64;
 
 struct ParParams {
@@ -436,13 +440,13 @@ __global__ __launch_bounds__(256) void k_par_tails(const ParParams P) {
 }
 
 // carry[c] = sum of the items since the last segment head before chunk c:  x[c] = heads[c-1] ? tails[c-1] : x[c-1] + tails[c-1]
-// one workgroup: 64 row groups of 16 lanes, each over kParChunks / 64 consecutive chunks, two sweeps
-__global__ __launch_bounds__(1024) void k_par_carry(const ParParams P) {
-  __shared__ i64 s_end[64][2][16];
-  __shared__ i64 s_in[64][2][16];
-  __shared__ uint8_t s_seen[64];
+// one workgroup: kParRowGroups row groups of 16 lanes, each over kParRowChunks consecutive chunks, two sweeps
+__global__ __launch_bounds__(kParRowGroups * 16) void k_par_carry(const ParParams P) {
+  __shared__ i64 s_end[kParRowGroups][2][16];
+  __shared__ i64 s_in[kParRowGroups][2][16];
+  __shared__ uint8_t s_seen[kParRowGroups];
   const u32 rg = threadIdx.x >> 4, comp = threadIdx.x & 15;
-  constexpr u32 R = kParChunks / 64;
+  constexpr u32 R = kParRowChunks;
   const u32 c0 = rg * R;
   for (u32 sweep = 0; sweep < 2; ++sweep) {
     i64 xL = sweep ? s_in[rg][0][comp] : 0, xU = sweep ? s_in[rg][1][comp] : 0;
@@ -456,9 +460,9 @@ __global__ __launch_bounds__(1024) void k_par_carry(const ParParams P) {
       s_end[rg][0][comp] = xL; s_end[rg][1][comp] = xU;
       if (comp == 0) s_seen[rg] = seen;
       __syncthreads();
-      if (rg == 0) {   // 64 sequential steps over the row groups
+      if (rg == 0) {   // kParRowGroups sequential steps over the row groups
         i64 yL = 0, yU = 0;
-        for (u32 r = 0; r < 64; ++r) {
+        for (u32 r = 0; r < kParRowGroups; ++r) {
           s_in[r][0][comp] = yL; s_in[r][1][comp] = yU;
           if (s_seen[r]) { yL = s_end[r][0][comp]; yU = s_end[r][1][comp]; } else { yL += s_end[r][0][comp]; yU += s_end[r][1][comp]; }
         }

@@ -52,7 +52,7 @@ COMMIT_ABI_SYMBOLS = ("cns_commit_check", "cns_commit_shape")
 # ... and include/crane_gpu_submit/submit_limits.h
 SUBMIT_ABI_SYMBOLS = ("cns_set_submit_limits", "cns_check_submissions", "cns_get_submit_usage", "cns_get_submit_timing", "cns_submit_shape")
 LIMITS_ABI_SYMBOLS = ("cns_set_run_limits", "cns_apply_run_limits", "cns_upload_limit_jobs", "cns_run_limits_resident",
-                      "cns_download_limits", "cns_get_limit_timing", "cns_get_usage")
+                      "cns_download_limits", "cns_get_limit_timing", "cns_get_usage", "cns_limits_shape")
 
 
 class EngineError(RuntimeError):
@@ -175,6 +175,12 @@ class GpuNodeSelector:
         t = lm.CnsLimitTiming()
         self._check(self._L.cns_get_limit_timing(self._h, C.byref(t)))
         return {f: getattr(t, f) for f, _ in lm.CnsLimitTiming._fields_}
+
+    def limits_shape(self):
+        """(min_item_chunk, num_chunks, batch, carry_row_chunks, max_rounds, scan_jobs): where the run-limit kernels' paths change."""
+        v = [C.c_uint32(0) for _ in range(6)]
+        self._check(self._L.cns_limits_shape(*[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def usage(self):
         """Usage tables after the last admission (what DoMallocResource_ left)."""

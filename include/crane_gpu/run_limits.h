@@ -177,6 +177,13 @@ int cns_download_limits(cns_handle* h, uint8_t* limit_reason_out, uint64_t* num_
 
 int cns_get_limit_timing(const cns_handle* h, cns_limit_timing* t);
 
+/* Where the device code's paths change (for tests that place their sizes on those seams); any pointer may be NULL.
+ * The sorted (candidate, usage record) items are walked in num_chunks chunks of max(min_item_chunk, ceil(items / num_chunks))
+ * items, `batch` items per load; the carry scan takes carry_row_chunks consecutive chunks per row group; after max_rounds
+ * bracketing rounds the ordered kernel decides; past scan_jobs jobs the candidate scan sums several block counts per thread. */
+int cns_limits_shape(uint32_t* min_item_chunk, uint32_t* num_chunks, uint32_t* batch, uint32_t* carry_row_chunks,
+                     uint32_t* max_rounds, uint32_t* scan_jobs);
+
 /* Parity / write-back: usage tables after the last admission (what DoMallocResource_ left), same shapes as in
  * cns_limit_tables; any pointer may be NULL. */
 int cns_get_usage(cns_handle* h, cns_usage* user_qos, uint8_t* user_qos_exists, cns_usage* user_part,

@@ -78,8 +78,10 @@ def _unlimited(v):                                 # :362-365
     return v["cpu"] == lm.UNLIMITED_CPU_RAW and v["mem"] == lm.MAX_JOB_MEMORY and not v["gres"]
 
 
-def run(layout, t, lj, pl):
-    """Returns (reason[J] u8, admitted).  layout: abi.GresLayout, t: LimitTables, lj: LimitJobs, pl: abi.Placements"""
+def run(layout, t, lj, pl, trace=None):
+    """Returns (reason[J] u8, admitted).  layout: abi.GresLayout, t: LimitTables, lj: LimitJobs, pl: abi.Placements
+    trace: a list that receives, for every rejected job, (job, reason, code of the user's checks, [(account, code) for every
+    account of the chain whose checks fail on the usage the job saw, from the job's account upward]): which entities fail AT ONCE."""
     Q, Pn = t.num_qos, t.num_partitions
     qos = [{"jpu": int(q["max_jobs_per_user"]), "jpa": int(q["max_jobs_per_account"]), "jobs": int(q["max_jobs"]),
             "cpu_x": int(q["max_cpus_per_user_raw"]), "wall": int(q["max_wall_sec"]),
@@ -173,6 +175,15 @@ def run(layout, t, lj, pl):
             else: r = _check_tres(use, q["tres"], 0)
         reason[i] = r
         if r:
+            if trace is not None:
+                ru = entity_qos(uq, u * Q + qi, q, True, alloc, tl) or entity_part(up, x * Pn + p, upl, q, True, alloc, tl)
+                fails = []
+                for a in chain:
+                    apl = int(t.acct_part_limit[a * Pn + p]) if t.acct_part_limit is not None else NONE
+                    c = entity_qos(aq, a * Q + qi, q, False, alloc, tl) or entity_part(ap, a * Pn + p, apl, q, False, alloc, tl)
+                    if c:
+                        fails.append((a, c))
+                trace.append((i, r, ru, fails))
             continue
         adm += 1                                         # :1067-1124
         for tab, key in [(uq, u * Q + qi), (up, x * Pn + p), (qg, qi)] + [(aq, a * Q + qi) for a in chain] + [(ap, a * Pn + p) for a in chain]:

@@ -297,19 +297,25 @@ def mode(request, monkeypatch):
     return request.param
 
 
-def _gpu_vs_oracle(engine_default, cluster, jobs, now, lay, t, lj, tag="", expect_fallback=None):
-    eng = engine_default(device=0)
+def _gpu_vs_oracle(engine_default, cluster, jobs, now, lay, t, lj, tag="", expect_fallback=None, eng=None, ref=None):
+    """eng: an open engine to run on (it stays open: several cases on one handle); ref: (placements, reason, admitted, usage) of the
+    oracle where the caller has them already (one oracle run shared by both modes)"""
+    own = eng is None
+    if own:
+        eng = engine_default(device=0)
     try:
         eng.set_nodes(cluster)
         got = eng.node_select(now, jobs)
-        ref = pyoracle.select(cluster, jobs, now)
-        assert got.diff(ref.placements) is None, tag
+        if ref is None:
+            sel = pyoracle.select(cluster, jobs, now)
+            ref = (sel.placements,) + tuple(pyoracle.run_limits(lay, t, lj, sel.placements))
+        pl_ref, r_ref, a_ref, u_ref = ref
+        assert got.diff(pl_ref) is None, tag
         eng.set_run_limits(t)
         reason, adm = eng.apply_run_limits(lj)
         usage = eng.usage()
-        r_ref, a_ref, u_ref = pyoracle.run_limits(lay, t, lj, ref.placements)
         bad = np.nonzero(reason != r_ref)[0]
-        assert bad.size == 0, f"{tag}: job {bad[0]}: gpu {lm.LIMIT_REASON_STR[int(reason[bad[0]])]!r} oracle {lm.LIMIT_REASON_STR[int(r_ref[bad[0]])]!r}"
+        assert bad.size == 0, f"{tag}: {bad.size} jobs differ, first job {bad[0]}: gpu {lm.LIMIT_REASON_STR[int(reason[bad[0]])]!r} oracle {lm.LIMIT_REASON_STR[int(r_ref[bad[0]])]!r}"
         assert adm == a_ref
         for f in usage.__dataclass_fields__:
             assert np.array_equal(getattr(usage, f), getattr(u_ref, f)), f"{tag}: usage table {f} differs"
@@ -323,7 +329,8 @@ def _gpu_vs_oracle(engine_default, cluster, jobs, now, lay, t, lj, tag="", expec
         assert np.array_equal(reason2, reason) and adm2 == adm
         return reason, usage
     finally:
-        eng.close()
+        if own:
+            eng.close()
 
 
 @pytest.mark.gpu
