@@ -7,7 +7,7 @@
 
 static int commit_impl(cns_handle* h, const cns_commit_events* ev, const cns_commit_jobs* jb, const cns_commit_out* out, double* kernel_ms) {
   const u64 J = jb->num_jobs;
-  const u32 N = h->N, V = h->V;
+  const u32 N = h->lay.N, V = h->rlay.V;
   const u32 E = ev ? ev->num_node_events : 0, A = ev ? ev->num_affected_resv : 0;
   if (J && (!jb->time_limit_sec || !out->code)) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: missing array");
 

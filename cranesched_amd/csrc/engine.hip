@@ -43,6 +43,7 @@
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 #include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
 #include "csr_host.inc"        // the CSR rules of the callers' lists: offsets, sorted lists without a repeat (no HIP in there either)
+#include "snapshot_host.inc"   // the layout of a snapshot: groups, refusals, slots, reservations, node types, running entries (no HIP in there either)
 #include "buf_slots.h"         // the slots of cns_engine's per-feature buffer sets
 
 using namespace cns;
@@ -58,8 +59,9 @@ constexpr u32 kGiantPartSlots = 262144;   // one partition that shares no node (
 constexpr u32 kGiantGroupSlots = 524288;  // a group of partitions that share nodes (ALL over 262 144 nodes + subsets that cover it once more)
 static_assert(kGiantPartSlots <= kGiantGroupSlots && kGiantGroupSlots <= w8::WideInfo::giant_mem_slots, "k_mem's giant masks hold the widest group");
 static_assert(w8::WideInfo::mem_slots >= w64::WideInfo::lanes * w64::WideInfo::npl_max, "k_wide's widest tile stays below k_mem's ordinary masks");
-// the widest partition / group a snapshot may hold (cns_set_nodes refuses the others with CNS_PART_REFUSED_WIDTH)
-inline u32 width_cap(bool group) { return group ? kGiantGroupSlots : kGiantPartSlots; }
+// the widest partition / group a snapshot may hold (cns_set_nodes refuses the others with CNS_PART_REFUSED_WIDTH), and its node types
+const cns_snapshot::Caps kCaps{kGiantPartSlots, kGiantGroupSlots, CNS_MAX_NODE_TYPES};
+static_assert(cns_snapshot::kNone == kNone && cns_snapshot::kTlCap == kTlCap && CNS_MAX_NODE_TYPES == CNS_MAX_NODE_TYPES_DEV, "snapshot_host.inc: the kernels' constants");
 
 std::string g_create_error;
 
@@ -115,39 +117,18 @@ struct cns_engine {
   hipEvent_t ev2[2] = {nullptr, nullptr};
   std::string err;
 
-  // cluster (host copies)
-  u32 N = 0, P = 0, S = 0, T = 0, max_np = 0;
-  bool big_nodes = false;  // any GRES or > 64 cores (48-byte node record in the traffic model)
-  std::vector<u32> part_off, slot_node, orig_pos_slot;  // orig_pos_slot: caller's part_nodes position -> slot or kNone
-  std::vector<u32> node_slot;                 // node -> its PRIMARY slot (the one whose NodeBlock holds the shared time map)
-  // Overlapping partitions (one NodeState per craned shared by every partition that lists it, one cost per partition:
-  // JobScheduler.cpp:6585-6615, JobScheduler.h:498-516): partitions connected through shared nodes form ONE engine
-  // partition (workgroup) that runs their jobs in queue order; a node then has one slot per member partition.
-  u32 Pu = 0;                                 // partitions of the caller
-  bool shared = false;                        // some node belongs to several partitions
+  // the snapshot (host copies, snapshot_host.inc): what cns_set_nodes, cns_set_reservations and cns_set_running derived from the caller's
+  // arrays.  Each is replaced whole, and only by a call that passed validation.
+  cns_snapshot::Layout lay;                   // partitions and groups, the slots of the real nodes
+  cns_snapshot::ResvLayout rlay;              // ... extended by the reservations' virtual partitions: the slot list the device runs on
+  cns_snapshot::RunLayout run;                // the running allocations grouped by slot (cns_select_preempt reads the entries)
   u32 num_cus = 0;                            // compute units of the device (0: unknown); k_wide needs one per workgroup, all resident at once
-  std::vector<u32> upart_eng, upart_size;     // caller's partition -> engine partition, its schedulable node count
-  std::vector<uint8_t> refused_probe;         // the statuses of the last cns_set_nodes call, also when it failed because EVERY partition was refused
-  std::vector<uint8_t> upart_refused;         // caller's partition -> cns_partition_status: != 0: its group is outside the engine's limits — its jobs get
-                                              // CNS_REASON_ENGINE_REFUSED, every other partition is served (cns_get_partition_status)
-  std::vector<uint8_t> upart_tag;             // ... and its member tag inside that engine partition
-  std::vector<std::vector<u32>> node_slots;   // node -> all its slots
-  std::vector<uint8_t> slot_tag;              // slot -> member tag
+  std::vector<uint8_t> refused_probe;         // the statuses of the last cns_set_nodes call that computed them: a success, or the failure because EVERY
+                                              // partition was refused (empty after any other failure)
   DevBuf d_slot_block, d_sib_off, d_sib, d_type_tag, d_jtag;
   GresDev gres{};
   bool have_nodes = false, have_jobs = false, have_run = false;
 
-  // layout: slots [0, S_real) are the partitions' nodes, slots [S_real, S) the virtual nodes of the reservations
-  // (one extra "partition" P_real + v per reservation v, JobScheduler.cpp:6657-6668)
-  u32 P_real = 0, S_real = 0, V = 0;
-  std::vector<Res> node_total;                       // res_total per node (host copy)
-  std::vector<Res> slot_total;                       // res_total per slot (virtual slots: the reserved share)
-  std::vector<i64> slot_end;                         // end of the slot's time map (INF, or the reservation's end)
-  std::vector<i64> resv_start, resv_end;             // per reservation
-  std::vector<std::map<u32, u32>> resv_node_slot;    // per reservation: node -> slot
-  std::vector<u32> rv_off;                           // [S+1] reservation entries touching a REAL slot
-  std::vector<i64> rv_start, rv_endt;
-  std::vector<Res> rv_res;
   DevBuf d_slot_total, d_slot_end, d_slot_type, d_rv_off, d_rv_start, d_rv_end, d_rv_res, d_first_resv, d_resv_se;
   // device buffers
   DevBuf d_part_off, d_slot_node, d_type_total, d_blocks, d_cost, d_fcpu,
@@ -161,7 +142,6 @@ struct cns_engine {
   u32 host_threads = 0;                         // cns_set_host_threads (0: CNS_HOST_THREADS, else up to 16)
   const u64* place_off = nullptr;               // [J + 1] first placement record per job (in h_place)
   struct ResOff { size_t start, cpu, mem, clo, chi, gres, node, ntasks, reason, c2, c3, total; } ro{};
-  bool wide_cores = false;   // a node of the snapshot has a core id above 127: the results carry the core_w2 / core_w3 planes
   // what-if probes against the final state of the last cycle (probe_host.inc): table, results and scratch in buffers of their own
   DevBuf d_pb[PB_COUNT];
   ResOff pro{};
@@ -191,7 +171,6 @@ struct cns_engine {
   cns_timing timing{};
   std::string last_kernel;
   i64 last_now = 0;
-  std::vector<u32> eng_members;                 // engine partition -> number of caller partitions it runs (> 1: they share nodes)
   std::vector<u32> job_part;                    // pending job (queue index) -> engine partition (kNone: not given to the ordered loop)
   std::vector<u64> part_jobs;                   // engine partition -> jobs of the uploaded queue that reach its ordered loop
   std::vector<uint8_t> pre_part;                // cycle with preemption: engine partition has a pending job whose qos may preempt
@@ -199,7 +178,6 @@ struct cns_engine {
   DevBuf d_params3, d_pmap_c, d_wide_mem;       // the serial-only launch of k_wide (groups wider than k_select's tile)
   DevBuf d_giant;                               // ... its GiantCtl blocks when it runs with helper workgroups (k_giant)
   DevBuf d_flen, d_tag_off, d_tag_base;         // ... its compact map lengths, and the slot range of every member partition of a group
-  std::vector<u32> tag_off, tag_base;
   // several devices (group_host.inc): this engine's rank in a communicator, the all-gathered results of every rank
   void* comm = nullptr;                         // ncclComm_t
   u32 comm_nranks = 0, comm_rank = 0;
@@ -216,9 +194,6 @@ struct cns_engine {
   DevBuf d_lim[29], d_limpar[17];
   DevBuf d_step[13];  // step scheduler (steps_host.inc)
   // preemption (include/crane_gpu/preempt.h): what cns_set_running kept of the running set, and the cycle's tables
-  u32 R = 0;                                    // running jobs of the last cns_set_running
-  std::vector<u32> ent_job, ent_slot;           // slot-grouped allocation entry d -> running job, slot
-  std::vector<i64> ent_end;                     // ... -> end time as handed in
   std::set<void*> host_bufs;                    // page-locked host buffers handed out by cns_host_alloc
   bool pre_active = false;                      // the next run is a cycle with preemption (general path of k_select only)
   PreParams pre_params{};
@@ -313,9 +288,9 @@ struct RunKnobs {
 // (the probes fill a block without knobs: no selection kernel runs there)
 void fill_params(cns_engine* h, KParams& K, i64 now, const RunKnobs& kn = RunKnobs{}) {
   memset(&K, 0, sizeof K);
-  K.num_nodes = h->N; K.num_parts = h->P; K.num_slots = h->S; K.num_types = h->T;
+  K.num_nodes = h->lay.N; K.num_parts = h->rlay.P; K.num_slots = h->rlay.S; K.num_types = h->rlay.T;
   K.tl_cap = kTlCap;
-  K.wide_cores = h->wide_cores ? 1u : 0u;
+  K.wide_cores = h->lay.wide_cores ? 1u : 0u;
   K.max_jobs_per_node = h->cfg.max_job_num_per_node;
   K.now = now;
   K.max_window = h->cfg.max_time_window_sec;
@@ -343,7 +318,7 @@ void fill_params(cns_engine* h, KParams& K, i64 now, const RunKnobs& kn = RunKno
   K.rv_res = h->d_rv_res.as<Res>();
   K.first_resv = h->d_first_resv.as<i64>();
   K.resv_se = h->d_resv_se.as<i64>();
-  K.num_real_parts = h->P_real;
+  K.num_real_parts = h->lay.P_real;
   K.type_total = h->d_type_total.as<Res>();
   K.blocks = h->d_blocks.as<char>();
   K.block_stride = kBlockStride;
@@ -352,7 +327,7 @@ void fill_params(cns_engine* h, KParams& K, i64 now, const RunKnobs& kn = RunKno
   K.f_mem = h->d_fmem.as<u32>();
   K.f_cnt = h->d_fcnt.as<u64>();
   K.dip_t = h->d_dipt.as<u32>(); K.dip_cm = h->d_dipcm.as<u32>(); K.dip_g = h->d_dipg.as<u32>();
-  if (h->shared) { K.f_len = h->d_flen.as<u32>(); K.tag_off = h->d_tag_off.as<u32>(); K.tag_base = h->d_tag_base.as<u32>(); }
+  if (h->lay.shared) { K.f_len = h->d_flen.as<u32>(); K.tag_off = h->d_tag_off.as<u32>(); K.tag_base = h->d_tag_base.as<u32>(); }
   K.rn_off = h->d_rn_off.as<u32>();
   K.rn_end = h->d_rn_end.as<i64>();
   K.rn_res = h->d_rn_res.as<Res>();
@@ -366,8 +341,8 @@ void fill_params(cns_engine* h, KParams& K, i64 now, const RunKnobs& kn = RunKno
   K.o_mem = (u64*)(rb + h->ro.mem);
   K.o_clo = (u64*)(rb + h->ro.clo);
   K.o_chi = (u64*)(rb + h->ro.chi);
-  K.o_c2 = h->wide_cores ? (u64*)(rb + h->ro.c2) : nullptr;
-  K.o_c3 = h->wide_cores ? (u64*)(rb + h->ro.c3) : nullptr;
+  K.o_c2 = h->lay.wide_cores ? (u64*)(rb + h->ro.c2) : nullptr;
+  K.o_c3 = h->lay.wide_cores ? (u64*)(rb + h->ro.c3) : nullptr;
   K.o_gres = (u64*)(rb + h->ro.gres);
   K.o_node = (u32*)(rb + h->ro.node);
   K.o_ntasks = (u32*)(rb + h->ro.ntasks);
@@ -383,7 +358,7 @@ void fill_params(cns_engine* h, KParams& K, i64 now, const RunKnobs& kn = RunKno
   K.giant_ctl = nullptr; K.giant_nh = 0; K.pad_gnh = 0;
   K.pre = h->pre_active ? h->pre_params : PreParams{};
   K.gres = h->gres;
-  if (h->shared) {
+  if (h->lay.shared) {
     K.slot_block = h->d_slot_block.as<u32>(); K.sib_off = h->d_sib_off.as<u32>(); K.sib = h->d_sib.as<u32>();
     K.slot_tag = h->d_type_tag.as<uint8_t>();
   }
@@ -495,7 +470,7 @@ Launched launch_wide(cns_engine* h, const KParams& K, const LaunchCtx& L, const 
   const char* kname = "";
   const void* fn = W::pick(W::lanes * c.width, &kname, c.windows);
   const bool last_in_hbm = c.width > W::last_in_lds_rows;   // 8 / 16 rows per lane: the home workgroup's last-task table does not fit the LDS
-  return launch_wide_family(fn, c, K, L, h->num_cus, {{&h->d_wide, (size_t)h->P * W::ctl_bytes}, {&h->d_wide_last, last_in_hbm ? (size_t)h->P * W::lanes * W::npl_max * sizeof(u32) : 0}},
+  return launch_wide_family(fn, c, K, L, h->num_cus, {{&h->d_wide, (size_t)h->rlay.P * W::ctl_bytes}, {&h->d_wide_last, last_in_hbm ? (size_t)h->rlay.P * W::lanes * W::npl_max * sizeof(u32) : 0}},
                             false, [&](KParams& K2) {
                               K2.wide_ctl = h->d_wide.as<char>();
                               K2.wide_aux = c.extra;
@@ -514,7 +489,7 @@ Launched launch_serial(cns_engine* h, const KParams& K, const LaunchCtx& L, cons
   using W = w8::WideInfo;
   const bool giant = c.family == cns_plan::Family::Giant;
   const void* fn = c.giant_masks ? (const void*)w8::k_wide<1, false, w8::kWMemWordsGiant> : (const void*)w8::k_wide<1, false>;
-  return launch_wide_family(fn, c, K, L, h->num_cus, {{&h->d_wide_mem, (size_t)h->P * W::ctl_bytes}, {&h->d_giant, giant ? (size_t)h->P * sizeof(w8::GiantCtl) : 0}},
+  return launch_wide_family(fn, c, K, L, h->num_cus, {{&h->d_wide_mem, (size_t)h->rlay.P * W::ctl_bytes}, {&h->d_giant, giant ? (size_t)h->rlay.P * sizeof(w8::GiantCtl) : 0}},
                             true, [&](KParams& K2) {
                               K2.wide_ctl = h->d_wide_mem.as<char>();
                               K2.serial_only = 1;
@@ -555,101 +530,58 @@ int run_launch(cns_engine* h, const KParams& K, hipStream_t stream, const KParam
   return fail(h, CNS_ERR_UNSUPPORTED, PL.exhausted);
 }
 
-// Everything that depends on the slot list (real + virtual): per-slot res_total / time-map end, node types
-// (= distinct res_total records), the device copies and the per-slot buffers.
-int finalize_layout(cns_engine* h, const std::vector<Res>* virt_total = nullptr) {
-  const u32 S = h->S;
-  h->slot_total.resize(S);
-  h->slot_end.assign(S, INT64_MAX);
-  for (u32 q = 0; q < h->S_real; ++q) h->slot_total[q] = h->node_total[h->slot_node[q]];
-  for (u32 q = h->S_real; q < S; ++q) h->slot_total[q] = (*virt_total)[q - h->S_real];
-  for (u32 v = 0; v < h->V; ++v)
-    for (u32 q = h->part_off[h->P_real + v]; q < h->part_off[h->P_real + v + 1]; ++q) h->slot_end[q] = h->resv_end[v];
-  // (per partition / group: checked in cns_set_nodes, per reservation in cns_set_reservations — this is the backstop for k_mem's masks)
-  if (h->max_np > kGiantGroupSlots)
-    return fail(h, CNS_ERR_UNSUPPORTED, "partition with more than " + std::to_string(kGiantGroupSlots) + " schedulable (partition, node) slots");
-  std::map<std::tuple<i64, u64, u64, u64, u64, u64, u64>, u32> tmap;
-  std::vector<Res> type_total;
-  std::vector<uint8_t> slot_type(std::max<u32>(S, 1), 0);
-  h->slot_tag.resize(S, 0);   // virtual (reservation) slots: tag 0
-  for (u32 q = 0; q < S; ++q) {
-    const Res& r = h->slot_total[q];
-    auto key = std::make_tuple(r.cpu, r.mem, r.clo, r.chi, r.gres, r.c2, r.c3);
-    auto it = tmap.find(key);
-    if (it == tmap.end()) {
-      if (type_total.size() >= CNS_MAX_NODE_TYPES)
-        return fail(h, CNS_ERR_UNSUPPORTED, "more than 64 distinct res_total records (nodes + reservation shares)");
-      it = tmap.emplace(key, (u32)type_total.size()).first;
-      type_total.push_back(r);
-    }
-    slot_type[q] = (uint8_t)it->second;
-  }
-  h->T = (u32)type_total.size();
-  if (h->shared) {
-    std::vector<u32> slot_block(S), sib_off(S + 1, 0), sib;
-    for (u32 q = 0; q < S; ++q) {
-      slot_block[q] = q;
-      if (q < h->S_real) {
-        const auto& all = h->node_slots[h->slot_node[q]];
-        slot_block[q] = all.front();
-        for (u32 o : all) if (o != q) sib.push_back(o);
-      }
-      sib_off[q + 1] = (u32)sib.size();
-    }
-    if (sib.empty()) sib.push_back(0);
-    if (int rc = upload(h, h->d_slot_block, slot_block)) return rc;
-    if (int rc = upload(h, h->d_sib_off, sib_off)) return rc;
-    if (int rc = upload(h, h->d_sib, sib)) return rc;
-    if (int rc = upload(h, h->d_type_tag, h->slot_tag)) return rc;   // per slot: member partition inside the group
-  }
-  std::vector<i64> resv_se(2 * std::max<u32>(h->V, 1), 0);
-  for (u32 v = 0; v < h->V; ++v) { resv_se[2 * v] = h->resv_start[v]; resv_se[2 * v + 1] = h->resv_end[v]; }
-  if (int rc = upload(h, h->d_part_off, h->part_off)) return rc;
-  if (int rc = upload(h, h->d_slot_node, h->slot_node)) return rc;
-  if (int rc = upload(h, h->d_slot_total, h->slot_total)) return rc;
-  if (int rc = upload(h, h->d_slot_end, h->slot_end)) return rc;
-  if (int rc = upload(h, h->d_slot_type, slot_type)) return rc;
-  if (int rc = upload(h, h->d_type_total, type_total)) return rc;
-  if (int rc = upload(h, h->d_rv_off, h->rv_off)) return rc;
-  {
-    std::vector<i64> a = h->rv_start, b = h->rv_endt;
-    std::vector<Res> c = h->rv_res;
-    if (a.empty()) { a.push_back(0); b.push_back(0); c.push_back(Res{0, 0, 0, 0, 0}); }
-    if (int rc = upload(h, h->d_rv_start, a)) return rc;
-    if (int rc = upload(h, h->d_rv_end, b)) return rc;
-    if (int rc = upload(h, h->d_rv_res, c)) return rc;
-  }
-  if (int rc = upload(h, h->d_resv_se, resv_se)) return rc;
-  const size_t S1 = std::max<u32>(S, 1);
-  HIPCHK(h, h->d_blocks.ensure(S1 * kBlockStride));  // 64.6 KB per node: HBM is plentiful
-  HIPCHK(h, h->d_cost.ensure(S1 * sizeof(double)));
-  HIPCHK(h, h->d_fcpu.ensure(S1 * sizeof(int)));
-  HIPCHK(h, h->d_fmem.ensure(S1 * sizeof(u32)));
-  HIPCHK(h, h->d_fcnt.ensure(S1 * sizeof(u64)));
-  HIPCHK(h, h->d_dipt.ensure(S1 * sizeof(u32))); HIPCHK(h, h->d_dipcm.ensure(S1 * sizeof(u32))); HIPCHK(h, h->d_dipg.ensure(S1 * sizeof(u32)));
-  if (h->shared) {
-    HIPCHK(h, h->d_flen.ensure(S1 * sizeof(u32)));
-    // the virtual partitions of reservations share nothing: one range over all of their slots (their jobs carry tag 0).  Read only by
-    // k_mem (a reservation wider than k_wide's tile); the other kernels take a partition without shared nodes whole.
-    std::vector<u32> tb = h->tag_base, to = h->tag_off;
-    tb.resize(std::max<size_t>(h->P, 1), 0);
-    for (u32 p = h->P_real; p < h->P; ++p) { tb[p] = (u32)to.size(); to.push_back(0); to.push_back(h->part_off[p + 1] - h->part_off[p]); }
-    if (int rc = upload(h, h->d_tag_base, tb)) return rc;
-    if (int rc = upload(h, h->d_tag_off, to)) return rc;
-  }
-  HIPCHK(h, h->d_first_resv.ensure(S1 * sizeof(i64)));
-  HIPCHK(h, h->d_heap.ensure((size_t)(S + h->P + 1) * sizeof(HeapEnt)));
-  HIPCHK(h, h->d_bfj.ensure(S1 * sizeof(u32)));
-  HIPCHK(h, h->d_gupd.ensure(S1 * sizeof(UpdRec)));
-  HIPCHK(h, h->d_fault.ensure(4 * sizeof(u32)));
-  HIPCHK(h, h->d_prof.ensure(((size_t)(h->P + 8) * (size_t)w64::WideInfo::group * 32 + (size_t)h->P * 8 + 2048) * sizeof(u64)));   // (k_wide: blocks > partitions)
-  // no running jobs until cns_set_running
-  std::vector<u32> rn_off(S + 1, 0);
-  if (int rc = upload(h, h->d_rn_off, rn_off)) return rc;
-  HIPCHK(h, h->d_rn_end.ensure(16));
-  HIPCHK(h, h->d_rn_res.ensure(sizeof(Res)));
+// v on the device; an empty vector as one zero element (a kernel's table pointer always names something)
+template <class T>
+int upload_some(cns_engine* h, DevBuf& b, const std::vector<T>& v) {
+  static const T zero{};
+  return v.empty() ? stage(h, b, &zero, sizeof(T)) : upload(h, b, v);
+}
+
+int upload_running(cns_engine* h) {
+  if (int rc = upload(h, h->d_rn_off, h->run.rn_off)) return rc;
+  if (int rc = upload_some(h, h->d_rn_end, h->run.rn_end)) return rc;
+  if (int rc = upload_some(h, h->d_rn_res, h->run.rn_res)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return 0;
+}
+
+// The handle's layout (h->lay, h->rlay: snapshot_host.inc) on the device and the per-slot buffers sized for it.  Running jobs must be
+// set again after the layout changed: none until cns_set_running, on the host as on the device.
+int upload_snapshot(cns_engine* h) {
+  const cns_snapshot::ResvLayout& X = h->rlay;
+  (void)cns_snapshot::build_running(h->lay, X, nullptr, h->run);
+  if (h->lay.shared) {
+    if (int rc = upload(h, h->d_slot_block, X.slot_block)) return rc;
+    if (int rc = upload(h, h->d_sib_off, X.sib_off)) return rc;
+    if (int rc = upload_some(h, h->d_sib, X.sib)) return rc;
+    if (int rc = upload(h, h->d_type_tag, X.slot_tag)) return rc;   // per slot: member partition inside the group
+    if (int rc = upload(h, h->d_tag_base, X.tag_base)) return rc;
+    if (int rc = upload(h, h->d_tag_off, X.tag_off)) return rc;
+  }
+  std::vector<i64> resv_se;
+  for (u32 v = 0; v < X.V; ++v) { resv_se.push_back(X.resv_start[v]); resv_se.push_back(X.resv_end[v]); }
+  if (int rc = upload(h, h->d_part_off, X.part_off)) return rc;
+  if (int rc = upload(h, h->d_slot_node, X.slot_node)) return rc;
+  if (int rc = upload(h, h->d_slot_total, X.slot_total)) return rc;
+  if (int rc = upload(h, h->d_slot_end, X.slot_end)) return rc;
+  if (int rc = upload_some(h, h->d_slot_type, X.slot_type)) return rc;
+  if (int rc = upload(h, h->d_type_total, X.type_total)) return rc;
+  if (int rc = upload(h, h->d_rv_off, X.rv_off)) return rc;
+  if (int rc = upload_some(h, h->d_rv_start, X.rv_start)) return rc;
+  if (int rc = upload_some(h, h->d_rv_end, X.rv_endt)) return rc;
+  if (int rc = upload_some(h, h->d_rv_res, X.rv_res)) return rc;
+  if (int rc = upload_some(h, h->d_resv_se, resv_se)) return rc;
+  const size_t S1 = std::max<u32>(X.S, 1);
+  const std::pair<DevBuf*, size_t> per_slot[] = {   // (d_blocks: 64.6 KB per node — HBM is plentiful; d_flen: groups only)
+      {&h->d_blocks, kBlockStride}, {&h->d_cost, sizeof(double)}, {&h->d_fcpu, sizeof(int)}, {&h->d_fmem, sizeof(u32)}, {&h->d_fcnt, sizeof(u64)},
+      {&h->d_dipt, sizeof(u32)}, {&h->d_dipcm, sizeof(u32)}, {&h->d_dipg, sizeof(u32)}, {&h->d_first_resv, sizeof(i64)}, {&h->d_bfj, sizeof(u32)},
+      {&h->d_gupd, sizeof(UpdRec)}, {&h->d_flen, h->lay.shared ? sizeof(u32) : 0}};
+  for (const auto& [buf, elem] : per_slot)
+    if (elem) HIPCHK(h, buf->ensure(S1 * elem));
+  HIPCHK(h, h->d_heap.ensure((size_t)(X.S + X.P + 1) * sizeof(HeapEnt)));
+  HIPCHK(h, h->d_fault.ensure(4 * sizeof(u32)));
+  HIPCHK(h, h->d_prof.ensure(((size_t)(X.P + 8) * (size_t)w64::WideInfo::group * 32 + (size_t)X.P * 8 + 2048) * sizeof(u64)));   // (k_wide: blocks > partitions)
+  return upload_running(h);   // (its synchronize: resv_se is a local vector)
 }
 
 }  // namespace
@@ -720,8 +652,11 @@ void cns_destroy(cns_handle* h) {
 }
 
 static void valid_keep_nodes(cns_handle* h, const cns_node_soa* nd);   // valid_host.inc
+// The three calls of the snapshot: argument and state checks here, the layout in snapshot_host.inc (built into a local: a call that
+// fails validation leaves the handle's snapshot, host mirror and device buffers, as it was), then the uploads.
 int cns_set_nodes(cns_handle* h, const cns_node_soa* nd) {
   if (!h || !nd) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_nodes: null argument");
+  h->refused_probe.clear();
   if (!nd->cpu_total_raw || !nd->mem_total || !nd->core_lo || !nd->part_offsets || (!nd->part_nodes && nd->part_offsets[nd->num_partitions]))
     return fail(h, CNS_ERR_INVALID_ARG, "cns_set_nodes: missing array");
   if (nd->num_nodes == 0 || nd->num_partitions == 0) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_nodes: empty cluster");
@@ -729,158 +664,15 @@ int cns_set_nodes(cns_handle* h, const cns_node_soa* nd) {
   if (int rc = build_gres(h, nd->gres)) return rc;
   h->have_nodes = h->have_jobs = h->have_run = false;
   h->rq_have = false;   // (the per-node tables of cns_resvq_set_state index the nodes of the snapshot they were built for)
-  const u32 N = nd->num_nodes;
-  u32 P = nd->num_partitions;
-  std::vector<Res> total(N);
   u64 all_gres = 0;
   for (u32 c = 0; c < h->gres.num_classes; ++c) all_gres |= h->gres.class_mask[c];
-  bool big = false, wide = false;
-  for (u32 n = 0; n < N; ++n) {
-    total[n].cpu = nd->cpu_total_raw[n];
-    total[n].mem = nd->mem_total[n];
-    total[n].clo = nd->core_lo[n];
-    total[n].chi = nd->core_hi ? nd->core_hi[n] : 0;
-    total[n].c2 = nd->core_w2 ? nd->core_w2[n] : 0;
-    total[n].c3 = nd->core_w3 ? nd->core_w3[n] : 0;
-    if (total[n].c2 | total[n].c3) wide = true;
-    total[n].gres = nd->gres_slots ? nd->gres_slots[n] : 0;
-    if (total[n].gres & ~all_gres) return fail(h, CNS_ERR_INVALID_ARG, "node GRES slot outside every class");
-    if (total[n].gres || total[n].chi) big = true;
-  }
-  // partitions: schedulable nodes only, ascending dense index (= canonical cost tie-break).  Partitions that share a
-  // node are merged into one engine partition (union-find over the shared nodes); without sharing the engine
-  // partitions are the caller's, one to one.
-  const u32 total_pos = nd->part_offsets[P];
-  std::vector<std::vector<std::pair<u32, u32>>> plist(P);  // per caller partition: (node, original position)
-  std::vector<u32> uf(P);
-  for (u32 p = 0; p < P; ++p) uf[p] = p;
-  auto find = [&](u32 x) { while (uf[x] != x) { uf[x] = uf[uf[x]]; x = uf[x]; } return x; };
-  std::vector<u32> first_part(N, kNone);
-  bool shared = false;
-  // What lies outside the engine's limits refuses ONLY the partitions it touches — the group of partitions connected through shared
-  // nodes that lists the node (the reference bounds none of this: CpuSet is a std::set<uint32_t>, GRES maps are unbounded,
-  // PublicHeader.h:555-573,427-494): a node the caller flags as not expressible in this ABI's formats (cns_node_soa::unsupported:
-  // a core id >= 256, more GRES slots than the 64-bit mask holds), a node whose cpu count does not fit, the 65th distinct res_total
-  // record, a group wider than the widest tile.  Their jobs come back with CNS_REASON_ENGINE_REFUSED; the caller's CPU scheduler takes them.
-  std::vector<uint8_t> part_bad(P, 0);
-  for (u32 p = 0; p < P; ++p) {
-    if (nd->part_offsets[p + 1] < nd->part_offsets[p]) return fail(h, CNS_ERR_INVALID_ARG, "part_offsets not monotone");
-    auto& lst = plist[p];
-    for (u32 i = nd->part_offsets[p]; i < nd->part_offsets[p + 1]; ++i) {
-      u32 n = nd->part_nodes[i];
-      if (n >= N) return fail(h, CNS_ERR_INVALID_ARG, "part_nodes entry >= num_nodes");
-      if (nd->schedulable && !nd->schedulable[n]) continue;  // JobScheduler.cpp:6595
-      if ((nd->unsupported && nd->unsupported[n]) || total[n].cpu <= 0 || total[n].cpu >= 0x7FFFFFFEll) {
-        part_bad[p] = (nd->unsupported && nd->unsupported[n]) ? CNS_PART_REFUSED_NODE : CNS_PART_REFUSED_CPU;
-        if (first_part[n] == kNone) first_part[n] = p;   // (the partitions that share this node go with it)
-        else { u32 a = find(first_part[n]), b = find(p); if (a != b) uf[std::max(a, b)] = std::min(a, b); }
-        continue;
-      }
-      lst.emplace_back(n, i);
-    }
-    std::sort(lst.begin(), lst.end());
-    for (size_t i = 1; i < lst.size(); ++i)
-      if (lst[i].first == lst[i - 1].first) return fail(h, CNS_ERR_INVALID_ARG, "node listed twice in one partition");
-    for (auto& [n, pos] : lst) {
-      if (first_part[n] == kNone) first_part[n] = p;
-      else { shared = true; u32 a = find(first_part[n]), b = find(p); if (a != b) uf[std::max(a, b)] = std::min(a, b); }
-    }
-  }
-  std::vector<u32> upart_eng(P), upart_size(P);
-  std::vector<uint8_t> upart_tag(P, 0);
-  std::vector<std::vector<u32>> members;  // engine partition -> caller partitions, ascending
-  {
-    std::vector<u32> eng_of_root(P, kNone);
-    for (u32 p = 0; p < P; ++p) {
-      const u32 r = find(p);
-      if (eng_of_root[r] == kNone) { eng_of_root[r] = (u32)members.size(); members.emplace_back(); }
-      upart_eng[p] = eng_of_root[r];
-      if (members[upart_eng[p]].size() >= 255) return fail(h, CNS_ERR_UNSUPPORTED, "more than 255 partitions connected through shared nodes");
-      upart_tag[p] = (uint8_t)members[upart_eng[p]].size();
-      members[upart_eng[p]].push_back(p);
-      upart_size[p] = (u32)plist[p].size();
-    }
-  }
-  const u32 PE = (u32)members.size();
-  // ---- refusals, group by group (in engine-partition order: which group gets the last free node type is deterministic) ----
-  std::vector<uint8_t> upart_refused(P, 0);
-  {
-    std::set<std::tuple<i64, u64, u64, u64, u64, u64, u64>> types;
-    for (u32 e = 0; e < PE; ++e) {
-      uint8_t why = 0;
-      for (u32 p : members[e]) if (part_bad[p] && !why) why = part_bad[p];
-      u32 npe = 0;
-      for (u32 p : members[e]) npe += (u32)plist[p].size();
-      const u32 cap = width_cap(members[e].size() > 1);
-      if (!why && npe > cap) why = CNS_PART_REFUSED_WIDTH;
-      if (!why) {
-        auto mine = types;
-        for (u32 p : members[e])
-          for (auto& [n, pos] : plist[p]) mine.insert(std::make_tuple(total[n].cpu, total[n].mem, total[n].clo, total[n].chi, total[n].gres, total[n].c2, total[n].c3));
-        if (mine.size() > CNS_MAX_NODE_TYPES) why = CNS_PART_REFUSED_TYPES;
-        else types.swap(mine);
-      }
-      if (why)
-        for (u32 p : members[e]) { upart_refused[p] = why; plist[p].clear(); upart_size[p] = 0; }
-    }
-    bool any_served = false;
-    for (u32 p = 0; p < P; ++p) any_served = any_served || !upart_refused[p];
-    h->refused_probe = upart_refused;   // (why, per partition of THIS call: cns_group_set_nodes reads it when a device's whole share is refused)
-    if (!any_served) return fail(h, CNS_ERR_UNSUPPORTED, "every partition of the snapshot is outside the engine's limits (a node flagged unsupported, a cpu count outside (0, 2^31-2), more than 64 distinct res_total records, or a group wider than the widest tile)");
-  }
-  std::vector<u32> part_off(PE + 1, 0), slot_node, node_slot(N, kNone);
-  std::vector<std::vector<u32>> node_slots(N);
-  std::vector<uint8_t> slot_tag;
-  std::vector<u32> orig_pos_slot(total_pos, kNone);
-  u32 max_np = 0;
-  for (u32 e = 0; e < PE; ++e) {
-    part_off[e] = (u32)slot_node.size();
-    for (u32 p : members[e])
-      for (auto& [n, pos] : plist[p]) {
-        const u32 q = (u32)slot_node.size();
-        if (node_slot[n] == kNone) node_slot[n] = q;
-        node_slots[n].push_back(q);
-        orig_pos_slot[pos] = q;
-        slot_node.push_back(n);
-        slot_tag.push_back(upart_tag[p]);
-      }
-    max_np = std::max<u32>(max_np, (u32)slot_node.size() - part_off[e]);
-  }
-  part_off[PE] = (u32)slot_node.size();
-  // the slots of a group are its member partitions' lists one after the other: member t (its tag) owns [tag_off[b + t], tag_off[b + t + 1])
-  // relative to the group's first slot, b = tag_base[group]
-  h->tag_off.clear(); h->tag_base.assign(PE, 0);
-  for (u32 e = 0; e < PE; ++e) {
-    h->tag_base[e] = (u32)h->tag_off.size();
-    u32 o = 0;
-    for (u32 p : members[e]) { h->tag_off.push_back(o); o += (u32)plist[p].size(); }
-    h->tag_off.push_back(o);
-  }
-  const u32 S = (u32)slot_node.size();
-  // k_select / k_pipe tiles hold 16 576 / 8 192 slots; k_wide (64 scanner waves x 16 rows) 65 536 — but only partitions that
-  // share no node with another one run on it (groups run on k_select), and only while the device can hold its workgroups
-  for (u32 e = 0; e < PE; ++e) {
-    const u32 npe = part_off[e + 1] - part_off[e];
-    // (groups wider than k_select's tile, and partitions wider than k_wide's, run on k_wide's home workgroup alone,
-    // KParams::serial_only: launch_mem)
-    const u32 cap = width_cap(members[e].size() > 1);
-    if (npe > cap)
-      return fail(h, CNS_ERR_UNSUPPORTED, (members[e].size() > 1 ? "group of partitions sharing nodes with more than " : "partition with more than ") +
-                                              std::to_string(cap) + " schedulable (partition, node) slots");
-  }
-  h->Pu = P; h->shared = shared; h->upart_eng = upart_eng; h->upart_size = upart_size; h->upart_tag = upart_tag;
-  h->upart_refused = upart_refused;
-  h->eng_members.clear();
-  for (const auto& m : members) h->eng_members.push_back((u32)m.size());
-  h->node_slots = node_slots; h->slot_tag = slot_tag;
-  P = PE;
-  h->N = N; h->P = P; h->S = S; h->max_np = max_np; h->big_nodes = big || wide; h->wide_cores = wide;
-  h->P_real = P; h->S_real = S; h->V = 0;
-  h->part_off = part_off; h->slot_node = slot_node; h->node_slot = node_slot; h->orig_pos_slot = orig_pos_slot;
-  h->node_total = total;
-  h->resv_start.clear(); h->resv_end.clear(); h->resv_node_slot.clear();
-  h->rv_off.assign(S + 1, 0); h->rv_start.clear(); h->rv_endt.clear(); h->rv_res.clear();
-  if (int rc = finalize_layout(h)) return rc;
+  cns_snapshot::Layout lay;
+  cns_snapshot::ResvLayout rlay;
+  cns_snapshot::Status st = cns_snapshot::build_layout(nd, all_gres, kCaps, lay, &h->refused_probe);
+  if (!st) st = cns_snapshot::build_resv(lay, nullptr, rlay);
+  if (st) return fail(h, st.code, st.msg);
+  h->lay = std::move(lay); h->rlay = std::move(rlay);
+  if (int rc = upload_snapshot(h)) return rc;
   valid_keep_nodes(h, nd);   // (cns_validate_jobs derives its tables from these at its first call)
   h->have_nodes = true;
   return CNS_OK;
@@ -891,142 +683,21 @@ int cns_set_reservations(cns_handle* h, const cns_resv_soa* rv) {
   if (!h->have_nodes) return fail(h, CNS_ERR_STATE, "cns_set_reservations before cns_set_nodes");
   HIPCHK(h, hipSetDevice(h->device));
   h->have_jobs = h->have_run = false;
+  cns_snapshot::ResvLayout rlay;
+  if (const cns_snapshot::Status st = cns_snapshot::build_resv(h->lay, rv, rlay)) return fail(h, st.code, st.msg);
+  h->rlay = std::move(rlay);
   h->vd_rv_have = false;   // (cns_validate_jobs rebuilds its table of the reservations' nodes)
-  const u32 V = rv ? rv->num_resv : 0;
-  if (V && (!rv->start_sec || !rv->end_sec || !rv->alloc_offsets || !rv->alloc_node || !rv->alloc_cpu_raw ||
-            !rv->alloc_mem || !rv->alloc_core_lo))
-    return fail(h, CNS_ERR_INVALID_ARG, "cns_set_reservations: missing array");
-  // back to the layout of cns_set_nodes, then append one virtual partition per reservation
-  h->P = h->P_real; h->S = h->S_real; h->V = V;
-  h->part_off.resize(h->P_real + 1);
-  h->slot_node.resize(h->S_real);
-  h->resv_start.assign(V, 0); h->resv_end.assign(V, 0);
-  h->resv_node_slot.assign(V, {});
-  std::vector<std::vector<std::tuple<i64, i64, Res>>> per_slot(h->S_real);  // reservation entries of the real slots
-  std::vector<Res> virt_total;
-  u64 all_gres = 0;
-  for (u32 c = 0; c < h->gres.num_classes; ++c) all_gres |= h->gres.class_mask[c];
-  for (u32 v = 0; v < V; ++v) {
-    h->resv_start[v] = rv->start_sec[v];
-    h->resv_end[v] = rv->end_sec[v];
-    if (rv->alloc_offsets[v + 1] < rv->alloc_offsets[v]) return fail(h, CNS_ERR_INVALID_ARG, "reservation alloc_offsets not monotone");
-    std::vector<std::pair<u32, Res>> al;
-    for (u32 a = rv->alloc_offsets[v]; a < rv->alloc_offsets[v + 1]; ++a) {
-      const u32 n = rv->alloc_node[a];
-      if (n >= h->N) return fail(h, CNS_ERR_INVALID_ARG, "reservation node >= num_nodes");
-      Res r;
-      r.cpu = rv->alloc_cpu_raw[a]; r.mem = rv->alloc_mem[a]; r.clo = rv->alloc_core_lo[a];
-      r.chi = rv->alloc_core_hi ? rv->alloc_core_hi[a] : 0;
-      r.c2 = rv->alloc_core_w2 ? rv->alloc_core_w2[a] : 0;
-      r.c3 = rv->alloc_core_w3 ? rv->alloc_core_w3[a] : 0;
-      r.gres = rv->alloc_gres ? rv->alloc_gres[a] : 0;
-      if (r.gres & ~all_gres) return fail(h, CNS_ERR_INVALID_ARG, "reservation GRES slot outside every class");
-      if (r.cpu <= 0 || r.cpu >= 0x7FFFFFFEll) return fail(h, CNS_ERR_UNSUPPORTED, "reservation cpu share must be in (0, 2^31-2)");
-      al.emplace_back(n, r);
-      if (r.gres || r.chi) h->big_nodes = true;
-    }
-    std::sort(al.begin(), al.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    for (size_t i = 1; i < al.size(); ++i)
-      if (al[i].first == al[i - 1].first) return fail(h, CNS_ERR_INVALID_ARG, "node listed twice in one reservation");
-    if (al.size() > kGiantPartSlots) return fail(h, CNS_ERR_UNSUPPORTED, "reservation over more than " + std::to_string(kGiantPartSlots) + " nodes");
-    for (auto& [n, r] : al) {
-      h->resv_node_slot[v][n] = (u32)h->slot_node.size();  // virtual node: its own NodeState (:6661-6664)
-      h->slot_node.push_back(n);
-      virt_total.push_back(r);
-      for (u32 q : h->node_slots[n]) per_slot[q].emplace_back(rv->start_sec[v], rv->end_sec[v], r);   // every partition's slot of the node
-    }
-    h->part_off.push_back((u32)h->slot_node.size());
-    h->max_np = std::max<u32>(h->max_np, (u32)al.size());
-  }
-  h->P = h->P_real + V;
-  h->S = (u32)h->slot_node.size();
-  h->rv_off.assign(h->S + 1, 0); h->rv_start.clear(); h->rv_endt.clear(); h->rv_res.clear();
-  for (u32 q = 0; q < h->S_real; ++q) {
-    // release + dip events of a node share the node block's upper half with the running allocations (k_init_nodes)
-    if (per_slot[q].size() > 200) return fail(h, CNS_ERR_UNSUPPORTED, "more than 200 reservations on one node");
-    for (auto& [st, en, r] : per_slot[q]) { h->rv_start.push_back(st); h->rv_endt.push_back(en); h->rv_res.push_back(r); }
-    h->rv_off[q + 1] = (u32)h->rv_start.size();
-  }
-  for (u32 q = h->S_real; q < h->S; ++q) h->rv_off[q + 1] = h->rv_off[q];
-  if (int rc = finalize_layout(h, &virt_total)) return rc;
-  // running jobs must be set again after the layout changed
-  std::vector<u32> rn_off(h->S + 1, 0);
-  if (int rc = upload(h, h->d_rn_off, rn_off)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return CNS_OK;
+  return upload_snapshot(h);
 }
 
 int cns_set_running(cns_handle* h, const cns_running_soa* rn) {
   if (!h) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_running: null handle");
   if (!h->have_nodes) return fail(h, CNS_ERR_STATE, "cns_set_running before cns_set_nodes");
   HIPCHK(h, hipSetDevice(h->device));
-  const u32 N = h->N, S = h->S;
-  // allocations are grouped by SLOT: the node's own slot, or — for a job running inside a reservation
-  // (JobScheduler.cpp:6692-6707) — the reservation's virtual node
-  // (slots of the node: one per partition that lists it — they all start from the same NodeState, JobScheduler.h:498-511)
-  static const std::vector<u32> kNoSlots;
-  std::vector<u32> one(1);
-  auto slots_of = [&](u32 job, u32 n) -> const std::vector<u32>& {
-    const u32 v = rn->reservation ? rn->reservation[job] : CNS_RESV_NONE;
-    if (v == CNS_RESV_NONE) return h->node_slots[n];  // empty: unschedulable node, ignored (:6685-6686)
-    if (v >= h->V) return kNoSlots;                    // reservation not found (:6693-6700)
-    auto it = h->resv_node_slot[v].find(n);
-    if (it == h->resv_node_slot[v].end()) return kNoSlots;
-    one[0] = it->second;
-    return one;
-  };
-  std::vector<u32> rn_off(S + 1, 0);
-  std::vector<i64> rn_end;
-  std::vector<Res> rn_res;
-  if (rn && rn->num_jobs) {
-    if (!rn->end_sec || !rn->alloc_offsets || !rn->alloc_node || !rn->alloc_cpu_raw || !rn->alloc_mem || !rn->alloc_core_lo)
-      return fail(h, CNS_ERR_INVALID_ARG, "cns_set_running: missing array");
-    const u32 A = rn->alloc_offsets[rn->num_jobs];
-    if (A != rn->num_allocs) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_running: num_allocs mismatch");
-    for (u32 j = 0; j < rn->num_jobs; ++j)
-      for (u32 a = rn->alloc_offsets[j]; a < rn->alloc_offsets[j + 1]; ++a) {
-        const u32 n = rn->alloc_node[a];
-        if (n >= N) return fail(h, CNS_ERR_INVALID_ARG, "running allocation on node >= num_nodes");
-        for (u32 q : slots_of(j, n)) rn_off[q + 1]++;
-      }
-    for (u32 q = 0; q < S; ++q) {
-      const u32 nrv = h->rv_off[q + 1] - h->rv_off[q];
-      if (nrv ? rn_off[q + 1] + 2 * nrv + 2 > kTlCap / 2 : rn_off[q + 1] + 2 > kTlCap)
-        return fail(h, CNS_ERR_UNSUPPORTED, "too many running allocations / reservations on one node (1006, or 502 events with reservations)");
-      rn_off[q + 1] += rn_off[q];
-    }
-    rn_end.resize(rn_off[S]);
-    rn_res.resize(rn_off[S]);
-    h->ent_job.assign(rn_off[S], 0);
-    h->ent_slot.assign(rn_off[S], 0);
-    std::vector<u32> cur(rn_off.begin(), rn_off.end() - 1);
-    for (u32 j = 0; j < rn->num_jobs; ++j)  // stable: per slot, input order (cost accumulation order)
-      for (u32 a = rn->alloc_offsets[j]; a < rn->alloc_offsets[j + 1]; ++a) {
-        Res r;
-        r.cpu = rn->alloc_cpu_raw[a];
-        r.mem = rn->alloc_mem[a];
-        r.clo = rn->alloc_core_lo[a];
-        r.chi = rn->alloc_core_hi ? rn->alloc_core_hi[a] : 0;
-        r.c2 = rn->alloc_core_w2 ? rn->alloc_core_w2[a] : 0;
-        r.c3 = rn->alloc_core_w3 ? rn->alloc_core_w3[a] : 0;
-        r.gres = rn->alloc_gres ? rn->alloc_gres[a] : 0;
-        for (u32 q : slots_of(j, rn->alloc_node[a])) {
-          u32 d = cur[q]++;
-          rn_end[d] = rn->end_sec[j];
-          rn_res[d] = r;
-          h->ent_job[d] = j;
-          h->ent_slot[d] = q;
-        }
-      }
-  }
-  if (!(rn && rn->num_jobs)) { h->ent_job.clear(); h->ent_slot.clear(); }
-  h->R = rn ? rn->num_jobs : 0;
-  h->ent_end = rn_end;
-  if (int rc = upload(h, h->d_rn_off, rn_off)) return rc;
-  if (rn_end.empty()) { rn_end.push_back(0); rn_res.push_back(Res{0, 0, 0, 0, 0}); }
-  if (int rc = upload(h, h->d_rn_end, rn_end)) return rc;
-  if (int rc = upload(h, h->d_rn_res, rn_res)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  cns_snapshot::RunLayout run;
+  if (const cns_snapshot::Status st = cns_snapshot::build_running(h->lay, h->rlay, rn, run)) return fail(h, st.code, st.msg);
+  h->run = std::move(run);
+  if (int rc = upload_running(h)) return rc;
   h->have_run = false;
   return CNS_OK;
 }
@@ -1086,16 +757,16 @@ static int upload_jobs_impl(cns_handle* h, const cns_job_soa* jb) {
   namespace jh = cns_jobs_host;
   HIPCHK(h, h->h_reason.ensure(std::max<u64>(J, 1)));
   HIPCHK(h, h->h_place.ensure((J + 1) * 8));
-  if (h->shared) HIPCHK(h, h->h_jtag.ensure(std::max<u64>(J, 1)));
+  if (h->lay.shared) HIPCHK(h, h->h_jtag.ensure(std::max<u64>(J, 1)));
   h->job_part.resize((size_t)J);
   jh::Route R;
-  R.P = h->P; R.Pu = h->Pu; R.P_real = h->P_real; R.V = h->V;
-  R.upart_refused = h->upart_refused.data(); R.upart_eng = h->upart_eng.data(); R.upart_size = h->upart_size.data();
-  R.upart_tag = h->upart_tag.data(); R.part_off = h->part_off.data();
-  R.s_node = h->big_nodes ? 48 : 32; R.gres_classes = h->gres.num_classes; R.batch = batch;
+  R.P = h->rlay.P; R.Pu = h->lay.Pu; R.P_real = h->lay.P_real; R.V = h->rlay.V;
+  R.upart_refused = h->lay.upart_refused.data(); R.upart_eng = h->lay.upart_eng.data(); R.upart_size = h->lay.upart_size.data();
+  R.upart_tag = h->lay.upart_tag.data(); R.part_off = h->rlay.part_off.data();
+  R.s_node = h->rlay.big_nodes ? 48 : 32; R.gres_classes = h->gres.num_classes; R.batch = batch;
   jh::Out O;
   O.reason = h->h_reason.as<uint8_t>(); O.job_part = h->job_part.data(); O.place_off = h->h_place.as<u64>();
-  O.jtag = h->shared ? h->h_jtag.as<uint8_t>() : nullptr;
+  O.jtag = h->lay.shared ? h->h_jtag.as<uint8_t>() : nullptr;
   h->place_off = O.place_off;
   std::vector<jh::Chunk> chunks;
   {
@@ -1108,8 +779,8 @@ static int upload_jobs_impl(cns_handle* h, const cns_job_soa* jb) {
   }
   const u64 Jg = O.Jg, places = O.places;
   const std::vector<u64>& pj_off = O.pj_off;
-  h->part_jobs.resize(h->P);
-  for (u32 p = 0; p < h->P; ++p) h->part_jobs[p] = pj_off[p + 1] - pj_off[p];
+  h->part_jobs.resize(h->rlay.P);
+  for (u32 p = 0; p < h->rlay.P; ++p) h->part_jobs[p] = pj_off[p + 1] - pj_off[p];
   HIPCHK(h, h->h_grouped.ensure(std::max<u64>(Jg, 1) * 4));
   O.grouped = h->h_grouped.as<u32>();
   // pass 2: the offsets of the placement records and the queue grouped by partition in queue order, one u32 per job
@@ -1118,7 +789,7 @@ static int upload_jobs_impl(cns_handle* h, const cns_job_soa* jb) {
   if (Jg == 0) O.grouped[0] = 0;
   if (int rc = stage(h, rb_[14], h->h_place.p, (J + 1) * 8)) return rc;
   if (int rc = stage(h, rb_[15], h->h_grouped.p, std::max<u64>(Jg, 1) * 4)) return rc;
-  if (h->shared) { if (int rc = stage(h, h->d_jtag, h->h_jtag.p, std::max<u64>(J, 1))) return rc; }
+  if (h->lay.shared) { if (int rc = stage(h, h->d_jtag, h->h_jtag.p, std::max<u64>(J, 1))) return rc; }
   HIPCHK(h, h->d_jobs.ensure((size_t)std::max<u64>(Jg, 1) * kJobRecDwords * 4));
   if (Jg) {
     PackParams K{};
@@ -1130,7 +801,7 @@ static int upload_jobs_impl(cns_handle* h, const cns_job_soa* jb) {
     K.gtot = jb->gres_total ? rb_[10].as<uint8_t>() : nullptr; K.gspec = jb->gres_spec ? rb_[11].as<uint8_t>() : nullptr;
     K.incl_off = jb->incl_offsets ? rb_[12].as<u64>() : nullptr; K.excl_off = jb->excl_offsets ? rb_[13].as<u64>() : nullptr;
     K.place_off = rb_[14].as<u64>(); K.jobrec = h->d_jobs.as<u32>();
-    K.tag = h->shared ? h->d_jtag.as<uint8_t>() : nullptr;
+    K.tag = h->lay.shared ? h->d_jtag.as<uint8_t>() : nullptr;
     hipLaunchKernelGGL(k_pack_jobs, dim3((unsigned)((Jg + 255) / 256)), dim3(256), 0, h->stream, K);
     HIPCHK(h, hipGetLastError());
   }
@@ -1145,7 +816,7 @@ static int upload_jobs_impl(cns_handle* h, const cns_job_soa* jb) {
   r.chi = rsec(8, places); r.gres = rsec(8, places); r.node = rsec(4, places); r.ntasks = rsec(4, places);
   r.reason = rsec(1, J);
   r.c2 = r.c3 = ro;   // the planes of core ids 128..255 exist only for a snapshot with such nodes (nothing more to ship otherwise)
-  if (h->wide_cores) { r.c2 = rsec(8, places); r.c3 = rsec(8, places); }
+  if (h->lay.wide_cores) { r.c2 = rsec(8, places); r.c3 = rsec(8, places); }
   r.total = ro;
   HIPCHK(h, h->d_results.ensure(ro));
   HIPCHK(h, hipEventRecord(e1, h->stream));
@@ -1174,7 +845,7 @@ static int run_resident_once(cns_handle* h, int64_t now, const RunKnobs& kn, boo
   HIPCHK(h, hipMemsetAsync(rb + h->ro.start, 0, h->ro.node - h->ro.start, h->stream));  // start + 8-byte records
   HIPCHK(h, hipMemsetAsync(rb + h->ro.node, 0xFF, 4 * pl, h->stream));                  // CNS_NODE_NONE
   HIPCHK(h, hipMemsetAsync(rb + h->ro.ntasks, 0, 4 * pl, h->stream));
-  if (h->wide_cores) HIPCHK(h, hipMemsetAsync(rb + h->ro.c2, 0, h->ro.total - h->ro.c2, h->stream));   // core ids 128..255 of the records
+  if (h->lay.wide_cores) HIPCHK(h, hipMemsetAsync(rb + h->ro.c2, 0, h->ro.total - h->ro.c2, h->stream));   // core ids 128..255 of the records
   HIPCHK(h, hipMemcpyAsync(rb + h->ro.reason, h->d_reason_init.p, J, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_fault.p, 0, 16, h->stream));
   if (h->pre_active) {
@@ -1182,15 +853,15 @@ static int run_resident_once(cns_handle* h, int64_t now, const RunKnobs& kn, boo
     // k_select partitions too, and a second pass over a first pass's per-slot job lists (slot_head / rec_next), hidden
     // candidates (ent_gone / rec_gone) and preempted pairs (out_cnt) would loop on a self-linked list or report pairs twice.
     DevBuf* B = h->d_pre;
-    HIPCHK(h, hipMemsetAsync(B[B_ENTGONE].p, 0, std::max<size_t>(h->ent_job.size(), 1), h->stream));
-    HIPCHK(h, hipMemsetAsync(B[B_HEAD].p, 0xFF, (size_t)std::max<u32>(h->S, 1) * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(B[B_ENTGONE].p, 0, std::max<size_t>(h->run.ent_job.size(), 1), h->stream));
+    HIPCHK(h, hipMemsetAsync(B[B_HEAD].p, 0xFF, (size_t)std::max<u32>(h->rlay.S, 1) * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(B[B_RECGONE].p, 0, pl, h->stream));
     HIPCHK(h, hipMemsetAsync(h->pre_params.out_cnt, 0, 16, h->stream));
   }
-  HIPCHK(h, hipMemsetAsync(h->d_prof.p, 0, ((size_t)h->P * (32 + 16) + 2048) * sizeof(u64), h->stream));   // cycle counters + the always-on protocol counters
+  HIPCHK(h, hipMemsetAsync(h->d_prof.p, 0, ((size_t)h->rlay.P * (32 + 16) + 2048) * sizeof(u64), h->stream));   // cycle counters + the always-on protocol counters
   HIPCHK(h, h->d_params.ensure(sizeof(KParams)));
   HIPCHK(h, hipMemcpyAsync(h->d_params.p, &K, sizeof(KParams), hipMemcpyHostToDevice, h->stream));
-  if (h->S) hipLaunchKernelGGL(k_init_nodes, dim3((h->S + 255) / 256), dim3(256), 0, h->stream, h->d_params.as<KParams>());
+  if (h->rlay.S) hipLaunchKernelGGL(k_init_nodes, dim3((h->rlay.S + 255) / 256), dim3(256), 0, h->stream, h->d_params.as<KParams>());
   if (h->Jg) hipLaunchKernelGGL(k_prep_jobs, dim3((unsigned)((h->Jg + 255) / 256)), dim3(256), 0, h->stream, h->d_params.as<KParams>(), (u64)h->Jg);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
@@ -1198,9 +869,9 @@ static int run_resident_once(cns_handle* h, int64_t now, const RunKnobs& kn, boo
   cns_plan::Candidate ca, cb, cc;   // what launched for the plan's a / b / c
   if (h->Jg) {
     cns_plan::Inputs in;
-    in.parts.resize(h->P);
-    for (u32 p = 0; p < h->P; ++p)
-      in.parts[p] = {p < h->part_jobs.size() ? h->part_jobs[p] : 0, h->part_off[p + 1] - h->part_off[p], p < h->eng_members.size() ? h->eng_members[p] : 1u,
+    in.parts.resize(h->rlay.P);
+    for (u32 p = 0; p < h->rlay.P; ++p)
+      in.parts[p] = {p < h->part_jobs.size() ? h->part_jobs[p] : 0, h->rlay.part_off[p + 1] - h->rlay.part_off[p], p < h->lay.eng_members.size() ? h->lay.eng_members[p] : 1u,
                      p < h->pre_part.size() && h->pre_part[p]};
     in.pre_active = h->pre_active; in.num_cus = h->num_cus; in.kernel_pin = h->cfg.kernel_pin;
     in.sw = kn.sw; in.protocol_off = protocol_off; in.wide_window = K.wide_window; in.aux_override = kn.aux;
@@ -1326,7 +997,7 @@ int cns_download(cns_handle* h, cns_placement_soa* out) {
   if (!out->start_sec || !out->reason || !out->place_offsets || !out->node_idx || !out->ntasks || !out->cpu_raw ||
       !out->mem || !out->core_lo || !out->core_hi || !out->gres)
     return fail(h, CNS_ERR_INVALID_ARG, "cns_download: missing result array");
-  if (h->wide_cores && (!out->core_w2 || !out->core_w3))
+  if (h->lay.wide_cores && (!out->core_w2 || !out->core_w3))
     return fail(h, CNS_ERR_INVALID_ARG, "cns_download: the snapshot has nodes with core ids above 127: core_w2 / core_w3 are required");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
@@ -1342,7 +1013,7 @@ int cns_download(cns_handle* h, cns_placement_soa* out) {
   HIPCHK(h, get(out->core_lo, h->ro.clo, 8 * pl));
   HIPCHK(h, get(out->core_hi, h->ro.chi, 8 * pl));
   HIPCHK(h, get(out->gres, h->ro.gres, 8 * pl));
-  if (h->wide_cores) {
+  if (h->lay.wide_cores) {
     HIPCHK(h, get(out->core_w2, h->ro.c2, 8 * pl));
     HIPCHK(h, get(out->core_w3, h->ro.c3, 8 * pl));
   } else {
@@ -1420,13 +1091,13 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
   struct PreCall { cns_engine* h; ~PreCall() { h->pre_call = false; } } pre_call{h};   // (run_resident_once notes it: cns_probe refuses such a state)
   h->pre_call = true;
   const u64 J = jobs->num_jobs;
-  const u32 R = h->R;
+  const u32 R = h->run.R;
   if (J && (!pre->pd_qos || !pre->pd_qos_priority || !pre->pd_priority)) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: missing pending-job array");
   if (R && (!pre->rn_job_id || !pre->rn_qos || !pre->rn_qos_priority || !pre->rn_start_sec)) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: missing running-job array");
   if (!pout->offsets || !pout->preempted || !pout->cancelled_job_ids || !pout->preempting_job_ids) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: missing output array");
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = cns_upload_jobs(h, jobs)) return rc;
-  const u32 A = (u32)h->ent_job.size();
+  const u32 A = (u32)h->run.ent_job.size();
   // m_preempting_set_: ids that no longer run are dropped, the others end at now + 1 (JobScheduler.cpp:6545-6559)
   std::map<u32, u32> id_to_rn;
   for (u32 r = 0; r < R; ++r) id_to_rn.emplace(pre->rn_job_id[r], r);
@@ -1438,18 +1109,18 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
     rj_pre[it->second] = 1;
     set_in.push_back(pre->preempting_job_ids[i]);
   }
-  std::vector<i64> ent_end = h->ent_end, rj_end(std::max<u32>(R, 1), 0), rj_start(std::max<u32>(R, 1), 0);
+  std::vector<i64> ent_end = h->run.rn_end, rj_end(std::max<u32>(R, 1), 0), rj_start(std::max<u32>(R, 1), 0);
   std::vector<u32> rj_qos(std::max<u32>(R, 1), 0), rj_qprio(std::max<u32>(R, 1), 0), rj_off(R + 1, 0), rj_ent(std::max<u32>(A, 1), 0);
-  for (u32 d = 0; d < A; ++d) rj_off[h->ent_job[d] + 1]++;
+  for (u32 d = 0; d < A; ++d) rj_off[h->run.ent_job[d] + 1]++;
   for (u32 r = 0; r < R; ++r) rj_off[r + 1] += rj_off[r];
   {
     std::vector<u32> cur(rj_off.begin(), rj_off.end() - 1);
-    for (u32 d = 0; d < A; ++d) rj_ent[cur[h->ent_job[d]]++] = d;
+    for (u32 d = 0; d < A; ++d) rj_ent[cur[h->run.ent_job[d]]++] = d;
   }
   for (u32 r = 0; r < R; ++r) { rj_qos[r] = pre->rn_qos[r]; rj_qprio[r] = pre->rn_qos_priority[r]; rj_start[r] = pre->rn_start_sec[r]; }
   std::vector<char> have_end(std::max<u32>(R, 1), 0);
   for (u32 d = 0; d < A; ++d) {
-    const u32 r = h->ent_job[d];
+    const u32 r = h->run.ent_job[d];
     if (rj_pre[r]) ent_end[d] = now + 1;
     rj_end[r] = std::max<i64>(ent_end[d], now + 1);   // :6513-6514
     have_end[r] = 1;
@@ -1463,7 +1134,7 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
     ~RestoreEnd() {
       if (!armed) return;
       const std::string keep = h->err;   // the restore must not overwrite the call's own error
-      if (upload(h, h->d_rn_end, h->ent_end) == CNS_OK) (void)hipStreamSynchronize(h->stream);
+      if (upload(h, h->d_rn_end, h->run.rn_end) == CNS_OK) (void)hipStreamSynchronize(h->stream);
       h->err = keep;
     }
   } restore_end{h, false};
@@ -1504,7 +1175,7 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
   // job plus every pending job of the cycle (at most all of them hold resources on one job's nodes), bounded by 64 Mi entries
   // over all partitions; segment-tree pools of 65 536 nodes.  Exceeding either is CNS_ERR_UNSUPPORTED, not a device fault.
   const u32 pool_nodes = 1u << 16;
-  const u32 cand_cap = (u32)std::max<u64>(4096, std::min<u64>((u64)R + J + 1, (64ull << 20) / std::max<u32>(h->P, 1)));
+  const u32 cand_cap = (u32)std::max<u64>(4096, std::min<u64>((u64)R + J + 1, (64ull << 20) / std::max<u32>(h->rlay.P, 1)));
   const u32 out_cap = (u32)std::min<u64>(4 * (J + R) + 64, 1u << 28);
   DevBuf* B = h->d_pre;
   if (int rc = upload(h, B[B_QPOFF], qp_off)) return rc;
@@ -1513,8 +1184,8 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
   if (int rc = upload(h, B[B_PJQP], pj_qprio)) return rc;
   if (int rc = upload(h, B[B_PJPRIO], pj_prio)) return rc;
   HIPCHK(h, B[B_PJREC0].ensure(std::max<u64>(J, 1) * 4)); HIPCHK(h, B[B_PJK].ensure(std::max<u64>(J, 1) * 4)); HIPCHK(h, B[B_PJEND].ensure(std::max<u64>(J, 1) * 8));
-  { std::vector<u32> ej = h->ent_job, es = h->ent_slot; if (ej.empty()) { ej.push_back(0); es.push_back(0); }
-    if (int rc = upload(h, B[B_RNJOB], ej)) return rc; if (int rc = upload(h, B[B_ENTSLOT], es)) return rc; }
+  if (int rc = upload_some(h, B[B_RNJOB], h->run.ent_job)) return rc;
+  if (int rc = upload_some(h, B[B_ENTSLOT], h->run.ent_slot)) return rc;
   HIPCHK(h, B[B_ENTGONE].ensure(std::max<u32>(A, 1)));   // (zeroed at the start of every pass: run_resident_once)
   if (int rc = upload(h, B[B_RJQOS], rj_qos)) return rc;
   if (int rc = upload(h, B[B_RJQP], rj_qprio)) return rc;
@@ -1523,11 +1194,11 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
   if (int rc = upload(h, B[B_RJPRE], rj_pre)) return rc;
   if (int rc = upload(h, B[B_RJOFF], rj_off)) return rc;
   if (int rc = upload(h, B[B_RJENT], rj_ent)) return rc;
-  HIPCHK(h, B[B_HEAD].ensure((size_t)std::max<u32>(h->S, 1) * 4));
+  HIPCHK(h, B[B_HEAD].ensure((size_t)std::max<u32>(h->rlay.S, 1) * 4));
   HIPCHK(h, B[B_RECNEXT].ensure(places * 4)); HIPCHK(h, B[B_RECORIG].ensure(places * 4)); HIPCHK(h, B[B_RECSLOT].ensure(places * 4));
   HIPCHK(h, B[B_RECGONE].ensure(places));
   // one block for: segment-tree pools | candidate lists | chosen lists | output counter | output pairs
-  const size_t pool_b = (size_t)h->P * pool_nodes * sizeof(PreNode), cand_b = (size_t)h->P * cand_cap * 4;
+  const size_t pool_b = (size_t)h->rlay.P * pool_nodes * sizeof(PreNode), cand_b = (size_t)h->rlay.P * cand_cap * 4;
   const size_t off_cand = align16(pool_b), off_chosen = off_cand + align16(cand_b), off_cnt = off_chosen + align16(cand_b), off_out = off_cnt + 16;
   HIPCHK(h, B[B_MISC].ensure(off_out + (size_t)out_cap * 8));
   char* misc = B[B_MISC].as<char>();
@@ -1548,7 +1219,7 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
   // CNS_PREEMPT_TREE=literal: TryPreempt_ on the node-for-node trees only (else: the fall-back of a call that runs out of compressed records)
   { const char* tr = getenv("CNS_PREEMPT_TREE"); Q.literal_tree = (tr && !strcmp(tr, "literal")) ? 1u : ((tr && !strcmp(tr, "tiny")) ? 2u : 0u); }   // tiny: a handful of compressed records per call, the rest falls back
   // the partitions that have a pending job whose qos may preempt: only they run on k_select's general path (run_resident_once)
-  h->pre_part.assign(h->P, 0);
+  h->pre_part.assign(h->rlay.P, 0);
   for (u64 j = 0; j < J; ++j) {
     const u32 q = pre->pd_qos[j];
     if (j < h->job_part.size() && h->job_part[(size_t)j] != kNone && q < pre->num_qos && pre->qos_preempt_offsets[q + 1] > pre->qos_preempt_offsets[q])
@@ -1596,8 +1267,8 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
 int cns_get_partition_status(const cns_handle* h, uint8_t* status, uint32_t capacity) {
   if (!h || !status) return fail(const_cast<cns_handle*>(h), CNS_ERR_INVALID_ARG, "cns_get_partition_status: null argument");
   if (!h->have_nodes) return fail(const_cast<cns_handle*>(h), CNS_ERR_STATE, "cns_get_partition_status before cns_set_nodes");
-  if (capacity < h->Pu) return fail(const_cast<cns_handle*>(h), CNS_ERR_INVALID_ARG, "cns_get_partition_status: capacity below the number of partitions");
-  for (u32 p = 0; p < h->Pu; ++p) status[p] = h->upart_refused[p];
+  if (capacity < h->lay.Pu) return fail(const_cast<cns_handle*>(h), CNS_ERR_INVALID_ARG, "cns_get_partition_status: capacity below the number of partitions");
+  for (u32 p = 0; p < h->lay.Pu; ++p) status[p] = h->lay.upart_refused[p];
   return CNS_OK;
 }
 
@@ -1619,15 +1290,15 @@ int cns_debug_get_costs(cns_handle* h, double* out) {
   if (!h || !out) return fail(h, CNS_ERR_INVALID_ARG, "cns_debug_get_costs: null argument");
   if (!h->have_run) return fail(h, CNS_ERR_STATE, "cns_debug_get_costs before a successful run");
   HIPCHK(h, hipSetDevice(h->device));
-  std::vector<double> c(std::max<u32>(h->S, 1));
-  HIPCHK(h, hipMemcpy(c.data(), h->d_cost.p, (size_t)h->S * sizeof(double), hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < h->orig_pos_slot.size(); ++i) out[i] = h->orig_pos_slot[i] == kNone ? 0.0 : c[h->orig_pos_slot[i]];
+  std::vector<double> c(std::max<u32>(h->rlay.S, 1));
+  HIPCHK(h, hipMemcpy(c.data(), h->d_cost.p, (size_t)h->rlay.S * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < h->lay.orig_pos_slot.size(); ++i) out[i] = h->lay.orig_pos_slot[i] == kNone ? 0.0 : c[h->lay.orig_pos_slot[i]];
   return CNS_OK;
 }
 
 const char* cns_debug_last_kernel(const cns_handle* h) { return h ? h->last_kernel.c_str() : ""; }
 
-uint32_t cns_debug_engine_partitions(const cns_handle* h) { return (h && h->have_nodes) ? h->P : 0u; }
+uint32_t cns_debug_engine_partitions(const cns_handle* h) { return (h && h->have_nodes) ? h->rlay.P : 0u; }
 
 int cns_debug_get_prof(cns_handle* h, uint64_t* out, uint32_t capacity) {
   // cycle counters of the last run, 32 per partition; all zero unless the library was built with -DCNS_PROF
@@ -1638,9 +1309,9 @@ int cns_debug_get_prof(cns_handle* h, uint64_t* out, uint32_t capacity) {
   HIPCHK(h, hipSetDevice(h->device));
   // behind them (from index 32 * P): 16 always-on protocol counter slots per partition of k_wide (every build; wide_kernel.inc kWs*)
 #ifdef CNS_DEBUG_FLUSH_LOG
-  const size_t n = std::min<size_t>((size_t)h->P * (32 + 16) + 2048, capacity);   // + the flush log of partition 0 (diagnostics build)
+  const size_t n = std::min<size_t>((size_t)h->rlay.P * (32 + 16) + 2048, capacity);   // + the flush log of partition 0 (diagnostics build)
 #else
-  const size_t n = std::min<size_t>((size_t)h->P * (32 + 16), capacity);
+  const size_t n = std::min<size_t>((size_t)h->rlay.P * (32 + 16), capacity);
 #endif
   HIPCHK(h, hipMemcpy(out, h->d_prof.p, n * sizeof(u64), hipMemcpyDeviceToHost));
   return CNS_OK;
@@ -1650,9 +1321,9 @@ int cns_debug_get_timeline(cns_handle* h, uint32_t node, uint32_t capacity, uint
                            int64_t* cpu_raw, uint64_t* mem, uint64_t* core_lo, uint64_t* core_hi, uint64_t* gres) {
   if (!h || !len) return fail(h, CNS_ERR_INVALID_ARG, "cns_debug_get_timeline: null argument");
   if (!h->have_run) return fail(h, CNS_ERR_STATE, "cns_debug_get_timeline before a successful run");
-  if (node >= h->N) return fail(h, CNS_ERR_INVALID_ARG, "cns_debug_get_timeline: node out of range");
+  if (node >= h->lay.N) return fail(h, CNS_ERR_INVALID_ARG, "cns_debug_get_timeline: node out of range");
   HIPCHK(h, hipSetDevice(h->device));
-  const u32 slot = h->node_slot[node];
+  const u32 slot = h->lay.node_slot[node];
   if (slot == kNone) { *len = 0; return CNS_OK; }  // not schedulable / in no partition: no NodeState (cpp:6595)
   const char* blk = h->d_blocks.as<char>() + (size_t)slot * kBlockStride;
   NodeHdr hd;
@@ -1671,16 +1342,16 @@ int cns_debug_get_timeline(cns_handle* h, uint32_t node, uint32_t capacity, uint
 int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity, uint64_t* core_w2, uint64_t* core_w3) {
   if (!h || !core_w2 || !core_w3) return fail(h, CNS_ERR_INVALID_ARG, "cns_debug_get_timeline_cores: null argument");
   if (!h->have_run) return fail(h, CNS_ERR_STATE, "cns_debug_get_timeline_cores before a successful run");
-  if (node >= h->N) return fail(h, CNS_ERR_INVALID_ARG, "cns_debug_get_timeline_cores: node out of range");
+  if (node >= h->lay.N) return fail(h, CNS_ERR_INVALID_ARG, "cns_debug_get_timeline_cores: node out of range");
   HIPCHK(h, hipSetDevice(h->device));
-  const u32 slot = h->node_slot[node];
+  const u32 slot = h->lay.node_slot[node];
   if (slot == kNone) return CNS_OK;
   const char* blk = h->d_blocks.as<char>() + (size_t)slot * kBlockStride;
   NodeHdr hd;
   HIPCHK(h, hipMemcpy(&hd, blk, sizeof hd, hipMemcpyDeviceToHost));
   const u32 m = std::min(hd.len, capacity);
   for (u32 i = 0; i < m; ++i) core_w2[i] = core_w3[i] = 0;
-  if (!h->wide_cores) return CNS_OK;   // (the TlExt array of a block is live only for snapshots with such core ids)
+  if (!h->lay.wide_cores) return CNS_OK;   // (the TlExt array of a block is live only for snapshots with such core ids)
   std::vector<TlExt> e(std::max<u32>(m, 1));
   if (m) HIPCHK(h, hipMemcpy(e.data(), blk + sizeof(NodeHdr) + (size_t)kTlCap * sizeof(TlMem), (size_t)m * sizeof(TlExt), hipMemcpyDeviceToHost));
   for (u32 i = 0; i < m; ++i) { core_w2[i] = e[i].c2; core_w3[i] = e[i].c3; }

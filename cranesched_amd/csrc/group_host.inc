@@ -119,7 +119,7 @@ int cns_comm_destroy(cns_handle* h) {
 int cns_results_layout(const cns_handle* h, cns_results_offsets* out) {
   if (!h || !out) return fail(const_cast<cns_handle*>(h), CNS_ERR_INVALID_ARG, "cns_results_layout: null argument");
   if (!h->have_jobs) return fail(const_cast<cns_handle*>(h), CNS_ERR_STATE, "cns_results_layout before cns_upload_jobs");
-  out->num_jobs = h->J; out->num_places = h->places; out->wide_cores = h->wide_cores ? 1u : 0u;
+  out->num_jobs = h->J; out->num_places = h->places; out->wide_cores = h->lay.wide_cores ? 1u : 0u;
   out->start_sec = h->ro.start; out->cpu_raw = h->ro.cpu; out->mem = h->ro.mem; out->core_lo = h->ro.clo; out->core_hi = h->ro.chi;
   out->gres = h->ro.gres; out->node_idx = h->ro.node; out->ntasks = h->ro.ntasks; out->reason = h->ro.reason;
   out->core_w2 = h->ro.c2; out->core_w3 = h->ro.c3; out->total_bytes = h->ro.total;
@@ -249,7 +249,7 @@ int cns_group_set_nodes(cns_group* g, const cns_node_soa* nd) {
     }
     if (st != 0) return gfail(g, st, "device " + std::to_string(g->devices[d]) + ": " + cns_last_error(g->eng[d]));
     g->active.push_back(d);
-    for (size_t l = 0; l < g->dev_parts[d].size(); ++l) g->part_status[g->dev_parts[d][l]] = g->eng[d]->upart_refused[l];
+    for (size_t l = 0; l < g->dev_parts[d].size(); ++l) g->part_status[g->dev_parts[d][l]] = g->eng[d]->lay.upart_refused[l];
   }
   g->V = 0;
   if (g->active.empty()) return gfail(g, CNS_ERR_UNSUPPORTED, "every partition of the snapshot is outside the engine's limits on every device");
@@ -447,7 +447,7 @@ int cns_group_select(cns_group* g, int64_t now, const cns_job_soa* jb, cns_place
   }
   const auto t3 = std::chrono::steady_clock::now();
   bool any_wide = false;
-  for (u32 d : g->active) any_wide = any_wide || g->eng[d]->wide_cores;
+  for (u32 d : g->active) any_wide = any_wide || g->eng[d]->lay.wide_cores;
   if (any_wide && (!out->core_w2 || !out->core_w3)) return gfail(g, CNS_ERR_INVALID_ARG, "cns_group_select: the snapshot has nodes with core ids above 127: core_w2 / core_w3 are required");
   auto scatter = [&](u32 d) {
     if (!is_active[d]) return;
@@ -468,8 +468,8 @@ int cns_group_select(cns_group* g, int64_t now, const cns_job_soa* jb, cns_place
       for (u64 i = 0; i < k; ++i) {
         out->node_idx[dst + i] = nd[src + i]; out->ntasks[dst + i] = nt[src + i]; out->cpu_raw[dst + i] = cpu[src + i]; out->mem[dst + i] = mem[src + i];
         out->core_lo[dst + i] = lo[src + i]; out->core_hi[dst + i] = hi[src + i]; out->gres[dst + i] = gr[src + i];
-        if (out->core_w2) out->core_w2[dst + i] = h->wide_cores ? w2[src + i] : 0;
-        if (out->core_w3) out->core_w3[dst + i] = h->wide_cores ? w3[src + i] : 0;
+        if (out->core_w2) out->core_w2[dst + i] = h->lay.wide_cores ? w2[src + i] : 0;
+        if (out->core_w3) out->core_w3[dst + i] = h->lay.wide_cores ? w3[src + i] : 0;
       }
       src += k;
     }

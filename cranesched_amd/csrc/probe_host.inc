@@ -46,13 +46,13 @@ static int probe_upload_impl(cns_handle* h, const cns_job_soa* jb) {
   std::vector<u32> job_part((size_t)std::max<u64>(J, 1), kNone);
   std::vector<u64> place_off((size_t)J + 1, 0);
   jh::Route R;
-  R.P = h->P; R.Pu = h->Pu; R.P_real = h->P_real; R.V = h->V;
-  R.upart_refused = h->upart_refused.data(); R.upart_eng = h->upart_eng.data(); R.upart_size = h->upart_size.data();
-  R.upart_tag = h->upart_tag.data(); R.part_off = h->part_off.data();
-  R.s_node = h->big_nodes ? 48 : 32; R.gres_classes = h->gres.num_classes; R.batch = J;
+  R.P = h->rlay.P; R.Pu = h->lay.Pu; R.P_real = h->lay.P_real; R.V = h->rlay.V;
+  R.upart_refused = h->lay.upart_refused.data(); R.upart_eng = h->lay.upart_eng.data(); R.upart_size = h->lay.upart_size.data();
+  R.upart_tag = h->lay.upart_tag.data(); R.part_off = h->rlay.part_off.data();
+  R.s_node = h->rlay.big_nodes ? 48 : 32; R.gres_classes = h->gres.num_classes; R.batch = J;
   jh::Out O;
   O.reason = reason.data(); O.job_part = job_part.data(); O.place_off = place_off.data();
-  O.jtag = h->shared ? jtag.data() : nullptr;
+  O.jtag = h->lay.shared ? jtag.data() : nullptr;
   std::vector<jh::Chunk> chunks;
   {
     std::string perr;
@@ -68,7 +68,7 @@ static int probe_upload_impl(cns_handle* h, const cns_job_soa* jb) {
   for (u64 i = 0; i < Jg; ++i) { part_of[(size_t)i] = job_part[grouped[(size_t)i]]; kmax = std::max(kmax, jb->node_num[grouped[(size_t)i]]); }
   if (int rc = stage(h, rb_[14], place_off.data(), (J + 1) * 8)) return rc;
   if (int rc = stage(h, rb_[15], grouped.data(), grouped.size() * 4)) return rc;
-  if (h->shared) { if (int rc = stage(h, B[PB_JTAG], jtag.data(), jtag.size())) return rc; }
+  if (h->lay.shared) { if (int rc = stage(h, B[PB_JTAG], jtag.data(), jtag.size())) return rc; }
   if (int rc = stage(h, B[PB_PART], part_of.data(), part_of.size() * 4)) return rc;
   if (int rc = stage(h, B[PB_REASON], reason.data(), reason.size())) return rc;
   HIPCHK(h, B[PB_JOBS].ensure((size_t)std::max<u64>(Jg, 1) * kJobRecDwords * 4));
@@ -82,7 +82,7 @@ static int probe_upload_impl(cns_handle* h, const cns_job_soa* jb) {
     K.gtot = jb->gres_total ? rb_[10].as<uint8_t>() : nullptr; K.gspec = jb->gres_spec ? rb_[11].as<uint8_t>() : nullptr;
     K.incl_off = jb->incl_offsets ? rb_[12].as<u64>() : nullptr; K.excl_off = jb->excl_offsets ? rb_[13].as<u64>() : nullptr;
     K.place_off = rb_[14].as<u64>(); K.jobrec = B[PB_JOBS].as<u32>();
-    K.tag = h->shared ? B[PB_JTAG].as<uint8_t>() : nullptr;
+    K.tag = h->lay.shared ? B[PB_JTAG].as<uint8_t>() : nullptr;
     hipLaunchKernelGGL(k_pack_jobs, dim3((unsigned)((Jg + 255) / 256)), dim3(256), 0, h->stream, K);
     HIPCHK(h, hipGetLastError());
   }
@@ -94,7 +94,7 @@ static int probe_upload_impl(cns_handle* h, const cns_job_soa* jb) {
   r.chi = rsec(8, places); r.gres = rsec(8, places); r.node = rsec(4, places); r.ntasks = rsec(4, places);
   r.reason = rsec(1, J);
   r.c2 = r.c3 = ro;
-  if (h->wide_cores) { r.c2 = rsec(8, places); r.c3 = rsec(8, places); }
+  if (h->lay.wide_cores) { r.c2 = rsec(8, places); r.c3 = rsec(8, places); }
   r.total = ro;
   HIPCHK(h, B[PB_RESULTS].ensure(ro));
   HIPCHK(h, hipStreamSynchronize(h->stream));   // (the staging vectors above end with this scope)
@@ -130,7 +130,7 @@ int cns_probe_run_resident(cns_handle* h, double* kernel_ms) {
   K.o_start = (i64*)(rb + ro.start); K.o_cpu = (i64*)(rb + ro.cpu); K.o_mem = (u64*)(rb + ro.mem); K.o_clo = (u64*)(rb + ro.clo);
   K.o_chi = (u64*)(rb + ro.chi); K.o_gres = (u64*)(rb + ro.gres); K.o_node = (u32*)(rb + ro.node); K.o_ntasks = (u32*)(rb + ro.ntasks);
   K.o_reason = (uint8_t*)(rb + ro.reason);
-  K.o_c2 = h->wide_cores ? (u64*)(rb + ro.c2) : nullptr; K.o_c3 = h->wide_cores ? (u64*)(rb + ro.c3) : nullptr;
+  K.o_c2 = h->lay.wide_cores ? (u64*)(rb + ro.c2) : nullptr; K.o_c3 = h->lay.wide_cores ? (u64*)(rb + ro.c3) : nullptr;
   K.bf_j = nullptr; K.g_upd = nullptr; K.prof = nullptr; K.wide_ctl = nullptr; K.wide_last = nullptr; K.giant_ctl = nullptr;
   K.f_len = nullptr;                         // (kept by one commit path only: the block header has the length)
   K.general_only = 0; K.serial_only = 0; K.part_map = nullptr; K.launch_parts = 0; K.pre = PreParams{};
@@ -138,7 +138,7 @@ int cns_probe_run_resident(cns_handle* h, double* kernel_ms) {
   HIPCHK(h, hipMemsetAsync(rb + ro.start, 0, ro.node - ro.start, h->stream));
   HIPCHK(h, hipMemsetAsync(rb + ro.node, 0xFF, 4 * pl, h->stream));   // CNS_NODE_NONE
   HIPCHK(h, hipMemsetAsync(rb + ro.ntasks, 0, 4 * pl, h->stream));
-  if (h->wide_cores) HIPCHK(h, hipMemsetAsync(rb + ro.c2, 0, ro.total - ro.c2, h->stream));
+  if (h->lay.wide_cores) HIPCHK(h, hipMemsetAsync(rb + ro.c2, 0, ro.total - ro.c2, h->stream));
   HIPCHK(h, hipMemcpyAsync(rb + ro.reason, B[PB_REASON].p, J, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, B[PB_FAULT].ensure(16));
   HIPCHK(h, hipMemsetAsync(B[PB_FAULT].p, 0, 16, h->stream));
@@ -150,7 +150,7 @@ int cns_probe_run_resident(cns_handle* h, double* kernel_ms) {
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_probe, kProbeBlock, 0) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
     const u64 resident = (u64)std::max(per_cu, 1) * std::max<u32>(h->num_cus, 1);
-    const u32 stride = std::min<u32>(h->max_np, h->pkmax) + 1u;
+    const u32 stride = std::min<u32>(h->rlay.max_np, h->pkmax) + 1u;
     u64 grid = std::min<u64>(h->pJg, resident);
     const u64 scratch_cap = 1ull << 30;       // ... and at most 1 GiB of it (a probe over thousands of nodes of a giant partition)
     grid = std::max<u64>(1, std::min<u64>(grid, scratch_cap / ((u64)stride * sizeof(HeapEnt))));
@@ -194,7 +194,7 @@ int cns_probe_download(cns_handle* h, cns_placement_soa* out) {
   if (!out->start_sec || !out->reason || !out->place_offsets || !out->node_idx || !out->ntasks || !out->cpu_raw ||
       !out->mem || !out->core_lo || !out->core_hi || !out->gres)
     return fail(h, CNS_ERR_INVALID_ARG, "cns_probe_download: missing result array");
-  if (h->wide_cores && (!out->core_w2 || !out->core_w3))
+  if (h->lay.wide_cores && (!out->core_w2 || !out->core_w3))
     return fail(h, CNS_ERR_INVALID_ARG, "cns_probe_download: the snapshot has nodes with core ids above 127: core_w2 / core_w3 are required");
   HIPCHK(h, hipSetDevice(h->device));
   const char* rb = h->d_pb[PB_RESULTS].as<char>();
@@ -209,7 +209,7 @@ int cns_probe_download(cns_handle* h, cns_placement_soa* out) {
   HIPCHK(h, get(out->core_lo, ro.clo, 8 * pl));
   HIPCHK(h, get(out->core_hi, ro.chi, 8 * pl));
   HIPCHK(h, get(out->gres, ro.gres, 8 * pl));
-  if (h->wide_cores) {
+  if (h->lay.wide_cores) {
     HIPCHK(h, get(out->core_w2, ro.c2, 8 * pl));
     HIPCHK(h, get(out->core_w3, ro.c3, 8 * pl));
   } else {

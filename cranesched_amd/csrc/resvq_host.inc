@@ -15,7 +15,7 @@ static u64 rq_interval_cap() {
 }
 
 static int resvq_set_state_impl(cns_handle* h, const cns_running_soa* rn, const cns_resv_soa* rv) {
-  const u32 N = h->N;
+  const u32 N = h->lay.N;
   const u32 RJ = rn ? rn->num_jobs : 0, RA = rn ? rn->num_allocs : 0;
   if (RJ && (!rn->end_sec || !rn->alloc_offsets || (RA && !rn->alloc_node))) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: missing array (running)");
   if (RJ) {

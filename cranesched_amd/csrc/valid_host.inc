@@ -3,7 +3,7 @@
 // partition (a counting sort over chunks of the queue on the host threads of jobs_host.inc), the chunk table, the buffers.  Every test of
 // a job against a node or a partition runs on the device (valid_kernels.inc).  Everything lives in cns_engine::d_vd and the vd_* copies of
 // the caller's node arrays that cns_set_nodes keeps: no flag and no buffer of a cycle, a probe or a reservation what-if is read or
-// written, except the node lists of the reservations (cns_engine::resv_node_slot, read).  No CPU fallback.
+// written, except the node lists of the reservations (cns_engine::rlay, read).  No CPU fallback.
 
 constexpr u64 kVdMaxJobs = 0xFFFFFFF0ull;   // 2^32 - 16 jobs of one call (DESIGN.md 8): job indices and grouped positions are 32-bit
 
@@ -51,12 +51,10 @@ static int valid_build_tables(cns_handle* h) {
 
 // the nodes of every reservation of the last cns_set_reservations, ascending (:7339-7342)
 static int valid_build_resv(cns_handle* h) {
-  const u32 V = (u32)h->resv_node_slot.size();
-  std::vector<u32> off((size_t)V + 1, 0), nodes;
-  for (u32 v = 0; v < V; ++v) {
-    for (const auto& kv : h->resv_node_slot[v]) nodes.push_back(kv.first);   // (a std::map: ascending)
-    off[(size_t)v + 1] = (u32)nodes.size();
-  }
+  const cns_snapshot::ResvLayout& X = h->rlay;   // (the slots of reservation v's virtual partition are its nodes, ascending)
+  const u32 V = X.V, first = h->lay.S_real;
+  std::vector<u32> off((size_t)V + 1, 0), nodes(X.slot_node.begin() + first, X.slot_node.end());
+  for (u32 v = 0; v < V; ++v) off[(size_t)v + 1] = X.part_off[h->lay.P_real + v + 1] - first;
   if (int rc = upload(h, h->d_vd[VD_RVOFF], off)) return rc;
   if (int rc = upload(h, h->d_vd[VD_RVNODES], nodes)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));

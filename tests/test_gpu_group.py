@@ -229,6 +229,30 @@ def test_group_serves_the_other_devices_when_one_devices_share_is_refused(classe
         g.close()
 
 
+def test_group_reports_a_hard_error_behind_a_refused_share(classes):
+    """The statuses cns_group_set_nodes reads when a device's whole share is refused are those of THAT call: a device that served nothing in
+    one snapshot and fails the next one for another reason (here: a node listed twice, CNS_ERR_INVALID_ARG) fails the group's call."""
+    import dataclasses
+    from cranesched_amd.engine import EngineError
+    from tests import kat
+    _, Group = classes
+    c = kat.cluster([4] * 8, parts=[[0, 1, 2, 3], [4, 5, 6, 7]])
+    unsup = np.zeros(8, np.uint8); unsup[5] = 1
+    refused = dataclasses.replace(c, unsupported=unsup)                  # partition 1 is device 1's whole share: it serves nothing
+    twice = dataclasses.replace(c, part_nodes=np.array([0, 1, 2, 3, 4, 5, 6, 6], np.uint32))
+    g = Group([0, 0])
+    try:
+        g.set_nodes(refused)
+        assert g.partition_status().tolist() == [0, 1]
+        with pytest.raises(EngineError) as ei:
+            g.set_nodes(twice)
+        assert ei.value.status == -1 and "node listed twice in one partition" in str(ei.value)
+        g.set_nodes(c)                                                   # ... and the group is usable behind it
+        assert g.partition_status().tolist() == [0, 0]
+    finally:
+        g.close()
+
+
 def _ndev():
     import torch
     return torch.cuda.device_count() if torch.cuda.is_available() else 0

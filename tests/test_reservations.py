@@ -233,6 +233,43 @@ def test_gpu_reservation_argument_checks(engine_cls):
         eng.close()
 
 
+@pytest.mark.gpu
+def test_gpu_refused_snapshot_calls_change_nothing(engine_cls):
+    """A cns_set_reservations or cns_set_running that fails validation leaves the handle's snapshot as it was, host mirror and device
+    tables: the layout is built aside and moved into the handle only when the call succeeds (csrc/snapshot_host.inc).  After every refused
+    call the running set is set again and the cycle must come out as before it — with a running job INSIDE the reservation, whose virtual
+    slot a half-written layout no longer had."""
+    from cranesched_amd.engine import EngineError
+    c = kat.cluster([8] * 8, parts=[[0, 1, 2, 3], [4, 5, 6, 7]])
+    rv = _resv([(NOW - 10, NOW + 500, [(1, 4, 8, 0xF0), (5, 4, 8, 0xF0)])])
+    run = _running([(NOW + 50, 0, [(1, 1, 1, 0x10)]), (NOW + 80, None, [(0, 2, 2, 0x3), (4, 2, 2, 0x3)]), (NOW + 120, None, [(6, 8, 4, 0xFF)])])
+    j = kat.jobs([dict(cpu=6, L=100), dict(cpu=2, L=100), dict(cpu=8, L=60, part=1), dict(cpu=2, L=100), dict(cpu=4, L=30, k=2, part=1),
+                  dict(cpu=1, L=10)])
+    j.reservation = np.array([abi.RESV_NONE, 0, abi.RESV_NONE, 0, abi.RESV_NONE, 3], np.uint32)
+    ref = pyoracle.select(c, j, NOW, running=run, reservations=rv)
+    short = _running([(NOW + 50, None, [(0, 1, 1, 0x1)])])
+    short.alloc_node = np.append(short.alloc_node, np.uint32(1))      # num_allocs = alloc_offsets[num_jobs] + 1
+    refused = [lambda e: e.set_reservations(_resv([(NOW, NOW + 10, [(1, 1, 1, 0x1), (1, 1, 1, 0x2)])])),   # a node twice
+               lambda e: e.set_reservations(_resv([(NOW, NOW + 10, [(2, 1, 1, 0x1), (8, 1, 1, 0x1)])])),   # a node >= num_nodes
+               lambda e: e.set_running(short)]
+    eng = engine_cls(device=0)
+    try:
+        eng.set_nodes(c); eng.set_reservations(rv); eng.set_running(run)
+        first = eng.node_select(NOW, j)
+        helpers.assert_same(eng, first, ref, c, tag="before the refused calls")
+        for i, call in enumerate(refused):
+            with pytest.raises(EngineError) as ei:
+                call(eng)
+            assert ei.value.status == -1
+            eng.set_running(run)
+            got = eng.node_select(NOW, j)
+            assert got.diff(first) is None, got.diff(first)
+            assert np.array_equal(got.reason[:j.num_jobs], first.reason[:j.num_jobs])
+            helpers.assert_same(eng, got, ref, c, tag=f"after refused call {i}")
+    finally:
+        eng.close()
+
+
 def core_id_shortfall_case():
     """res_avail with FEWER core ids than cpus (cpu_total 4, core ids {0,1}: the node table does not force them to
     agree) and two future dips whose core sets are disjoint, so the window minimum of a long job has an EMPTY core set:
