@@ -1,6 +1,7 @@
 // The CSR rules of the callers' lists, checked on the host: an offsets array [n + 1] starts at 0 and never decreases; a node list is
 // sorted here and then names no node twice and — where the caller gives a bound — no node at or above it.  No HIP in here: engine.hip
 // includes it, tests/cpp/csr_host_test.cpp compiles it with g++.  The callers form their own messages from what comes back.
+#pragma once
 #include <algorithm>
 #include <cstdint>
 #include <cstring>

@@ -192,7 +192,7 @@ struct cns_engine {
   u64 prio_bytes = 0;
   // run-limit admission (limits_host.inc)
   DevBuf d_lim[29], d_limpar[17];
-  DevBuf d_step[13];  // step scheduler (steps_host.inc)
+  DevBuf d_step[13];  // step scheduler (steps_call.inc)
   // preemption (include/crane_gpu/preempt.h): what cns_set_running kept of the running set, and the cycle's tables
   std::set<void*> host_bufs;                    // page-locked host buffers handed out by cns_host_alloc
   bool pre_active = false;                      // the next run is a cycle with preemption (general path of k_select only)
@@ -1360,7 +1360,7 @@ int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity
 
 #include "priority_host.inc"
 #include "limits_host.inc"
-#include "steps_host.inc"
+#include "steps_call.inc"
 #include "probe_host.inc"
 #include "resvq_host.inc"
 #include "valid_host.inc"

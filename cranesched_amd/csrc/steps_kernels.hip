@@ -4,54 +4,18 @@
 // A job's step queue is a chain (a step takes resources out of step_res_avail_, the next one sees what is left, the
 // first one that does not fit stops the queue), but jobs never share an allocation: ONE THREAD PER JOB, thousands of
 // independent chains.  The work per node is the exact bit-mask algebra of the node-selection path (res_dev.h:
-// GetFeasibleResourceInNode, -=), the top-k queue is libstdc++'s heap move for move (as in pq_emul.h, on an 8-byte
-// entry).  Availability lives in HBM as one 56-byte Res per (job, node), updated in place.
+// GetFeasibleResourceInNode, -=), the top-k queue is libstdc++'s heap move for move (step_pq.h: as in pq_emul.h, on an
+// 8-byte entry).  Availability lives in HBM as one Res per (job, node), sizeof(Res) bytes with the c2 / c3 core planes,
+// updated in place.
 //
 // Included by engine.hip (one translation unit, namespace cns).
 #pragma once
+#include "step_pq.h"        // the top-k queue: libstdc++'s heap on an 8-byte entry (no HIP in there)
+#include "steps_host.inc"   // StepRec, and the checks that let the kernel index without bounds of its own (no HIP in there)
 
 namespace cns {
 
-struct StepEnt { u32 ntasks; u32 pos; };   // NodeInfo {ntasks_on_node, craned_id} (:2056-2062)
-// a < b  <=>  a.ntasks_on_node > b.ntasks_on_node (:2059-2061)
-__device__ __forceinline__ bool step_comp(const StepEnt& a, const StepEnt& b) { return a.ntasks > b.ntasks; }
-// std::__push_heap / std::__adjust_heap of GCC's bits/stl_heap.h (see pq_emul.h for the annotated form)
-__device__ __forceinline__ void step_push_up(StepEnt* first, int hole, int top, StepEnt value) {
-  int parent = (hole - 1) / 2;
-  while (hole > top && step_comp(first[parent], value)) {
-    first[hole] = first[parent];
-    hole = parent;
-    parent = (hole - 1) / 2;
-  }
-  first[hole] = value;
-}
-__device__ __forceinline__ void step_pq_push(StepEnt* first, int len) { step_push_up(first, len - 1, 0, first[len - 1]); }
-__device__ __forceinline__ void step_pq_pop(StepEnt* first, int len) {  // len = size before the pop
-  if (len <= 1) return;
-  const StepEnt value = first[len - 1];
-  first[len - 1] = first[0];
-  const int n = len - 1;
-  int hole = 0, child = 0;
-  while (child < (n - 1) / 2) {
-    child = 2 * (child + 1);
-    if (step_comp(first[child], first[child - 1])) child--;
-    first[hole] = first[child];
-    hole = child;
-  }
-  if ((n & 1) == 0 && child == (n - 2) / 2) {
-    child = 2 * (child + 1);
-    first[hole] = first[child - 1];
-    hole = child - 1;
-  }
-  step_push_up(first, hole, 0, value);
-}
-
-struct StepRec {
-  Req node_req, task_req;      // req_node_res_view, req_task_res_view
-  u32 node_num, ntasks, tmin, tmax;
-  u32 incl_b, incl_e, excl_b, excl_e;
-  u64 place_off, task_off;
-};
+using cns_steps::StepRec;
 
 struct StepParams {
   u32 num_jobs, pad;
@@ -62,6 +26,7 @@ struct StepParams {
 };
 
 constexpr int kStepMaxNodes = 64;   // CNS_STEP_MAX_NODES
+static_assert(kStepMaxNodes == CNS_STEP_MAX_NODES, "steps_host.inc refuses what the heap cannot hold");
 
 __global__ __launch_bounds__(64) void k_sched_steps(const StepParams P) {
   const u32 j = blockIdx.x * 64 + threadIdx.x;

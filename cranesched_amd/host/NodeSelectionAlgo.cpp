@@ -2164,7 +2164,12 @@ void GpuNodeSelectionAlgo::SchedulePendingSteps(std::vector<JobStepQueue>& jobs)
   co.node_core_w2 = o_w2.data(); co.node_core_w3 = o_w3.data(); co.task_core_w2 = t_w2.data(); co.task_core_w3 = t_w3.data();
   co.avail_core_w2 = r_w2.data(); co.avail_core_w3 = r_w3.data();
   const int st = cns_schedule_steps(I.h, &cj, &cs, &co, nullptr);
-  if (st != 0) { status_ = st; error_ = cns_last_error(I.h); return; }
+  if (st != 0) {   // refused (CNS_ERR_UNSUPPORTED: a step of more than CNS_STEP_MAX_NODES nodes or CNS_STEP_MAX_TASKS_PER_NODE tasks per node) or failed:
+    status_ = st;  // every step of the pass is left to the caller, LastStatus() / LastError() say why
+    error_ = cns_last_error(I.h);
+    for (StepInScheduler* s : flat) s->scheduled = false;
+    return;
+  }
   status_ = 0;
   error_.clear();
   // ---- write back (:2109-2135) ----

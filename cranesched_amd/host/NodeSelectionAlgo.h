@@ -505,7 +505,8 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   // JobScheduler::StepScheduleThread_'s loop (JobScheduler.cpp:1992-2001) in one call: SchedulePendingSteps for every
   // job of `jobs`.  Steps that were scheduled get `scheduled`, craned_ids, allocated_res, craned_task_map and
   // task_res_map; each job's step_res_avail is updated; the first step of a job that does not fit stops that job's
-  // queue.  A job's nodes are walked in the order of the snapshot (the reference walks an unordered_map).
+  // queue.  A job's nodes are walked in the order of the snapshot (the reference walks an unordered_map).  A pass the engine refuses
+  // (include/crane_gpu/steps.h, "Limits": CNS_ERR_UNSUPPORTED in LastStatus()) leaves every step pending: the caller keeps them.
   void SchedulePendingSteps(std::vector<JobStepQueue>& jobs);
 
   // Measurement / test hook: only the host-side packing of the running jobs (what NodeSelect does before

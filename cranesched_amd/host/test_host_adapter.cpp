@@ -16,6 +16,7 @@
 #include "NodeSelectionAlgo.h"
 #include "adapter_test.h"
 #include "../../include/crane_gpu/node_select.h"   // cns_group_info (several devices)
+#include "../../include/crane_gpu/steps.h"         // CNS_STEP_MAX_TASKS_PER_NODE
 
 using namespace crane;
 
@@ -1432,6 +1433,18 @@ int main(int argc, char** argv) {
       CHECK(sT->craned_task_map.at("cn2") == (std::set<uint32_t>{0, 1}) && sT->craned_task_map.at("cn1") == (std::set<uint32_t>{2, 3, 4}));
       CHECK(sT->allocated_res.at("cn1").cpu_set.cpu_count == cpu_t(3));
       CHECK(a1.at("cn0").cpu_set.cpu_count == cpu_t(1) && a1.at("cn1").cpu_set.cpu_count == cpu_t(0));
+      // a step the engine refuses (include/crane_gpu/steps.h, "Limits") leaves every step of the pass to the caller; the next pass is served
+      ResourceV3 a2{{"cn0", avail(4, 8)}};
+      auto sOk = step(0, 1, 1, 1, 1), sBig = step(1, 1, 1, 1, CNS_STEP_MAX_TASKS_PER_NODE + 1);
+      sOk->scheduled = true;   // (stale from an earlier pass)
+      std::vector<JobStepQueue> r(1);
+      r[0].job_id = 12; r[0].step_res_avail = &a2; r[0].pending_steps = {sOk.get(), sBig.get()};
+      algo.SchedulePendingSteps(r);
+      CHECK(!algo.Ok() && algo.LastStatus() == CNS_ERR_UNSUPPORTED && algo.LastError().find("CNS_STEP_MAX_TASKS_PER_NODE") != std::string::npos);
+      CHECK(!sOk->scheduled && !sBig->scheduled && a2.at("cn0").cpu_set.cpu_count == cpu_t(4));
+      r[0].pending_steps = {sOk.get()};
+      algo.SchedulePendingSteps(r);
+      CHECK(algo.Ok() && sOk->scheduled && a2.at("cn0").cpu_set.cpu_count == cpu_t(3));
     }
 
     // --- a running job shapes the snapshot (cost and availability) ------------------------------------------

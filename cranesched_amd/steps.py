@@ -14,6 +14,7 @@ import numpy as np
 from . import abi
 
 STEP_MAX_NODES = 64
+STEP_MAX_TASKS_PER_NODE = 512   # CNS_STEP_MAX_TASKS_PER_NODE: the largest ntasks_per_node_max served
 _P = C.c_void_p
 
 

@@ -18,7 +18,10 @@
  * a job's nodes are walked in the order given (ascending dense node index).  Which of several equal-capacity nodes
  * leaves the queue, and the pop order, follow libstdc++'s heap exactly (as for NodeSelect's top-k queues).
  *
- * Limits: at most CNS_STEP_MAX_NODES nodes per step; the GRES layout is the handle's (cns_set_nodes).
+ * Limits: at most CNS_STEP_MAX_NODES nodes per step and an ntasks_per_node_max of at most CNS_STEP_MAX_TASKS_PER_NODE (a step
+ * beyond either: CNS_ERR_UNSUPPORTED, nothing of the call is scheduled); the GRES layout is the handle's (cns_set_nodes).
+ * Every offsets array starts at 0 and never decreases; node_offsets / step_offsets end at num_nodes / num_steps, incl_offsets /
+ * excl_offsets end at the length of their list (CNS_ERR_INVALID_ARG otherwise, before anything reaches the device).
  * No CPU fallback: CNS_ERR_NO_DEVICE without a GPU.
  */
 #ifndef CRANE_GPU_STEPS_H_
@@ -33,6 +36,11 @@ extern "C" {
 #endif
 
 #define CNS_STEP_MAX_NODES 64u
+/* Largest ntasks_per_node_max served.  The count of tasks on a node is found one task at a time (CtldPublicDefs.cpp:2083-2088), and a
+ * task request that asks for nothing (cpu 0, memory 0, no GRES) fits for ever, so ntasks_per_node_max is the only bound of that loop
+ * that holds for every request: one GPU thread would spin for up to 2^32 turns.  A design limit taken from what a node can hold, not a
+ * measured number: the engine's widest node has 256 cores and the smallest task share in use is half a core, 256 / (1/2) = 512 tasks. */
+#define CNS_STEP_MAX_TASKS_PER_NODE 512u
 
 /* Jobs with pending steps: their nodes with what is still free inside the job's allocation. */
 typedef struct cns_step_job_soa {
@@ -64,7 +72,7 @@ typedef struct cns_step_soa {
   const uint32_t* node_num;        /* 1 .. CNS_STEP_MAX_NODES */
   const uint32_t* ntasks;          /* >= node_num */
   const uint32_t* ntasks_per_node_min;
-  const uint32_t* ntasks_per_node_max;
+  const uint32_t* ntasks_per_node_max;  /* ntasks_per_node_min .. CNS_STEP_MAX_TASKS_PER_NODE */
   const uint32_t* incl_offsets;    /* [S+1] CSR included_nodes (dense node indices); NULL = none */
   const uint32_t* incl_nodes;
   const uint32_t* excl_offsets;    /* [S+1] CSR excluded_nodes; NULL = none */

@@ -6,7 +6,9 @@
 // unordered_map).  PINNED (round 4): the reference has no test of this function, but the function itself runs here:
 // oracle/_ref compiles CtldPublicDefs.cpp:2038-2159 (sliced at build time by oracle/ref_build/extract.py) and
 // tests/test_ref_pin_limits_steps.py holds this restatement to it (scheduled flags, nodes in pop order, every task's
-// allocation, step_res_avail_ afterwards) on the hand-derived scenarios of tests/test_steps.py and 15 random cases.
+// allocation, step_res_avail_ afterwards) on the hand-derived scenarios of tests/test_steps.py, 15 random cases, and the edge families
+// of tests/steps_edge.py: deep_heap and eviction_ladder (the queue at 63 / 64 / 65 entries with ties), task_gres (task requests that
+// carry GRES), exact_fit, launch_shapes.
 #pragma once
 #include <queue>
 #include <set>

@@ -11,7 +11,10 @@ AccountManager's three look-ups and the CommonStepInCtld members the function to
 Every comparison is exact: the reason of every job (as the reference's STRING), the number admitted, every usage record
 after the pass (cpu, memory, wall time, job count, every GRES name total and class count, and whether the map entry
 exists); for steps: which steps were scheduled, the nodes in the candidate queue's pop order with their task counts and
-summed allocations (core ids, GRES slots), every task's node and allocation, and step_res_avail_ afterwards.
+summed allocations (core ids, GRES slots), every task's node and allocation, and step_res_avail_ afterwards.  The step cases: the two
+hand-derived scenarios and the random cases of tests/test_steps.py (queues of at most 5 entries), and the edge families of
+tests/steps_edge.py — deep_heap and eviction_ladder (queues of up to 65 entries with ties, evictions from a full queue), task_gres (task
+requests that carry GRES, on two layouts), exact_fit, launch_shapes.
 """
 import numpy as np
 import pytest
@@ -20,6 +23,7 @@ from cranesched_amd import abi, limits as lm, synth
 from oracle import pyoracle
 from tests import kat
 from tests import test_run_limits as trl
+from tests import steps_edge
 from tests import test_steps as tst
 
 pytestmark = pytest.mark.skipif(not pyoracle.ref_available(), reason="oracle/_ref is not built and /root/reference is absent")
@@ -150,3 +154,12 @@ def test_reference_steps_random(seed):
 def test_reference_steps_random_core_ids_above_127(seed):
     lay, jobs, steps = tst.random_step_case(seed, J=100, wide=True)
     same_steps(f"steps wide {seed}", lay, jobs, steps)
+
+
+@pytest.mark.parametrize("name", list(steps_edge.CASES))
+def test_reference_steps_edge_families(name):
+    """tests/steps_edge.py: what no other step case reaches — std::priority_queue at 63 / 64 / 65 entries, req_task_res_view with GRES."""
+    lay, jobs, steps = steps_edge.CASES[name]()
+    a = same_steps(name, lay, jobs, steps)
+    if name.startswith(("deep_heap", "task_gres", "eviction", "exact")):
+        assert a.scheduled[:steps.num_steps].any()

@@ -233,6 +233,16 @@ def test_gpu_argument_checks(engine_default):
             eng.schedule_steps(jobs, bad)
         got, _ = eng.schedule_steps(jobs, steps)
         assert list(got.scheduled[:3]) == [1, 0, 0]
+        # two inputs the host pass refuses before any device work (tests/test_steps_host.py holds every refusal on the CPU)
+        backwards = st.StepJobs(jobs.node_offsets, jobs.node_idx, jobs.avail_cpu_raw, jobs.avail_mem, jobs.avail_core_lo, jobs.avail_core_hi,
+                                jobs.avail_gres, [4, 3])                                  # step_offsets that run backwards
+        with pytest.raises(EngineError, match="step_offsets"):
+            eng.schedule_steps(backwards, steps)
+        endless = _steps([dict(k=1, ntasks=2, cpu=1, tmax=st.STEP_MAX_TASKS_PER_NODE + 1), dict(k=1, ntasks=1), dict(k=1, ntasks=1)])
+        with pytest.raises(EngineError, match="CNS_STEP_MAX_TASKS_PER_NODE"):
+            eng.schedule_steps(jobs, endless)
+        got, _ = eng.schedule_steps(jobs, steps)                                          # the handle still serves
+        assert list(got.scheduled[:3]) == [1, 0, 0]
     finally:
         eng.close()
 
@@ -255,8 +265,11 @@ def _pyref_steps(lay, jobs, steps):
     for j in range(jobs.num_jobs):
         lo, hi = int(jobs.node_offsets[j]), int(jobs.node_offsets[j + 1])
         nodes = [int(x) for x in jobs.node_idx[lo:hi]]
-        avail = [_res(lay, jobs.avail_cpu_raw[p], jobs.avail_mem[p], jobs.avail_core_lo[p], jobs.avail_core_hi[p], jobs.avail_gres[p])
-                 for p in range(lo, hi)]
+        # (core ids 128..255: the restatement keeps a set of ids, so they ride in `hi` as bits 64.. of one Python int)
+        w2 = jobs.avail_core_w2 if jobs.avail_core_w2 is not None else np.zeros(jobs.num_nodes, np.uint64)
+        w3 = jobs.avail_core_w3 if jobs.avail_core_w3 is not None else np.zeros(jobs.num_nodes, np.uint64)
+        avail = [_res(lay, jobs.avail_cpu_raw[p], jobs.avail_mem[p], jobs.avail_core_lo[p],
+                      int(jobs.avail_core_hi[p]) | int(w2[p]) << 64 | int(w3[p]) << 128, jobs.avail_gres[p]) for p in range(lo, hi)]
         sts = []
         for s in range(int(jobs.step_offsets[j]), int(jobs.step_offsets[j + 1])):
             incl = set() if steps.incl_offsets is None else set(int(x) for x in steps.incl_nodes[int(steps.incl_offsets[s]):int(steps.incl_offsets[s + 1])])
@@ -273,6 +286,7 @@ def _pyref_steps(lay, jobs, steps):
 
 def _compare_steps(lay, jobs, steps, ref):
     rows, avail, _mask = _pyref_steps(lay, jobs, steps)
+    hi_of = lambda kind, i: int(getattr(ref, kind + "_core_hi")[i]) | int(getattr(ref, kind + "_core_w2")[i]) << 64 | int(getattr(ref, kind + "_core_w3")[i]) << 128
     for s, row in enumerate(rows):
         assert bool(ref.scheduled[s]) == (row is not None), f"step {s}: scheduled {ref.scheduled[s]} (oracle)"
         if row is None:
@@ -280,15 +294,15 @@ def _compare_steps(lay, jobs, steps, ref):
         places, tasks = row
         o, t = int(ref.place_offsets[s]), int(ref.task_offsets[s])
         got = [(int(ref.node_idx[o + i]), int(ref.node_ntasks[o + i]), int(ref.node_cpu_raw[o + i]), int(ref.node_mem[o + i]),
-                int(ref.node_core_lo[o + i]), int(ref.node_core_hi[o + i]), int(ref.node_gres[o + i])) for i in range(len(places))]
+                int(ref.node_core_lo[o + i]), hi_of("node", o + i), int(ref.node_gres[o + i])) for i in range(len(places))]
         want = [(n, k, a.cpu, a.mem) + _mask(lay, a) for n, k, a in places]
         assert got == want, f"step {s}: nodes {got} (oracle) vs {want} (python)"
         got = [(int(ref.task_node[t + i]), int(ref.task_cpu_raw[t + i]), int(ref.task_mem[t + i]), int(ref.task_core_lo[t + i]),
-                int(ref.task_core_hi[t + i]), int(ref.task_gres[t + i])) for i in range(len(tasks))]
+                hi_of("task", t + i), int(ref.task_gres[t + i])) for i in range(len(tasks))]
         want = [(n, a.cpu, a.mem) + _mask(lay, a) for n, a in tasks]
         assert got == want, f"step {s}: tasks {got} (oracle) vs {want} (python)"
     for p, a in enumerate(avail):
-        got = (int(ref.avail_cpu_raw[p]), int(ref.avail_mem[p]), int(ref.avail_core_lo[p]), int(ref.avail_core_hi[p]), int(ref.avail_gres[p]))
+        got = (int(ref.avail_cpu_raw[p]), int(ref.avail_mem[p]), int(ref.avail_core_lo[p]), hi_of("avail", p), int(ref.avail_gres[p]))
         assert got == (a.cpu, a.mem) + _mask(lay, a), f"node row {p}: step_res_avail_ {got} (oracle)"
     return sum(r is not None for r in rows), len(rows), sum(len(r[1]) for r in rows if r is not None)
 
