@@ -637,6 +637,102 @@ class CnsCommitOut(C.Structure):
     _fields_ = [("code", _P), ("counts", _P)]
 
 
+# ---- the pending gate in front of a cycle (include/crane_gpu_gate/pending_gate.h) ----------------------------------------
+GATE_TIME_INFINITE_FUTURE = (1 << 63) - 1
+GATE_TIME_INFINITE_PAST = -(1 << 63)
+(GATE_OK, GATE_OK_ARRAY_PARENT, GATE_HELD, GATE_BEGIN_TIME, GATE_DEPENDENCY, GATE_DEPENDENCY_NEVER, GATE_ARRAY_NO_META, GATE_ARRAY_COMPLETE,
+ GATE_ARRAY_CANCELLED, GATE_ARRAY_DEADLINE, GATE_ARRAY_NO_NEXT, GATE_ARRAY_TASK_LIMIT) = range(12)
+GATE_STR = {GATE_OK: "OK", GATE_OK_ARRAY_PARENT: "OK_ARRAY_PARENT", GATE_HELD: "HELD", GATE_BEGIN_TIME: "BEGIN_TIME", GATE_DEPENDENCY: "DEPENDENCY",
+            GATE_DEPENDENCY_NEVER: "DEPENDENCY_NEVER", GATE_ARRAY_NO_META: "ARRAY_NO_META", GATE_ARRAY_COMPLETE: "ARRAY_COMPLETE",
+            GATE_ARRAY_CANCELLED: "ARRAY_CANCELLED", GATE_ARRAY_DEADLINE: "ARRAY_DEADLINE", GATE_ARRAY_NO_NEXT: "ARRAY_NO_NEXT",
+            GATE_ARRAY_TASK_LIMIT: "ARRAY_TASK_LIMIT"}
+# what the reference writes into job->pending_reason there (JobScheduler.cpp:1381-1392, Array.cpp:238-256); "" where it writes ""
+GATE_REASON = {GATE_OK: "", GATE_OK_ARRAY_PARENT: "", GATE_HELD: "Held", GATE_BEGIN_TIME: "BeginTime", GATE_DEPENDENCY: "Dependency",
+               GATE_DEPENDENCY_NEVER: "DependencyNeverSatisfied", GATE_ARRAY_NO_META: "", GATE_ARRAY_COMPLETE: "ArrayMaterializationComplete",
+               GATE_ARRAY_CANCELLED: "Cancelled", GATE_ARRAY_DEADLINE: "Deadline", GATE_ARRAY_NO_NEXT: "", GATE_ARRAY_TASK_LIMIT: "ArrayTaskLimit"}
+GATE_AP_HAS_META, GATE_AP_HAS_PARENT, GATE_AP_COMPLETE, GATE_AP_CANCEL, GATE_AP_HAS_NEXT, GATE_AP_ALL = 1, 2, 4, 8, 16, 31
+
+
+class CnsGateJobs(C.Structure):
+    _fields_ = [("num_jobs", C.c_uint64), ("job_id", _P), ("held", _P), ("begin_sec", _P), ("dep_is_or", _P), ("dep_ready_sec", _P),
+                ("dep_offsets", _P), ("dep_job", _P), ("dep_delay_sec", _P), ("array_parent", _P), ("ap_flags", _P), ("ap_deadline_sec", _P),
+                ("ap_running", _P), ("ap_run_limit", _P)]
+
+
+class CnsGateEvents(C.Structure):
+    _fields_ = [("num_events", C.c_uint64), ("dependent_job_id", _P), ("dependee_job_id", _P), ("event_sec", _P)]
+
+
+class CnsGateOut(C.Structure):
+    _fields_ = [("code", _P), ("pending", _P), ("num_pending", _P), ("ready_sec", _P), ("dep_erased", _P), ("counts", _P), ("ev_stats", _P)]
+
+
+@dataclass
+class GateJobs:
+    """cns_gate_jobs: the pending map in ascending job id.  None for an optional array is the header's NULL."""
+    job_id: np.ndarray
+    held: Optional[np.ndarray] = None
+    begin_sec: Optional[np.ndarray] = None
+    dep_is_or: Optional[np.ndarray] = None
+    dep_ready_sec: Optional[np.ndarray] = None
+    dep_offsets: Optional[np.ndarray] = None
+    dep_job: Optional[np.ndarray] = None
+    dep_delay_sec: Optional[np.ndarray] = None
+    array_parent: Optional[np.ndarray] = None
+    ap_flags: Optional[np.ndarray] = None
+    ap_deadline_sec: Optional[np.ndarray] = None
+    ap_running: Optional[np.ndarray] = None
+    ap_run_limit: Optional[np.ndarray] = None
+
+    _DTYPES = (("job_id", np.uint32), ("held", np.uint8), ("begin_sec", np.int64), ("dep_is_or", np.uint8), ("dep_ready_sec", np.int64),
+               ("dep_offsets", np.uint64), ("dep_job", np.uint32), ("dep_delay_sec", np.uint64), ("array_parent", np.uint8), ("ap_flags", np.uint8),
+               ("ap_deadline_sec", np.int64), ("ap_running", np.uint64), ("ap_run_limit", np.uint64))
+
+    def __post_init__(self):
+        for f, dt in self._DTYPES:
+            a = getattr(self, f)
+            if a is not None:
+                setattr(self, f, _arr(a, dt))
+
+    @property
+    def num_jobs(self) -> int:
+        return len(self.job_id)
+
+    @property
+    def num_entries(self) -> int:
+        return 0 if self.dep_offsets is None or len(self.dep_offsets) == 0 else int(self.dep_offsets[-1])
+
+    def to_c(self) -> CnsGateJobs:
+        s = CnsGateJobs()
+        s.num_jobs = self.num_jobs
+        for f, _ in self._DTYPES:
+            a = getattr(self, f)
+            setattr(s, f, None if a is None else _ptr(a if len(a) else np.zeros(1, a.dtype)))
+        return s
+
+
+@dataclass
+class GateEvents:
+    """cns_gate_events: the dependency events in queue order."""
+    dependent_job_id: np.ndarray
+    dependee_job_id: np.ndarray
+    event_sec: np.ndarray
+
+    def __post_init__(self):
+        self.dependent_job_id = _arr(self.dependent_job_id, np.uint32)
+        n = len(self.dependent_job_id)
+        self.dependee_job_id = _arr(self.dependee_job_id, np.uint32, n)
+        self.event_sec = _arr(self.event_sec, np.int64, n)
+
+    def to_c(self) -> CnsGateEvents:
+        s = CnsGateEvents()
+        s.num_events = len(self.dependent_job_id)
+        for f in ("dependent_job_id", "dependee_job_id", "event_sec"):
+            a = getattr(self, f)
+            setattr(s, f, _ptr(a if len(a) else np.zeros(1, a.dtype)))
+        return s
+
+
 # ---- the submit limits over a batch of submissions (include/crane_gpu_submit/submit_limits.h) ----------------------------
 SUBMIT_JOB_MAX_TIME_LIMIT_SEC = 315576000000   # kJobMaxTimeLimitSec
 SUBMIT_CARRY = 1

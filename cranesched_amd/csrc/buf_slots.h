@@ -28,6 +28,11 @@ enum { SB_QOS = 0, SB_PL, SB_PARENT, SB_UPL, SB_APL, SB_UQ, SB_AQ, SB_G, SB_ST_S
        SB_PRE, SB_STATE, SB_STAT, SB_COND, SB_IKEY, SB_ITHR, SB_CODE, SB_TLO, SB_CTR,                                           // per job
        SB_SK0, SB_SK1, SB_SV0, SB_SV1, SB_HIST, SB_SKEY, SB_SITEM, SB_SADD, SB_VAL, SB_TAILS, SB_HEADS, SB_CARRY, SB_COUNT };   // the parallel pass
 
+// cns_engine::d_gate (gate_host.inc)
+enum { GT_JOBID = 0, GT_HELD, GT_BEGIN, GT_ISOR, GT_READY, GT_DEPOFF, GT_DEPJOB, GT_DELAY, GT_AP, GT_APFLAGS, GT_APDEAD, GT_APRUN, GT_APLIM,   // jobs
+       GT_EVDEPENDENT, GT_EVDEPENDEE, GT_EVSEC, GT_FIRST,                                                                                     // events
+       GT_CODE, GT_READYOUT, GT_ERASED, GT_WAVES, GT_TOTAL, GT_PENDING, GT_COUNTS, GT_COUNT };                                                // results
+
 // cns_engine::d_pre (engine.hip: a cycle with preemption)
 enum { B_QPOFF, B_QP, B_PJQOS, B_PJQP, B_PJPRIO, B_PJREC0, B_PJK, B_PJEND, B_RNJOB, B_ENTSLOT, B_ENTGONE, B_RJQOS, B_RJQP,
        B_RJSTART, B_RJEND, B_RJPRE, B_RJOFF, B_RJENT, B_HEAD, B_RECNEXT, B_RECORIG, B_RECSLOT, B_RECGONE, B_MISC, B_COUNT };

@@ -26,6 +26,7 @@
 #include "../../include/crane_gpu_valid/validity.h"
 #include "../../include/crane_gpu_commit/commit_check.h"
 #include "../../include/crane_gpu_submit/submit_limits.h"
+#include "../../include/crane_gpu_gate/pending_gate.h"
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
 #include <limits>
@@ -40,10 +41,12 @@
 #include "valid_kernels.inc"  // can each job of a batch ever run in its partition (include/crane_gpu_valid/validity.h)
 #include "commit_kernels.inc" // the commit loop's resource-changed and preempted-alive checks (include/crane_gpu_commit/commit_check.h)
 #include "submit_kernels.inc" // the submit limits over a batch of submissions (include/crane_gpu_submit/submit_limits.h)
+#include "gate_kernels.inc"   // the dependency-event drain and Phase 1 in front of a cycle (include/crane_gpu_gate/pending_gate.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 #include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
 #include "csr_host.inc"        // the CSR rules of the callers' lists: offsets, sorted lists without a repeat (no HIP in there either)
 #include "snapshot_host.inc"   // the layout of a snapshot: groups, refusals, slots, reservations, node types, running entries (no HIP in there either)
+#include "gate_check_host.inc" // the input rules of cns_gate_pending (no HIP in there either)
 #include "buf_slots.h"         // the slots of cns_engine's per-feature buffer sets
 
 using namespace cns;
@@ -168,6 +171,8 @@ struct cns_engine {
   bool vd_tab_have = false, vd_rv_have = false; // the tables derived from the node arrays / from the reservations are built
   // the commit loop's checks behind a cycle (commit_host.inc): the call's events, job arrays and results in buffers of their own
   DevBuf d_cc[CC_COUNT];
+  // the pending gate in front of a cycle (gate_host.inc): the call's jobs, events and results in buffers of their own
+  DevBuf d_gate[GT_COUNT];
   cns_timing timing{};
   std::string last_kernel;
   i64 last_now = 0;
@@ -1366,6 +1371,7 @@ int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity
 #include "valid_host.inc"
 #include "commit_host.inc"
 #include "submit_host.inc"
+#include "gate_host.inc"
 
 }  // extern "C"
 

@@ -51,6 +51,8 @@ VALID_ABI_SYMBOLS = ("cns_validate_jobs", "cns_validate_shape")
 COMMIT_ABI_SYMBOLS = ("cns_commit_check", "cns_commit_shape")
 # ... and include/crane_gpu_submit/submit_limits.h
 SUBMIT_ABI_SYMBOLS = ("cns_set_submit_limits", "cns_check_submissions", "cns_get_submit_usage", "cns_get_submit_timing", "cns_submit_shape")
+# ... and include/crane_gpu_gate/pending_gate.h
+GATE_ABI_SYMBOLS = ("cns_gate_pending", "cns_gate_shape")
 LIMITS_ABI_SYMBOLS = ("cns_set_run_limits", "cns_apply_run_limits", "cns_upload_limit_jobs", "cns_run_limits_resident",
                       "cns_download_limits", "cns_get_limit_timing", "cns_get_usage", "cns_limits_shape")
 
@@ -447,6 +449,35 @@ class GpuNodeSelector:
     def commit_timing(self) -> dict:
         """HIP-event time of the kernels of the last commit_check of this object."""
         return {"kernel_ms": getattr(self, "_commit_ms", 0.0)}
+
+    # -- the pending gate in front of a cycle (include/crane_gpu_gate/pending_gate.h) ------------------------------------------
+    def gate_pending(self, now: int, jobs: "abi.GateJobs", events: "abi.GateEvents | None" = None):
+        """The dependency-event drain and Phase 1 of ScheduleThread_ (JobScheduler.cpp:1353-1413) for every job of the pending map at
+        once.  -> (code, pending, ready_sec, dep_erased, counts, ev_stats): abi.GATE_* per job (the first failing check in the reference's
+        order), the rows that reach NodeSelect in ascending order, the ready times after the events, 1 per dependency entry an event
+        erased, the jobs per code [16], the events applied / without their pending job / without their dependency [3].  Needs a handle
+        only: no snapshot, no cycle."""
+        j, d = jobs.num_jobs, jobs.num_entries
+        code, pending = np.zeros(max(j, 1), np.uint8), np.zeros(max(j, 1), np.uint32)
+        ready, erased = np.zeros(max(j, 1), np.int64), np.zeros(max(d, 1), np.uint8)
+        npend, counts, stats = np.zeros(1, np.uint64), np.zeros(16, np.uint64), np.zeros(3, np.uint64)
+        cj = jobs.to_c()
+        ce = events.to_c() if events is not None else None
+        co = abi.CnsGateOut(abi._ptr(code), abi._ptr(pending), abi._ptr(npend), abi._ptr(ready), abi._ptr(erased), abi._ptr(counts), abi._ptr(stats))
+        ms = C.c_double(0)
+        self._check(self._L.cns_gate_pending(self._h, C.c_int64(now), C.byref(cj), C.byref(ce) if ce is not None else None, C.byref(co), C.byref(ms)))
+        self._gate_ms = ms.value
+        return code[:j], pending[:int(npend[0])], ready[:j], erased[:d], counts, stats
+
+    def gate_shape(self):
+        """(job_chunk, lane_max_deps, scan_span) of the gate's kernels: where their paths change."""
+        a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._check(self._L.cns_gate_shape(C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def gate_timing(self) -> dict:
+        """HIP-event time of the kernels of the last gate_pending of this object."""
+        return {"kernel_ms": getattr(self, "_gate_ms", 0.0)}
 
     # -- the submit limits over a batch of submissions (include/crane_gpu_submit/submit_limits.h) -----------------------------
     def set_submit_limits(self, tables):

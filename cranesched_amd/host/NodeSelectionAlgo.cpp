@@ -22,6 +22,7 @@
 #include "../../include/crane_gpu_valid/validity.h"
 #include "../../include/crane_gpu_commit/commit_check.h"
 #include "../../include/crane_gpu_submit/submit_limits.h"
+#include "../../include/crane_gpu_gate/pending_gate.h"
 
 namespace crane {
 
@@ -1501,6 +1502,91 @@ bool GpuNodeSelectionAlgo::CommitCheck(const std::vector<ResReduceEvent>& events
     if (code[j] >= CNS_COMMIT_RESOURCE_CHANGED && code[j] <= CNS_COMMIT_WAITING_PREEMPTION)
       const_cast<PdJobInScheduler*>(I.last_ord[j])->reason = kReason[code[j]];                             // :1518-1552
   if (codes) codes->assign(code.begin(), code.begin() + J);
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The pending gate in front of NodeSelect (include/crane_gpu_gate/pending_gate.h)
+// ---------------------------------------------------------------------------------------------------------
+bool GpuNodeSelectionAlgo::BuildPendingQueue(TimeSec now, const std::vector<PendingGateJob>& jobs, const std::vector<DependencyEvent>& events,
+                                             PendingGateResult* out) {
+  Impl& I = *impl_;
+  *out = PendingGateResult{};
+  auto fail = [&](int st, const std::string& msg) { status_ = st; error_ = msg; return false; };
+  if (!I.h) return fail(status_ ? status_ : CNS_ERR_NO_DEVICE, error_);
+  const size_t J = jobs.size();
+  // ---- m_pending_job_map_'s order (:1377), every deps map as a list sorted by its key ----
+  std::vector<uint32_t> row(J);
+  for (size_t i = 0; i < J; ++i) row[i] = (uint32_t)i;
+  std::sort(row.begin(), row.end(), [&](uint32_t a, uint32_t b) { return jobs[a].job_id < jobs[b].job_id; });
+  std::vector<uint32_t> job_id(J + 1), dep_job;
+  std::vector<uint8_t> held(J + 1), is_or(J + 1), ap(J + 1), ap_flags(J + 1);
+  std::vector<int64_t> begin(J + 1), ready(J + 1), ap_dead(J + 1);
+  std::vector<uint64_t> off(J + 1, 0), delay, ap_run(J + 1), ap_lim(J + 1);
+  std::vector<std::pair<job_id_t, uint64_t>> list;
+  bool any_ap = false;
+  for (size_t r = 0; r < J; ++r) {
+    const PendingGateJob& j = jobs[row[r]];
+    job_id[r] = j.job_id; held[r] = j.held ? 1 : 0; begin[r] = j.begin_time;
+    const DependenciesInJob* d = j.dependencies;
+    is_or[r] = d && d->is_or ? 1 : 0;
+    ready[r] = d ? d->ready_time : INT64_MIN;
+    if (d) {
+      list.clear();
+      for (const auto& [dependee, type_delay] : d->deps) list.emplace_back(dependee, type_delay.second);
+      std::sort(list.begin(), list.end());
+      for (const auto& [dependee, dl] : list) { dep_job.push_back(dependee); delay.push_back(dl); }
+    }
+    off[r + 1] = dep_job.size();
+    ap[r] = j.is_array_parent ? 1 : 0;
+    any_ap |= j.is_array_parent;
+    const ArrayParentGate& a = j.array;
+    ap_flags[r] = (uint8_t)((a.has_meta ? CNS_GATE_AP_HAS_META : 0u) | (a.has_parent ? CNS_GATE_AP_HAS_PARENT : 0u) | (a.materialization_complete ? CNS_GATE_AP_COMPLETE : 0u) |
+                            (a.cancel_requested ? CNS_GATE_AP_CANCEL : 0u) | (a.has_next_task ? CNS_GATE_AP_HAS_NEXT : 0u));
+    ap_dead[r] = a.deadline_time; ap_run[r] = a.running_children; ap_lim[r] = a.run_limit;
+  }
+  const size_t D = dep_job.size(), E = events.size();
+  dep_job.push_back(0); delay.push_back(0);   // (a pointer to hand over also where D == 0)
+  cns_gate_jobs gj{};
+  gj.num_jobs = J;
+  gj.job_id = job_id.data(); gj.held = held.data(); gj.begin_sec = begin.data();
+  gj.dep_is_or = is_or.data(); gj.dep_ready_sec = ready.data(); gj.dep_offsets = off.data(); gj.dep_job = dep_job.data(); gj.dep_delay_sec = delay.data();
+  if (any_ap) { gj.array_parent = ap.data(); gj.ap_flags = ap_flags.data(); gj.ap_deadline_sec = ap_dead.data(); gj.ap_running = ap_run.data(); gj.ap_run_limit = ap_lim.data(); }
+  std::vector<uint32_t> e_dependent(E + 1), e_dependee(E + 1);
+  std::vector<int64_t> e_sec(E + 1);
+  for (size_t e = 0; e < E; ++e) { e_dependent[e] = events[e].dependent_job_id; e_dependee[e] = events[e].dependee_job_id; e_sec[e] = events[e].event_time; }
+  cns_gate_events ge{};
+  ge.num_events = E; ge.dependent_job_id = e_dependent.data(); ge.dependee_job_id = e_dependee.data(); ge.event_sec = e_sec.data();
+  std::vector<uint8_t> code(J + 1), erased(D + 1);
+  std::vector<uint32_t> pending(J + 1);
+  std::vector<int64_t> ready_out(J + 1);
+  uint64_t num_pending = 0;
+  PendingGateResult R;
+  cns_gate_out go{code.data(), pending.data(), &num_pending, ready_out.data(), erased.data(), R.counts, R.ev_stats};
+  const int st = cns_gate_pending(I.h, now, &gj, &ge, &go, &R.kernel_ms);
+  if (st != 0) return fail(st, cns_last_error(I.h));
+  status_ = 0;
+  error_.clear();
+  static const char* const kReason[] = {"", "", "Held", "BeginTime", "Dependency", "DependencyNeverSatisfied", "", "ArrayMaterializationComplete", "Cancelled", "Deadline", "",
+                                        "ArrayTaskLimit"};
+  static_assert(CNS_GATE_HELD == 2 && CNS_GATE_BEGIN_TIME == 3 && CNS_GATE_DEPENDENCY == 4 && CNS_GATE_DEPENDENCY_NEVER == 5 && CNS_GATE_ARRAY_COMPLETE == 7 &&
+                CNS_GATE_ARRAY_CANCELLED == 8 && CNS_GATE_ARRAY_DEADLINE == 9 && CNS_GATE_ARRAY_TASK_LIMIT == 11, "kReason follows cns_gate_code");
+  R.code.resize(J); R.reason.resize(J);
+  for (size_t r = 0; r < J; ++r) {
+    const PendingGateJob& j = jobs[row[r]];
+    R.code[row[r]] = code[r];
+    R.reason[row[r]] = kReason[code[r] <= CNS_GATE_ARRAY_TASK_LIMIT ? code[r] : 0];                  // :1381-1392, Array.cpp:238-256
+    if (DependenciesInJob* d = j.dependencies) {                                                    // what the UpdateDependency calls of :1364 leave
+      d->ready_time = ready_out[r];                                                                 // CtldPublicDefs.cpp:154-158
+      for (uint64_t x = off[r]; x < off[r + 1]; ++x) if (erased[x]) d->deps.erase(dep_job[x]);      // CtldPublicDefs.cpp:159
+    }
+  }
+  R.pending.resize(num_pending); R.materializes_array_child.resize(num_pending);
+  for (uint64_t k = 0; k < num_pending; ++k) {
+    R.pending[k] = row[pending[k]];
+    R.materializes_array_child[k] = code[pending[k]] == CNS_GATE_OK_ARRAY_PARENT;                   // :1406
+  }
+  *out = std::move(R);
   return true;
 }
 

@@ -444,6 +444,62 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
                    const std::unordered_set<job_id_t>& running_alive, const std::unordered_set<job_id_t>& pending_alive,
                    std::vector<uint8_t>* codes = nullptr, double* kernel_ms = nullptr);
 
+  // ---- the pending gate in front of NodeSelect (include/crane_gpu_gate/pending_gate.h) ------------------------------------------------
+  // The dependency-event drain (JobScheduler.cpp:1353-1372) and Phase 1 (:1374-1413) of ScheduleThread_ for the whole pending map at
+  // once: which jobs reach NodeSelect this cycle.  Inputs in the reference's own shapes:
+  //   jobs     one entry per job of m_pending_job_map_, in any order: Held() as the caller evaluated it, begin_time, a pointer to the
+  //            job's DependenciesInJob (CtldPublicDefs.h:454-469; null: the struct's defaults, no dependencies) and, for an array parent,
+  //            what PrepareParentForMaterialization and SpawnBlockReason read (Array.cpp:683-699, :236-259);
+  //   events   what m_dependency_event_queue_ handed out (:1357), in queue order.
+  // The adapter sorts the jobs by id (the btree order of :1377) and every dependency list by dependee, calls cns_gate_pending, and
+  // then leaves every DependenciesInJob as the reference's UpdateDependency calls would: ready_time folded, the applied entries erased
+  // (CtldPublicDefs.cpp:154-159).  Feeding the same structs into the next cycle's call therefore continues where the reference's
+  // JobInCtld would.  Times are whole seconds (fractional times rounded UP, pending_gate.h "Time domain"); kInfiniteFuture /
+  // kInfinitePast are absl::InfiniteFuture() / InfinitePast().
+  // out->code[i] / reason[i]: cns_gate_code and the pending_reason string of jobs[i]; out->pending: indices into `jobs` in ascending
+  // job id, the pending_jobs vector of :1375-1413; materializes_array_child alongside (:1406).  Held() itself, the array manager's
+  // bookkeeping, the construction of PdJobInScheduler and TriggerDependencyEvents stay with the caller.  Needs a device, no snapshot.
+  // false on an engine error (no device, two jobs with one id or another refused input): `out` is empty, no DependenciesInJob is written
+  // and Ok() / LastStatus() / LastError() say why; nothing is thrown.
+  struct DependenciesInJob {   // CtldPublicDefs.h:454-469
+    std::unordered_map<job_id_t, std::pair<int, uint64_t>> deps;   // dependee -> (crane::grpc::DependencyType, delay seconds)
+    bool is_or{false};
+    TimeSec ready_time{INT64_MIN};
+  };
+  struct ArrayParentGate {
+    bool has_meta{true};               // FindMeta_(parent.JobId()) != nullptr        Array.cpp:686
+    bool has_parent{true};             // parent_job_ != nullptr                      Array.cpp:237
+    bool materialization_complete{false};
+    bool cancel_requested{false};
+    TimeSec deadline_time{INT64_MAX};
+    bool has_next_task{true};          // NextMaterializableTaskId().has_value()      Array.cpp:249
+    uint64_t running_children{0};      // RunningChildCount()
+    uint64_t run_limit{UINT64_MAX};    // ArrayUtil::EffectiveRunLimit(array_spec)
+  };
+  struct PendingGateJob {
+    job_id_t job_id{0};
+    bool held{false};
+    TimeSec begin_time{INT64_MIN};
+    DependenciesInJob* dependencies{nullptr};
+    bool is_array_parent{false};
+    ArrayParentGate array;
+  };
+  struct DependencyEvent {   // JobScheduler.h: DependencyEvent
+    job_id_t dependent_job_id{0}, dependee_job_id{0};
+    TimeSec event_time{0};
+  };
+  struct PendingGateResult {
+    std::vector<uint8_t> code;                       // [jobs.size()] cns_gate_code
+    std::vector<const char*> reason;                 // [jobs.size()] job->pending_reason
+    std::vector<uint32_t> pending;                   // indices into jobs: pending_jobs, in its order
+    std::vector<uint8_t> materializes_array_child;   // [pending.size()]
+    uint64_t counts[16]{};                           // jobs per code
+    uint64_t ev_stats[3]{};                          // events applied, without their pending job, without their dependency
+    double kernel_ms{0.0};
+  };
+  static constexpr TimeSec kInfiniteFuture = INT64_MAX;   // absl::InfiniteFuture()
+  bool BuildPendingQueue(TimeSec now, const std::vector<PendingGateJob>& jobs, const std::vector<DependencyEvent>& events, PendingGateResult* out);
+
   // ---- the submit limits over a batch of submissions (include/crane_gpu_submit/submit_limits.h) -----------------------------------------
   // AccountMetaContainer::TryMallocMetaSubmitResource + MallocMetaSubmitResource (AccountMetaContainer.cpp:75-153, the call at
   // JobScheduler.cpp:3465-3476) for every request, IN THE ORDER GIVEN (arrival order): request i sees the submit counts as requests 0..i-1
