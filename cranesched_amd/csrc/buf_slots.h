@@ -1,9 +1,12 @@
 // The slots of cns_engine's per-feature device buffer sets: one enum per set, its *_COUNT sizes the array.
 #pragma once
 
-// cns_engine::d_pb (probe_host.inc)
-enum { PB_RAW0 = 0 /* .. 15: the caller's arrays, as cns_engine::d_raw */, PB_JOBS = 16, PB_INCL, PB_EXCL, PB_REASON, PB_RESULTS, PB_PARAMS, PB_PART, PB_CTR,
-       PB_HEAP, PB_JTAG, PB_FAULT, PB_COUNT };
+// JobTable::raw (engine.hip, job_table.inc): the caller's job arrays as uploaded, then what the host pass adds; k_pack_jobs reads them all
+enum { JR_LIMIT = 0, JR_NCPU, JR_NMEM, JR_TCPU, JR_TMEM, JR_K, JR_NTASKS, JR_TMIN, JR_TMAX, JR_EXCL, JR_GTOT, JR_GSPEC, JR_INCL_OFF, JR_EXCL_OFF,
+       JR_PLACE_OFF, JR_GROUPED, JR_COUNT };
+
+// cns_engine::d_pb (probe_host.inc): what the probes need besides their job table (cns_engine::pt)
+enum { PB_PARAMS = 0, PB_PART, PB_CTR, PB_HEAP, PB_FAULT, PB_COUNT };
 
 // cns_engine::d_rq (resvq_host.inc)
 enum { RQ_LATEST = 0, RQ_RVOFF, RQ_RVST, RQ_RVED, RQ_RAW_END, RQ_RAW_OFF, RQ_RAW_NODE,                              // state

@@ -2,8 +2,8 @@
 // Host work: validation of the caller's lists in the pass that copies them (every affected reservation's node list sorted on the way: a
 // node twice shows as two equal neighbours, and membership on the device is a bisection), the reservation -> affected-slot table, the
 // buffers.  Every test of a job against a node, a reservation or a running job runs on the device (commit_kernels.inc), on the
-// cycle's results where they are: cns_engine::d_results (start, reason, the node of every record) and d_raw[14] (the place offsets),
-// both read only.  Everything the call writes lives in cns_engine::d_cc.  No CPU fallback.
+// cycle's results where they are: the queue's JobTable, cns_engine::q (results: start, reason, the node of every record; and
+// raw[JR_PLACE_OFF]: the place offsets), both read only.  Everything the call writes lives in cns_engine::d_cc.  No CPU fallback.
 
 static int commit_impl(cns_handle* h, const cns_commit_events* ev, const cns_commit_jobs* jb, const cns_commit_out* out, double* kernel_ms) {
   const u64 J = jb->num_jobs;
@@ -92,11 +92,11 @@ static int commit_impl(cns_handle* h, const cns_commit_events* ev, const cns_com
       if (int rc = stage(h, B[CC_ALIVE], jb->running_alive, jb->running_alive ? (size_t)jb->num_running : 0)) return rc;
     }
     HIPCHK(h, B[CC_CODE].ensure((size_t)J));
-    const char* rb = h->d_results.as<char>();
+    const char* rb = h->q.results.as<char>();
     CcParams P{};
     P.J = J; P.N = N; P.V = V; P.A = A; P.R = jb->running_alive ? jb->num_running : 0;
-    P.start = (const i64*)(rb + h->ro.start); P.reason = (const uint8_t*)(rb + h->ro.reason);
-    P.place_off = h->d_raw[14].as<u64>(); P.place_node = (const u32*)(rb + h->ro.node);
+    P.start = (const i64*)(rb + h->q.ro.start); P.reason = (const uint8_t*)(rb + h->q.ro.reason);
+    P.place_off = h->q.raw[JR_PLACE_OFF].as<u64>(); P.place_node = (const u32*)(rb + h->q.ro.node);
     P.limit = B[CC_LIMIT].as<i64>();
     P.resv = jb->reservation ? B[CC_RESV].as<u32>() : nullptr;
     P.gone = jb->gone ? B[CC_GONE].as<uint8_t>() : nullptr;
@@ -131,8 +131,8 @@ int cns_commit_check(cns_handle* h, const cns_commit_events* ev, const cns_commi
   if (!h || !jobs || !out) return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: null argument");
   if (kernel_ms) *kernel_ms = 0.0;
   if (!h->have_run) return fail(h, CNS_ERR_STATE, "cns_commit_check before a successful cycle");
-  if (jobs->num_jobs != h->J)
-    return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: num_jobs " + std::to_string(jobs->num_jobs) + " is not the last cycle's " + std::to_string(h->J));
+  if (jobs->num_jobs != h->q.J)
+    return fail(h, CNS_ERR_INVALID_ARG, "cns_commit_check: num_jobs " + std::to_string(jobs->num_jobs) + " is not the last cycle's " + std::to_string(h->q.J));
   const int rc = commit_impl(h, ev, jobs, out, kernel_ms);
   if (rc != 0) drain(h);   // nothing of the call is left in flight, the message survives
   return rc;

@@ -109,6 +109,17 @@ struct PinBuf {
   template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
+// One uploaded cns_job_soa and its results.  The engine holds two: the cycle's queue (cns_engine::q) and the what-if probes against the
+// cycle's final state (cns_engine::pt).  job_table.inc has the steps the two callers sequence.
+struct JobTable {
+  DevBuf raw[JR_COUNT];                                  // the caller's arrays as uploaded, the place offsets, the grouped table (buf_slots.h)
+  DevBuf incl, excl, jtag, jobs, reason_init, results;   // node lists, member tags, the 64-dword records, the pre-set reasons, the packed results
+  PinBuf h_place, h_grouped, h_reason, h_jtag;           // what the host pass computes; h_place [J + 1] also answers a download's place_offsets
+  cns_jobs_host::ResOff ro{};                            // the sections of `results`
+  u64 J = 0, Jg = 0, places = 0;                         // jobs, those that reach an ordered loop, placement records (set with ro: table_layout)
+  std::vector<u32> job_part;                             // job (index of the caller's arrays) -> engine partition (kNone: not given to an ordered loop)
+};
+
 }  // namespace
 
 struct cns_engine {
@@ -128,7 +139,7 @@ struct cns_engine {
   u32 num_cus = 0;                            // compute units of the device (0: unknown); k_wide needs one per workgroup, all resident at once
   std::vector<uint8_t> refused_probe;         // the statuses of the last cns_set_nodes call that computed them: a success, or the failure because EVERY
                                               // partition was refused (empty after any other failure)
-  DevBuf d_slot_block, d_sib_off, d_sib, d_type_tag, d_jtag;
+  DevBuf d_slot_block, d_sib_off, d_sib, d_type_tag;
   GresDev gres{};
   bool have_nodes = false, have_jobs = false, have_run = false;
 
@@ -136,21 +147,15 @@ struct cns_engine {
   // device buffers
   DevBuf d_part_off, d_slot_node, d_type_total, d_blocks, d_cost, d_fcpu,
       d_fmem, d_fcnt, d_dipt, d_dipcm, d_dipg, d_rn_off, d_rn_end, d_rn_res, d_heap, d_bfj, d_gupd, d_fault;
-  DevBuf d_pj_off, d_jobs, d_incl, d_excl, d_reason_init, d_results, d_params, d_prof, d_wide;
-  DevBuf d_raw[16];  // the caller's job arrays as uploaded (k_pack_jobs reads them; d_raw[14] = place offsets)
-  // job table
-  u64 J = 0, Jg = 0, places = 0, jobs_ordered = 0, algo_bytes = 0;
+  DevBuf d_pj_off, d_params, d_prof, d_wide;
+  JobTable q;                                   // the cycle's queue (cns_upload_jobs)
+  u64 jobs_ordered = 0, algo_bytes = 0;
   u64 window_shaped = 0;   // jobs of the uploaded queue that a window of k_wide can decide: one node, one task per node, no GRES, no node lists, not exclusive
-  PinBuf h_place, h_grouped, h_reason, h_jtag;   // host staging of cns_upload_jobs (page-locked)
   u32 host_threads = 0;                         // cns_set_host_threads (0: CNS_HOST_THREADS, else up to 16)
-  const u64* place_off = nullptr;               // [J + 1] first placement record per job (in h_place)
-  struct ResOff { size_t start, cpu, mem, clo, chi, gres, node, ntasks, reason, c2, c3, total; } ro{};
-  // what-if probes against the final state of the last cycle (probe_host.inc): table, results and scratch in buffers of their own
+  // what-if probes against the final state of the last cycle (probe_host.inc): a table and results of their own, and their scratch
+  JobTable pt;
   DevBuf d_pb[PB_COUNT];
-  ResOff pro{};
-  u64 pJ = 0, pJg = 0, pplaces = 0;             // probes of the last cns_probe_upload, those that reach a walk, their placement records
-  u32 pkmax = 1;                                // ... and their widest node_num
-  std::vector<u64> probe_place_off;             // [pJ + 1]
+  u32 pkmax = 1;                                // the widest node_num of the probes that reach a walk
   bool have_probes = false, probes_answered = false;
   bool pre_call = false;                        // inside cns_select_preempt with preemption enabled
   bool run_preempt = false;                     // the last successful cycle was such a call (probes are not served behind it)
@@ -176,7 +181,6 @@ struct cns_engine {
   cns_timing timing{};
   std::string last_kernel;
   i64 last_now = 0;
-  std::vector<u32> job_part;                    // pending job (queue index) -> engine partition (kNone: not given to the ordered loop)
   std::vector<u64> part_jobs;                   // engine partition -> jobs of the uploaded queue that reach its ordered loop
   std::vector<uint8_t> pre_part;                // cycle with preemption: engine partition has a pending job whose qos may preempt
   DevBuf d_params2, d_pmap_a, d_pmap_b, d_wide_last;
@@ -248,7 +252,9 @@ int stage(cns_engine* h, DevBuf& b, const void* src, size_t bytes) {
 template <class T>
 int upload(cns_engine* h, DevBuf& b, const std::vector<T>& v) { return stage(h, b, v.data(), v.size() * sizeof(T)); }
 
-size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
+using cns_jobs_host::align16;
+
+#include "job_table.inc"   // the steps of a JobTable: check, lists_check, stage, route, layout, pack, reset, bind, download
 
 int build_gres(cns_engine* h, const cns_gres_layout& g) {
   GresDev d{};
@@ -337,21 +343,7 @@ void fill_params(cns_engine* h, KParams& K, i64 now, const RunKnobs& kn = RunKno
   K.rn_end = h->d_rn_end.as<i64>();
   K.rn_res = h->d_rn_res.as<Res>();
   K.pj_off = h->d_pj_off.as<u64>();
-  K.jobrec = h->d_jobs.as<u32>();
-  K.incl_nodes = h->d_incl.as<u32>();
-  K.excl_nodes = h->d_excl.as<u32>();
-  char* rb = h->d_results.as<char>();
-  K.o_start = (i64*)(rb + h->ro.start);
-  K.o_cpu = (i64*)(rb + h->ro.cpu);
-  K.o_mem = (u64*)(rb + h->ro.mem);
-  K.o_clo = (u64*)(rb + h->ro.clo);
-  K.o_chi = (u64*)(rb + h->ro.chi);
-  K.o_c2 = h->lay.wide_cores ? (u64*)(rb + h->ro.c2) : nullptr;
-  K.o_c3 = h->lay.wide_cores ? (u64*)(rb + h->ro.c3) : nullptr;
-  K.o_gres = (u64*)(rb + h->ro.gres);
-  K.o_node = (u32*)(rb + h->ro.node);
-  K.o_ntasks = (u32*)(rb + h->ro.ntasks);
-  K.o_reason = (uint8_t*)(rb + h->ro.reason);
+  table_bind(h, h->q, K);
   K.heap = h->d_heap.as<HeapEnt>();
   K.bf_j = h->d_bfj.as<u32>();
   K.g_upd = h->d_gupd.as<UpdRec>();
@@ -712,125 +704,38 @@ static int upload_jobs_impl(cns_handle* h, const cns_job_soa* jb);
 // queue that fails validation) returns only after the copies from the caller's arrays have drained.
 int cns_upload_jobs(cns_handle* h, const cns_job_soa* jb) {
   const int rc = upload_jobs_impl(h, jb);
-  if (rc != 0 && h && h->have_nodes) {
-    const std::string keep = h->err;            // (the drain must not replace the error it follows)
-    if (hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
-    (void)hipGetLastError();
-    h->err = keep;
-  }
+  if (rc != 0 && h && h->have_nodes) drain(h);
   return rc;
 }
 static int upload_jobs_impl(cns_handle* h, const cns_job_soa* jb) {
   if (!h || !jb) return fail(h, CNS_ERR_INVALID_ARG, "cns_upload_jobs: null argument");
   if (!h->have_nodes) return fail(h, CNS_ERR_STATE, "cns_upload_jobs before cns_set_nodes");
-  const u64 J = jb->num_jobs;
-  if (J && (!jb->partition || !jb->time_limit_sec || !jb->node_mem || !jb->task_cpu_raw || !jb->task_mem ||
-            !jb->node_num || !jb->ntasks || !jb->ntasks_per_node_min || !jb->ntasks_per_node_max))
-    return fail(h, CNS_ERR_INVALID_ARG, "cns_upload_jobs: missing array");
-  if (J > 0xFFFFFFF0ull) return fail(h, CNS_ERR_UNSUPPORTED, "more than 2^32-16 jobs");
+  if (int rc = table_check(h, jb, kQueueMsgs)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   hipEvent_t e0 = h->ev[0], e1 = h->ev[1];
   HIPCHK(h, hipEventRecord(e0, h->stream));
   h->have_jobs = h->have_run = false;
-  const u64 batch = h->cfg.scheduled_batch_size ? std::min<u64>(h->cfg.scheduled_batch_size, J) : J;
-  // The caller's arrays go to the device as they are (k_pack_jobs builds the 32-dword job records there); from page-locked arrays
-  // (cns_host_alloc) these are DMA transfers the thread does not wait for, and both host passes below run in their shadow.  A queue
-  // that fails validation returns only after the transfers have drained: the caller owns its arrays again when the call is back.
-  // (offsets without their node list are reported below, after the checks that come first: stage() issues no copy from a null source)
-  DevBuf* rb_ = h->d_raw;  // 0 L, 1 ncpu, 2 nmem, 3 tcpu, 4 tmem, 5 k, 6 ntasks, 7 tmin, 8 tmax, 9 excl, 10 gtot, 11 gspec, 12 incl_off,
-                           // 13 excl_off, 14 place_off, 15 grouped
-  if (int rc = stage(h, rb_[0], jb->time_limit_sec, J * 8)) return rc;
-  if (jb->node_cpu_raw) { if (int rc = stage(h, rb_[1], jb->node_cpu_raw, J * 8)) return rc; }
-  if (int rc = stage(h, rb_[2], jb->node_mem, J * 8)) return rc;
-  if (int rc = stage(h, rb_[3], jb->task_cpu_raw, J * 8)) return rc;
-  if (int rc = stage(h, rb_[4], jb->task_mem, J * 8)) return rc;
-  if (int rc = stage(h, rb_[5], jb->node_num, J * 4)) return rc;
-  if (int rc = stage(h, rb_[6], jb->ntasks, J * 4)) return rc;
-  if (int rc = stage(h, rb_[7], jb->ntasks_per_node_min, J * 4)) return rc;
-  if (int rc = stage(h, rb_[8], jb->ntasks_per_node_max, J * 4)) return rc;
-  if (jb->exclusive) { if (int rc = stage(h, rb_[9], jb->exclusive, J)) return rc; }
-  if (jb->gres_total) { if (int rc = stage(h, rb_[10], jb->gres_total, J * CNS_MAX_GRES_NAMES)) return rc; }
-  if (jb->gres_spec) { if (int rc = stage(h, rb_[11], jb->gres_spec, J * CNS_MAX_GRES_CLASSES)) return rc; }
-  if (jb->incl_offsets) { if (int rc = stage(h, rb_[12], jb->incl_offsets, (J + 1) * 8)) return rc; }
-  if (jb->excl_offsets) { if (int rc = stage(h, rb_[13], jb->excl_offsets, (J + 1) * 8)) return rc; }
-  const u64 n_incl = jb->incl_offsets ? jb->incl_offsets[J] : 0, n_excl = jb->excl_offsets ? jb->excl_offsets[J] : 0;
-  HIPCHK(h, h->d_incl.ensure(std::max<u64>(n_incl, 1) * 4));
-  HIPCHK(h, h->d_excl.ensure(std::max<u64>(n_excl, 1) * 4));
-  if (int rc = stage(h, h->d_incl, jb->incl_nodes, n_incl * 4)) return rc;
-  if (int rc = stage(h, h->d_excl, jb->excl_nodes, n_excl * 4)) return rc;
-  // BasicPriority (JobScheduler.h:185-200) + per-job pre-checks of the ordered loop (cpp:6744-6761): jobs_host.inc, pass 1 — on a few host threads
-  namespace jh = cns_jobs_host;
-  HIPCHK(h, h->h_reason.ensure(std::max<u64>(J, 1)));
-  HIPCHK(h, h->h_place.ensure((J + 1) * 8));
-  if (h->lay.shared) HIPCHK(h, h->h_jtag.ensure(std::max<u64>(J, 1)));
-  h->job_part.resize((size_t)J);
-  jh::Route R;
-  R.P = h->rlay.P; R.Pu = h->lay.Pu; R.P_real = h->lay.P_real; R.V = h->rlay.V;
-  R.upart_refused = h->lay.upart_refused.data(); R.upart_eng = h->lay.upart_eng.data(); R.upart_size = h->lay.upart_size.data();
-  R.upart_tag = h->lay.upart_tag.data(); R.part_off = h->rlay.part_off.data();
-  R.s_node = h->rlay.big_nodes ? 48 : 32; R.gres_classes = h->gres.num_classes; R.batch = batch;
-  jh::Out O;
-  O.reason = h->h_reason.as<uint8_t>(); O.job_part = h->job_part.data(); O.place_off = h->h_place.as<u64>();
-  O.jtag = h->lay.shared ? h->h_jtag.as<uint8_t>() : nullptr;
-  h->place_off = O.place_off;
-  std::vector<jh::Chunk> chunks;
-  {
-    std::string perr;
-    if (const int rc = jh::pass1(jb, R, O, chunks, jh::threads_for(J, h->host_threads), &perr)) { (void)hipStreamSynchronize(h->stream); return fail(h, rc, perr); }
-  }
-  if ((jb->incl_offsets && !jb->incl_nodes && jb->incl_offsets[J]) || (jb->excl_offsets && !jb->excl_nodes && jb->excl_offsets[J])) {
-    (void)hipStreamSynchronize(h->stream);
-    return fail(h, CNS_ERR_INVALID_ARG, "cns_upload_jobs: include / exclude offsets without node lists");
-  }
-  const u64 Jg = O.Jg, places = O.places;
-  const std::vector<u64>& pj_off = O.pj_off;
+  JobTable& T = h->q;
+  const u64 batch = h->cfg.scheduled_batch_size ? std::min<u64>(h->cfg.scheduled_batch_size, jb->num_jobs) : jb->num_jobs;
+  // The copies of the caller's arrays first: both host passes run in their shadow.  A queue that fails validation returns only after
+  // they have drained (cns_upload_jobs).  Offsets without their node list are reported behind the checks of pass 1, which come first.
+  if (int rc = table_stage(h, T, jb)) return rc;
+  // BasicPriority (JobScheduler.h:185-200) + the per-job pre-checks of the ordered loop (cpp:6744-6761)
+  cns_jobs_host::Out O;
+  if (int rc = table_route(h, T, jb, batch, "", O)) return rc;
+  if (int rc = table_lists_check(h, jb, kQueueMsgs)) return rc;
   h->part_jobs.resize(h->rlay.P);
-  for (u32 p = 0; p < h->rlay.P; ++p) h->part_jobs[p] = pj_off[p + 1] - pj_off[p];
-  HIPCHK(h, h->h_grouped.ensure(std::max<u64>(Jg, 1) * 4));
-  O.grouped = h->h_grouped.as<u32>();
-  // pass 2: the offsets of the placement records and the queue grouped by partition in queue order, one u32 per job
-  jh::pass2(jb, O, chunks);
-  if (J == 0) { O.reason[0] = CNS_REASON_NONE; if (O.jtag) O.jtag[0] = 0; }   // (the one-element stand-ins of an empty queue)
-  if (Jg == 0) O.grouped[0] = 0;
-  if (int rc = stage(h, rb_[14], h->h_place.p, (J + 1) * 8)) return rc;
-  if (int rc = stage(h, rb_[15], h->h_grouped.p, std::max<u64>(Jg, 1) * 4)) return rc;
-  if (h->lay.shared) { if (int rc = stage(h, h->d_jtag, h->h_jtag.p, std::max<u64>(J, 1))) return rc; }
-  HIPCHK(h, h->d_jobs.ensure((size_t)std::max<u64>(Jg, 1) * kJobRecDwords * 4));
-  if (Jg) {
-    PackParams K{};
-    K.Jg = Jg; K.grouped = rb_[15].as<u32>();
-    K.L = rb_[0].as<i64>(); K.ncpu = jb->node_cpu_raw ? rb_[1].as<i64>() : nullptr; K.nmem = rb_[2].as<u64>();
-    K.tcpu = rb_[3].as<i64>(); K.tmem = rb_[4].as<u64>(); K.k = rb_[5].as<u32>(); K.ntasks = rb_[6].as<u32>();
-    K.tmin = rb_[7].as<u32>(); K.tmax = rb_[8].as<u32>();
-    K.excl = jb->exclusive ? rb_[9].as<uint8_t>() : nullptr;
-    K.gtot = jb->gres_total ? rb_[10].as<uint8_t>() : nullptr; K.gspec = jb->gres_spec ? rb_[11].as<uint8_t>() : nullptr;
-    K.incl_off = jb->incl_offsets ? rb_[12].as<u64>() : nullptr; K.excl_off = jb->excl_offsets ? rb_[13].as<u64>() : nullptr;
-    K.place_off = rb_[14].as<u64>(); K.jobrec = h->d_jobs.as<u32>();
-    K.tag = h->lay.shared ? h->d_jtag.as<uint8_t>() : nullptr;
-    hipLaunchKernelGGL(k_pack_jobs, dim3((unsigned)((Jg + 255) / 256)), dim3(256), 0, h->stream, K);
-    HIPCHK(h, hipGetLastError());
-  }
-
-  if (int rc = upload(h, h->d_pj_off, pj_off)) return rc;
-  if (int rc = stage(h, h->d_reason_init, h->h_reason.p, std::max<u64>(J, 1))) return rc;
-  // results: one contiguous HBM buffer (also what an RCCL allgather ships)
-  cns_engine::ResOff& r = h->ro;
-  size_t ro = 0;
-  auto rsec = [&](size_t elem, u64 n) { size_t x = ro; ro = align16(ro + elem * (size_t)std::max<u64>(n, 1)); return x; };
-  r.start = rsec(8, J); r.cpu = rsec(8, places); r.mem = rsec(8, places); r.clo = rsec(8, places);
-  r.chi = rsec(8, places); r.gres = rsec(8, places); r.node = rsec(4, places); r.ntasks = rsec(4, places);
-  r.reason = rsec(1, J);
-  r.c2 = r.c3 = ro;   // the planes of core ids 128..255 exist only for a snapshot with such nodes (nothing more to ship otherwise)
-  if (h->lay.wide_cores) { r.c2 = rsec(8, places); r.c3 = rsec(8, places); }
-  r.total = ro;
-  HIPCHK(h, h->d_results.ensure(ro));
+  for (u32 p = 0; p < h->rlay.P; ++p) h->part_jobs[p] = O.pj_off[p + 1] - O.pj_off[p];
+  if (int rc = table_layout(h, T, jb, O)) return rc;
+  if (int rc = table_pack(h, T, jb)) return rc;
+  if (int rc = upload(h, h->d_pj_off, O.pj_off)) return rc;
   HIPCHK(h, hipEventRecord(e1, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   float ms = 0;
   HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
   h->timing = cns_timing{};
   h->timing.h2d_ms = ms;
-  h->J = J; h->Jg = Jg; h->places = places; h->jobs_ordered = batch; h->algo_bytes = O.algo; h->window_shaped = O.n_shaped;
+  h->jobs_ordered = batch; h->algo_bytes = O.algo; h->window_shaped = O.n_shaped;
   h->have_jobs = true;
   return CNS_OK;
 }
@@ -844,14 +749,8 @@ static int run_resident_once(cns_handle* h, int64_t now, const RunKnobs& kn, boo
   HIPCHK(h, hipSetDevice(h->device));
   KParams K;
   fill_params(h, K, now, kn);
-  char* rb = h->d_results.as<char>();
-  const u64 pl = std::max<u64>(h->places, 1), J = std::max<u64>(h->J, 1);
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  HIPCHK(h, hipMemsetAsync(rb + h->ro.start, 0, h->ro.node - h->ro.start, h->stream));  // start + 8-byte records
-  HIPCHK(h, hipMemsetAsync(rb + h->ro.node, 0xFF, 4 * pl, h->stream));                  // CNS_NODE_NONE
-  HIPCHK(h, hipMemsetAsync(rb + h->ro.ntasks, 0, 4 * pl, h->stream));
-  if (h->lay.wide_cores) HIPCHK(h, hipMemsetAsync(rb + h->ro.c2, 0, h->ro.total - h->ro.c2, h->stream));   // core ids 128..255 of the records
-  HIPCHK(h, hipMemcpyAsync(rb + h->ro.reason, h->d_reason_init.p, J, hipMemcpyDeviceToDevice, h->stream));
+  if (int rc = table_reset(h, h->q)) return rc;
   HIPCHK(h, hipMemsetAsync(h->d_fault.p, 0, 16, h->stream));
   if (h->pre_active) {
     // The mutable preemption state starts every PASS empty, not every call: the retry after a k_wide protocol fault re-runs the
@@ -860,19 +759,19 @@ static int run_resident_once(cns_handle* h, int64_t now, const RunKnobs& kn, boo
     DevBuf* B = h->d_pre;
     HIPCHK(h, hipMemsetAsync(B[B_ENTGONE].p, 0, std::max<size_t>(h->run.ent_job.size(), 1), h->stream));
     HIPCHK(h, hipMemsetAsync(B[B_HEAD].p, 0xFF, (size_t)std::max<u32>(h->rlay.S, 1) * 4, h->stream));
-    HIPCHK(h, hipMemsetAsync(B[B_RECGONE].p, 0, pl, h->stream));
+    HIPCHK(h, hipMemsetAsync(B[B_RECGONE].p, 0, std::max<u64>(h->q.places, 1), h->stream));
     HIPCHK(h, hipMemsetAsync(h->pre_params.out_cnt, 0, 16, h->stream));
   }
   HIPCHK(h, hipMemsetAsync(h->d_prof.p, 0, ((size_t)h->rlay.P * (32 + 16) + 2048) * sizeof(u64), h->stream));   // cycle counters + the always-on protocol counters
   HIPCHK(h, h->d_params.ensure(sizeof(KParams)));
   HIPCHK(h, hipMemcpyAsync(h->d_params.p, &K, sizeof(KParams), hipMemcpyHostToDevice, h->stream));
   if (h->rlay.S) hipLaunchKernelGGL(k_init_nodes, dim3((h->rlay.S + 255) / 256), dim3(256), 0, h->stream, h->d_params.as<KParams>());
-  if (h->Jg) hipLaunchKernelGGL(k_prep_jobs, dim3((unsigned)((h->Jg + 255) / 256)), dim3(256), 0, h->stream, h->d_params.as<KParams>(), (u64)h->Jg);
+  if (h->q.Jg) hipLaunchKernelGGL(k_prep_jobs, dim3((unsigned)((h->q.Jg + 255) / 256)), dim3(256), 0, h->stream, h->d_params.as<KParams>(), (u64)h->q.Jg);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
   bool split = false;
   cns_plan::Candidate ca, cb, cc;   // what launched for the plan's a / b / c
-  if (h->Jg) {
+  if (h->q.Jg) {
     cns_plan::Inputs in;
     in.parts.resize(h->rlay.P);
     for (u32 p = 0; p < h->rlay.P; ++p)
@@ -998,37 +897,11 @@ int cns_run_resident(cns_handle* h, int64_t now) {
 int cns_download(cns_handle* h, cns_placement_soa* out) {
   if (!h || !out) return fail(h, CNS_ERR_INVALID_ARG, "cns_download: null argument");
   if (!h->have_run) return fail(h, CNS_ERR_STATE, "cns_download before a successful run");
-  if (out->place_capacity < h->places) return fail(h, CNS_ERR_INVALID_ARG, "cns_download: place_capacity too small");
-  if (!out->start_sec || !out->reason || !out->place_offsets || !out->node_idx || !out->ntasks || !out->cpu_raw ||
-      !out->mem || !out->core_lo || !out->core_hi || !out->gres)
-    return fail(h, CNS_ERR_INVALID_ARG, "cns_download: missing result array");
-  if (h->lay.wide_cores && (!out->core_w2 || !out->core_w3))
-    return fail(h, CNS_ERR_INVALID_ARG, "cns_download: the snapshot has nodes with core ids above 127: core_w2 / core_w3 are required");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  const char* rb = h->d_results.as<char>();
-  auto get = [&](void* dst, size_t off, size_t bytes) -> hipError_t {
-    return bytes ? hipMemcpyAsync(dst, rb + off, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
-  };
-  const size_t J = (size_t)h->J, pl = (size_t)h->places;
-  HIPCHK(h, get(out->start_sec, h->ro.start, 8 * J));
-  HIPCHK(h, get(out->reason, h->ro.reason, J));
-  HIPCHK(h, get(out->cpu_raw, h->ro.cpu, 8 * pl));
-  HIPCHK(h, get(out->mem, h->ro.mem, 8 * pl));
-  HIPCHK(h, get(out->core_lo, h->ro.clo, 8 * pl));
-  HIPCHK(h, get(out->core_hi, h->ro.chi, 8 * pl));
-  HIPCHK(h, get(out->gres, h->ro.gres, 8 * pl));
-  if (h->lay.wide_cores) {
-    HIPCHK(h, get(out->core_w2, h->ro.c2, 8 * pl));
-    HIPCHK(h, get(out->core_w3, h->ro.c3, 8 * pl));
-  } else {
-    if (out->core_w2 && pl) memset(out->core_w2, 0, 8 * pl);
-    if (out->core_w3 && pl) memset(out->core_w3, 0, 8 * pl);
-  }
-  HIPCHK(h, get(out->node_idx, h->ro.node, 4 * pl));
-  HIPCHK(h, get(out->ntasks, h->ro.ntasks, 4 * pl));
+  if (int rc = table_download(h, h->q, out, kQueueMsgs)) return rc;
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-  memcpy(out->place_offsets, h->place_off, 8 * (J + 1));   // (host to host, in the shadow of the transfers)
+  table_offsets(h->q, out);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   float ms = 0;
   HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
@@ -1175,7 +1048,7 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
   std::vector<u32> pj_qos(std::max<u64>(J, 1), 0), pj_qprio(std::max<u64>(J, 1), 0);
   std::vector<double> pj_prio(std::max<u64>(J, 1), 0.0);
   for (u64 j = 0; j < J; ++j) { pj_qos[j] = pre->pd_qos[j]; pj_qprio[j] = pre->pd_qos_priority[j]; pj_prio[j] = pre->pd_priority[j]; }
-  const u64 places = std::max<u64>(h->places, 1);
+  const u64 places = std::max<u64>(h->q.places, 1);
   // work buffers per partition (documented in include/crane_gpu/preempt.h): candidate / chosen lists sized for every running
   // job plus every pending job of the cycle (at most all of them hold resources on one job's nodes), bounded by 64 Mi entries
   // over all partitions; segment-tree pools of 65 536 nodes.  Exceeding either is CNS_ERR_UNSUPPORTED, not a device fault.
@@ -1227,8 +1100,8 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
   h->pre_part.assign(h->rlay.P, 0);
   for (u64 j = 0; j < J; ++j) {
     const u32 q = pre->pd_qos[j];
-    if (j < h->job_part.size() && h->job_part[(size_t)j] != kNone && q < pre->num_qos && pre->qos_preempt_offsets[q + 1] > pre->qos_preempt_offsets[q])
-      h->pre_part[h->job_part[(size_t)j]] = 1;
+    if (j < h->q.job_part.size() && h->q.job_part[(size_t)j] != kNone && q < pre->num_qos && pre->qos_preempt_offsets[q + 1] > pre->qos_preempt_offsets[q])
+      h->pre_part[h->q.job_part[(size_t)j]] = 1;
   }
   h->pre_active = true;
   int rc = cns_run_resident(h, now);
@@ -1280,8 +1153,8 @@ int cns_get_partition_status(const cns_handle* h, uint8_t* status, uint32_t capa
 int cns_device_results(cns_handle* h, void** dptr, uint64_t* bytes) {
   if (!h || !dptr || !bytes) return fail(h, CNS_ERR_INVALID_ARG, "cns_device_results: null argument");
   if (!h->have_jobs) return fail(h, CNS_ERR_STATE, "cns_device_results before cns_upload_jobs");
-  *dptr = h->d_results.p;
-  *bytes = h->ro.total;
+  *dptr = h->q.results.p;
+  *bytes = h->q.ro.total;
   return CNS_OK;
 }
 

@@ -119,10 +119,10 @@ int cns_comm_destroy(cns_handle* h) {
 int cns_results_layout(const cns_handle* h, cns_results_offsets* out) {
   if (!h || !out) return fail(const_cast<cns_handle*>(h), CNS_ERR_INVALID_ARG, "cns_results_layout: null argument");
   if (!h->have_jobs) return fail(const_cast<cns_handle*>(h), CNS_ERR_STATE, "cns_results_layout before cns_upload_jobs");
-  out->num_jobs = h->J; out->num_places = h->places; out->wide_cores = h->lay.wide_cores ? 1u : 0u;
-  out->start_sec = h->ro.start; out->cpu_raw = h->ro.cpu; out->mem = h->ro.mem; out->core_lo = h->ro.clo; out->core_hi = h->ro.chi;
-  out->gres = h->ro.gres; out->node_idx = h->ro.node; out->ntasks = h->ro.ntasks; out->reason = h->ro.reason;
-  out->core_w2 = h->ro.c2; out->core_w3 = h->ro.c3; out->total_bytes = h->ro.total;
+  out->num_jobs = h->q.J; out->num_places = h->q.places; out->wide_cores = h->lay.wide_cores ? 1u : 0u;
+  out->start_sec = h->q.ro.start; out->cpu_raw = h->q.ro.cpu; out->mem = h->q.ro.mem; out->core_lo = h->q.ro.clo; out->core_hi = h->q.ro.chi;
+  out->gres = h->q.ro.gres; out->node_idx = h->q.ro.node; out->ntasks = h->q.ro.ntasks; out->reason = h->q.ro.reason;
+  out->core_w2 = h->q.ro.c2; out->core_w3 = h->q.ro.c3; out->total_bytes = h->q.ro.total;
   return CNS_OK;
 }
 
@@ -131,12 +131,12 @@ int cns_allgather_results(cns_handle* h, uint64_t slot_bytes, void** gathered) {
   if (!h || !gathered) return fail(h, CNS_ERR_INVALID_ARG, "cns_allgather_results: null argument");
   if (!h->comm) return fail(h, CNS_ERR_STATE, "cns_allgather_results before cns_comm_init_rank");
   if (!h->have_run) return fail(h, CNS_ERR_STATE, "cns_allgather_results before a successful run");
-  if (slot_bytes < h->ro.total || (slot_bytes & 15u)) return fail(h, CNS_ERR_INVALID_ARG, "cns_allgather_results: slot_bytes below this rank's results, or not a multiple of 16");
+  if (slot_bytes < h->q.ro.total || (slot_bytes & 15u)) return fail(h, CNS_ERR_INVALID_ARG, "cns_allgather_results: slot_bytes below this rank's results, or not a multiple of 16");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, h->d_gather.ensure((size_t)slot_bytes * h->comm_nranks));
   char* mine = h->d_gather.as<char>() + (size_t)slot_bytes * h->comm_rank;
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  HIPCHK(h, hipMemcpyAsync(mine, h->d_results.p, h->ro.total, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(mine, h->q.results.p, h->q.ro.total, hipMemcpyDeviceToDevice, h->stream));
   NCCLCHK_H(h, ncclAllGather(mine, h->d_gather.p, (size_t)slot_bytes, ncclUint8, (ncclComm_t)h->comm, h->stream));
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -406,11 +406,11 @@ int cns_group_select(cns_group* g, int64_t now, const cns_job_soa* jb, cns_place
   // ---- all-gather of the packed results on the devices: rank d's buffer at [d * slot) of every device's gather buffer -------------------
   size_t slot = 16;
   std::vector<size_t> rbytes(n, 0);   // (an idle device contributes an empty slot)
-  for (u32 d : g->active) { rbytes[d] = g->eng[d]->ro.total; slot = std::max(slot, align16(rbytes[d])); }
+  for (u32 d : g->active) { rbytes[d] = g->eng[d]->q.ro.total; slot = std::max(slot, align16(rbytes[d])); }
   for (u32 d = 0; d < n; ++d) {
     cns_engine* h = g->eng[d];
     if (hipSetDevice(h->device) != hipSuccess || g->d_gather[d].ensure(slot * n) != hipSuccess) return gfail(g, CNS_ERR_HIP, "cns_group_select: gather buffer allocation failed");
-    if (rbytes[d] && hipMemcpyAsync(g->d_gather[d].as<char>() + slot * d, h->d_results.p, rbytes[d], hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
+    if (rbytes[d] && hipMemcpyAsync(g->d_gather[d].as<char>() + slot * d, h->q.results.p, rbytes[d], hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
       return gfail(g, CNS_ERR_HIP, "cns_group_select: staging copy failed");
   }
   if (g->distinct) {
@@ -424,7 +424,7 @@ int cns_group_select(cns_group* g, int64_t now, const cns_job_soa* jb, cns_place
     for (u32 dst = 0; dst < n; ++dst)
       for (u32 src = 0; src < n; ++src) {
         if (src == dst || !rbytes[src]) continue;
-        if (hipMemcpyPeerAsync(g->d_gather[dst].as<char>() + slot * src, g->eng[dst]->device, g->eng[src]->d_results.p, g->eng[src]->device,
+        if (hipMemcpyPeerAsync(g->d_gather[dst].as<char>() + slot * src, g->eng[dst]->device, g->eng[src]->q.results.p, g->eng[src]->device,
                                rbytes[src], g->eng[dst]->stream) != hipSuccess)
           return gfail(g, CNS_ERR_HIP, "cns_group_select: device-to-device copy failed");
       }
@@ -454,12 +454,12 @@ int cns_group_select(cns_group* g, int64_t now, const cns_job_soa* jb, cns_place
     const cns_engine* h = g->eng[d];
     const cns_group::Shard& s = g->shard[d];
     const char* rb = (const char*)g->h_gather + slot * d;
-    const i64* st = (const i64*)(rb + h->ro.start);
-    const uint8_t* rs = (const uint8_t*)(rb + h->ro.reason);
-    const i64* cpu = (const i64*)(rb + h->ro.cpu);
-    const u64 *mem = (const u64*)(rb + h->ro.mem), *lo = (const u64*)(rb + h->ro.clo), *hi = (const u64*)(rb + h->ro.chi), *gr = (const u64*)(rb + h->ro.gres);
-    const u64 *w2 = (const u64*)(rb + h->ro.c2), *w3 = (const u64*)(rb + h->ro.c3);
-    const u32 *nd = (const u32*)(rb + h->ro.node), *nt = (const u32*)(rb + h->ro.ntasks);
+    const i64* st = (const i64*)(rb + h->q.ro.start);
+    const uint8_t* rs = (const uint8_t*)(rb + h->q.ro.reason);
+    const i64* cpu = (const i64*)(rb + h->q.ro.cpu);
+    const u64 *mem = (const u64*)(rb + h->q.ro.mem), *lo = (const u64*)(rb + h->q.ro.clo), *hi = (const u64*)(rb + h->q.ro.chi), *gr = (const u64*)(rb + h->q.ro.gres);
+    const u64 *w2 = (const u64*)(rb + h->q.ro.c2), *w3 = (const u64*)(rb + h->q.ro.c3);
+    const u32 *nd = (const u32*)(rb + h->q.ro.node), *nt = (const u32*)(rb + h->q.ro.ntasks);
     u64 src = 0;
     for (size_t x = 0; x < s.idx.size(); ++x) {
       const u64 j = s.idx[x];

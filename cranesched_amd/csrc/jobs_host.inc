@@ -193,4 +193,24 @@ inline void pass2(const cns_job_soa* jb, Out& o, std::vector<Chunk>& chunks) {
   o.place_off[jb->num_jobs] = o.places;
 }
 
+// The packed result buffer of a job table (one contiguous HBM buffer: what cns_results_layout reports and an all-gather ships): the
+// byte offset of every section, each a multiple of 16 and at least one element long.  The ORDER carries the reset in front of a pass:
+// start and the five 8-byte record arrays lie in one run (one memset over [start, node) zeroes them), node (0xFF) and ntasks follow,
+// and the planes of core ids 128..255 come last, c2 then c3 (one memset over [c2, total)).  They exist only for a snapshot with such
+// nodes: c2 == c3 == total otherwise, nothing more to ship.
+struct ResOff { size_t start, cpu, mem, clo, chi, gres, node, ntasks, reason, c2, c3, total; };
+inline size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
+inline ResOff result_layout(uint64_t J, uint64_t places, bool wide_cores) {
+  size_t end = 0;
+  auto sec = [&](size_t elem, uint64_t n) { const size_t at = end; end = align16(end + elem * (size_t)(n ? n : 1)); return at; };
+  ResOff r{};
+  r.start = sec(8, J); r.cpu = sec(8, places); r.mem = sec(8, places); r.clo = sec(8, places);
+  r.chi = sec(8, places); r.gres = sec(8, places); r.node = sec(4, places); r.ntasks = sec(4, places);
+  r.reason = sec(1, J);
+  r.c2 = r.c3 = end;
+  if (wide_cores) { r.c2 = sec(8, places); r.c3 = sec(8, places); }
+  r.total = end;
+  return r;
+}
+
 }  // namespace cns_jobs_host

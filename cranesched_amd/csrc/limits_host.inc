@@ -170,7 +170,7 @@ int cns_upload_limit_jobs(cns_handle* h, const cns_limit_job_soa* jb) {
     if (jb->user[i] >= h->lim_U || jb->user_acct[i] >= h->lim_UA || jb->account[i] >= h->lim_A || jb->qos[i] >= h->lim_Q ||
         jb->partition[i] >= h->lim_Pn)
       return fail(h, CNS_ERR_INVALID_ARG, "limit job " + std::to_string(i) + ": user / user_acct / account / qos / partition out of range");
-    if ((jb->select_index ? jb->select_index[i] : i) >= h->J)
+    if ((jb->select_index ? jb->select_index[i] : i) >= h->q.J)
       return fail(h, CNS_ERR_INVALID_ARG, "limit job " + std::to_string(i) + ": select_index outside the last cns_select");
   }
   HIPCHK(h, hipSetDevice(h->device));
@@ -185,7 +185,7 @@ int cns_upload_limit_jobs(cns_handle* h, const cns_limit_job_soa* jb) {
   if (int rc = stage(h, b[15], jb->partition, J * 4)) return rc;
   if (int rc = stage(h, b[16], jb->time_limit_sec, J * 8)) return rc;
   if (jb->skip) { if (int rc = stage(h, b[17], jb->skip, J)) return rc; }
-  if (int rc = stage(h, b[18], h->place_off, h->place_off ? (size_t)(h->J + 1) * 8 : 0)) return rc;
+  if (int rc = stage(h, b[18], h->q.h_place.p, h->q.h_place.p ? (size_t)(h->q.J + 1) * 8 : 0)) return rc;
   h->lim_has_sel = jb->select_index != nullptr;
   h->lim_has_skip = jb->skip != nullptr;
   const u64 nb = (J + 255) / 256, Jc = std::max<u64>(J, 1);
@@ -206,7 +206,7 @@ int cns_upload_limit_jobs(cns_handle* h, const cns_limit_job_soa* jb) {
   h->lim_timing = cns_limit_timing{};
   h->lim_timing.h2d_ms = ms;
   h->lim_J = J;
-  h->lim_sel_J = h->J;
+  h->lim_sel_J = h->q.J;
   h->lim_have_jobs = true;
   return CNS_OK;
 }
@@ -214,7 +214,7 @@ int cns_upload_limit_jobs(cns_handle* h, const cns_limit_job_soa* jb) {
 int cns_run_limits_resident(cns_handle* h) {
   if (!h) return fail(h, CNS_ERR_INVALID_ARG, "cns_run_limits_resident: null handle");
   if (!h->lim_have_jobs) return fail(h, CNS_ERR_STATE, "cns_run_limits_resident before cns_upload_limit_jobs");
-  if (!h->have_run || h->lim_sel_J != h->J) return fail(h, CNS_ERR_STATE, "cns_run_limits_resident without the matching cns_select results");
+  if (!h->have_run || h->lim_sel_J != h->q.J) return fail(h, CNS_ERR_STATE, "cns_run_limits_resident without the matching cns_select results");
   HIPCHK(h, hipSetDevice(h->device));
   h->lim_have_run = false;
   DevBuf* b = h->d_lim;
@@ -230,9 +230,9 @@ int cns_run_limits_resident(cns_handle* h) {
   P.acct_part_limit = h->lim_has_apl ? b[5].as<u32>() : nullptr;
   P.lim = b[0].as<LimRec>();
   P.usage = b[8].as<i64>(); P.exists = b[9].as<uint8_t>();
-  const char* rb = h->d_results.as<char>();
-  P.o_reason = (const uint8_t*)(rb + h->ro.reason); P.place_off = b[18].as<u64>(); P.o_node = (const u32*)(rb + h->ro.node);
-  P.o_cpu = (const i64*)(rb + h->ro.cpu); P.o_mem = (const u64*)(rb + h->ro.mem); P.o_gres = (const u64*)(rb + h->ro.gres);
+  const char* rb = h->q.results.as<char>();
+  P.o_reason = (const uint8_t*)(rb + h->q.ro.reason); P.place_off = b[18].as<u64>(); P.o_node = (const u32*)(rb + h->q.ro.node);
+  P.o_cpu = (const i64*)(rb + h->q.ro.cpu); P.o_mem = (const u64*)(rb + h->q.ro.mem); P.o_gres = (const u64*)(rb + h->q.ro.gres);
   P.blk_cnt = b[19].as<u32>(); P.blk_off = b[20].as<u64>(); P.total = b[21].as<u64>(); P.admitted = b[21].as<u64>() + 1;
   P.rec_add = b[22].as<i64>(); P.rec_c = b[23].as<u32>(); P.rec_l = b[24].as<u32>(); P.rec_en = b[25].as<u32>();
   P.rec_job = b[26].as<u32>(); P.rec_meta = b[27].as<u32>(); P.out = b[28].as<uint8_t>();

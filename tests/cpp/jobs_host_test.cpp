@@ -2,7 +2,8 @@
 // against the ONE-thread walk it replaced, written out below as it stood in engine.hip up to round 5 — BasicPriority's truncation
 // (JobScheduler.h:185-200), the pre-checks of the ordered loop (JobScheduler.cpp:6744-6761), the split by partition (:6516-6530).
 // Random queues (reservations, refused partitions, unknown partitions, skipped jobs, a batch limit, GRES, node lists, shared groups),
-// every thread count 1..9, and the two error classes with their precedence.   usage: jobs_host_test <cases> [bench]
+// every thread count 1..9, and the two error classes with their precedence.  And the layout of the packed result buffer
+// (result_layout) against the rules its readers rely on and one row derived by hand.   usage: jobs_host_test <cases> [bench | layout]
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -210,10 +211,49 @@ static bool run_parallel(const cns_job_soa* jb, const jh::Route& R, bool shared,
   return true;
 }
 
+// result_layout: what the reset in front of a pass, the download, cns_results_layout and the all-gather rely on.
+static int check_layout() {
+#define LCHECK(cond) do { if (!(cond)) { printf("layout J %llu places %llu wide %d: %s\n", (unsigned long long)J, (unsigned long long)pl, (int)wide, #cond); return 1; } } while (0)
+  for (u64 J : {0ull, 1ull, 3ull, 17ull})
+    for (u64 pl : {0ull, 1ull, 5ull, 33ull})
+      for (bool wide : {false, true}) {
+        const jh::ResOff r = jh::result_layout(J, pl, wide);
+        const u64 J1 = J ? J : 1, pl1 = pl ? pl : 1;
+        // the sections in their order, the bytes each must hold; behind the last one: total
+        const struct { size_t at; u64 bytes; } sec[] = {{r.start, 8 * J1},  {r.cpu, 8 * pl1},  {r.mem, 8 * pl1},    {r.clo, 8 * pl1},
+                                                        {r.chi, 8 * pl1},   {r.gres, 8 * pl1}, {r.node, 4 * pl1},   {r.ntasks, 4 * pl1},
+                                                        {r.reason, J1},     {r.c2, 8 * pl1},   {r.c3, 8 * pl1}};
+        const size_t n = wide ? 11 : 9;
+        LCHECK(r.start == 0 && r.total % 16 == 0);
+        for (size_t i = 0; i < n; ++i) {
+          const size_t next = i + 1 < n ? sec[i + 1].at : r.total;
+          LCHECK(sec[i].at % 16 == 0);
+          LCHECK(sec[i].at < next);                    // the order: start, cpu, mem, clo, chi, gres, node, ntasks, reason[, c2, c3]
+          LCHECK(next - sec[i].at >= sec[i].bytes);    // max(n, 1) elements before the next section begins
+        }
+        if (!wide) LCHECK(r.c2 == r.total && r.c3 == r.total);
+      }
+  {   // by hand, J = 3, places = 5: 24 -> 32 bytes of start, 40 -> 48 per 8-byte array, 20 -> 32 per 4-byte array, 3 -> 16 of reason
+    const u64 J = 3, pl = 5;
+    bool wide = false;
+    const jh::ResOff a = jh::result_layout(J, pl, wide);
+    LCHECK(a.start == 0 && a.cpu == 32 && a.mem == 80 && a.clo == 128 && a.chi == 176 && a.gres == 224 && a.node == 272 && a.ntasks == 304 && a.reason == 336);
+    LCHECK(a.c2 == 352 && a.c3 == 352 && a.total == 352);
+    wide = true;
+    const jh::ResOff b = jh::result_layout(J, pl, wide);
+    LCHECK(b.start == 0 && b.cpu == 32 && b.mem == 80 && b.clo == 128 && b.chi == 176 && b.gres == 224 && b.node == 272 && b.ntasks == 304 && b.reason == 336);
+    LCHECK(b.c2 == 352 && b.c3 == 400 && b.total == 448);
+  }
+#undef LCHECK
+  printf("ok: result layout, 32 shapes and the row derived by hand\n");
+  return 0;
+}
+
 #define CHECK(cond, what) do { if (!(cond)) { printf("case %d threads %u: %s differs\n", cs, t, what); return 1; } } while (0)
 
 int main(int argc, char** argv) {
   const int cases = argc > 1 ? atoi(argv[1]) : 300;
+  if (argc > 2 && !strcmp(argv[2], "layout")) return check_layout();
   if (argc > 2 && !strcmp(argv[2], "bench")) {   // what the pass costs at BASELINE's queue length on this host
     Snap sn; make_snap(sn, false);
     Queue q; make_queue(q, sn, 1000000, 0);

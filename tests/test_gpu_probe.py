@@ -238,6 +238,59 @@ def test_more_probes_than_resident_workgroups(engine_default):
         eng.close()
 
 
+# ---- one handle, two job tables ---------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _crossing_case(wide):
+    """A 96-node cluster (optionally with nodes of 192 / 256 cores), queues of 40 and 3 jobs, probe tables of 5, 300 and 40, and the
+    oracle's answer to every step of test_queue_and_probe_tables_cross_in_size."""
+    c, j40, now, run = helpers.random_case(12, J=40)
+    if wide:
+        c = helpers.widen_cores(c, 12)
+    j3 = pc.take(j40, [11, 4, 23])
+    p300 = helpers.random_case(2008, J=300)[1]
+    p5, p40 = pc.take(p300, np.arange(5)), pc.take(p300, np.arange(120, 160))
+    ref40 = pyoracle.select(c, j40, now, running=run).placements
+    ref3 = pyoracle.select(c, j3, now, running=run).placements
+    exp = {"p5": pc.expected(c, j40, p5, now, running=run), "p300": pc.expected(c, j40, p300, now, running=run),
+           "p40": pc.expected(c, j3, p40, now, running=run)}
+    return c, now, run, j40, j3, {"p5": p5, "p300": p300, "p40": p40}, ref40, ref3, exp
+
+
+@pytest.mark.parametrize("wide", [False, True], ids=["cores_to_128", "cores_to_256"])
+def test_queue_and_probe_tables_cross_in_size(engine_default, wide):
+    """The cycle's queue and the probes are two job tables on one handle, each with its buffers, counts and result layout.  Their sizes
+    cross in both directions here (queue 40 > probes 5 and 0, probes 300 > queue 40, queue 3 < probes 40), so a step that reads the
+    other table, or a capacity left from a larger one, is a wrong answer: every cycle against the oracle's, every probe table against
+    tests/probe_case.expected, the cycle's download unchanged behind the probes, and the same again behind a refused cns_upload_jobs.
+    Once more on a snapshot with core ids above 127: the core_w2 / core_w3 planes and their reset, for both tables."""
+    c, now, run, j40, j3, p, ref40, ref3, exp = _crossing_case(wide)
+    if wide:   # (asserted on the oracle's answers: the planes carry something in the first cycle and in the probes, nothing in the J = 3 cycle behind it)
+        assert ref40.core_w3.any() and not ref3.core_w2.any() and exp["p5"].core_w3.any() and exp["p300"].core_w3.any() and exp["p40"].core_w2.any()
+    eng = engine_default(device=0)
+    try:
+        eng.set_nodes(c)
+        eng.set_running(run)
+        first = eng.node_select(now, j40)
+        assert first.diff(ref40) is None, "J = 40: the cycle differs from the oracle"
+        _assert_probes("Q = 5 behind J = 40", eng.probe(p["p5"]), exp["p5"], p["p5"])
+        none = pc.take(p["p300"], [])
+        assert eng.probe(none).num_jobs == 0
+        eng.probe_upload(none)                  # ... and an empty table through the steps of a full one
+        assert eng.probe_run_resident() == 0.0 and eng.probe_download().num_jobs == 0
+        _assert_probes("Q = 300 behind J = 40", eng.probe(p["p300"]), exp["p300"], p["p300"])
+        assert eng.download().diff(first) is None, "the cycle's results changed under a probe table larger than the queue"
+        assert eng.node_select(now, j3).diff(ref3) is None, "J = 3 behind Q = 300: the cycle differs from the oracle"
+        _assert_probes("Q = 40 behind J = 3", eng.probe(p["p40"]), exp["p40"], p["p40"])
+        bad = dataclasses.replace(j3, node_num=np.zeros(3, np.uint32))
+        with pytest.raises(EngineError) as ei:
+            eng.upload_jobs(bad)
+        assert ei.value.status == -1
+        assert eng.node_select(now, j3).diff(ref3) is None, "J = 3 behind a refused upload: the cycle differs from the oracle"
+        _assert_probes("Q = 40 behind a refused upload", eng.probe(p["p40"]), exp["p40"], p["p40"])
+    finally:
+        eng.close()
+
+
 # ---- state machine ------------------------------------------------------------------------------------------------------------
 def test_probe_state_machine(engine_default):
     c, j, p, now, run, rv, cfg = scenario("random0")
