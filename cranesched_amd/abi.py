@@ -9,6 +9,7 @@ JobScheduler.h:92-170), plus the placement result.  Pure plumbing: no scheduling
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -506,6 +507,8 @@ class PreemptOut:
 # ---- reservation what-ifs (include/crane_gpu_resv/resv_probe.h) ---------------------------------------------------------
 RESVQ_OK, RESVQ_NOT_ENOUGH, RESVQ_IN_THE_PAST = 0, 1, 2
 RESVQ_FREE, RESVQ_RUNNING, RESVQ_RESERVED, RESVQ_NOT_FOUND = 0, 1, 2, 3
+# cns_resvq_shape's arguments, in the header's order
+ResvqShape = namedtuple("ResvqShape", ("pick_block", "pick_grid", "sort_tile", "scan_span"))
 
 
 class CnsResvqSoa(C.Structure):

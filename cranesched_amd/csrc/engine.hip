@@ -47,6 +47,7 @@
 #include "csr_host.inc"        // the CSR rules of the callers' lists: offsets, sorted lists without a repeat (no HIP in there either)
 #include "snapshot_host.inc"   // the layout of a snapshot: groups, refusals, slots, reservations, node types, running entries (no HIP in there either)
 #include "gate_check_host.inc" // the input rules of cns_gate_pending (no HIP in there either)
+#include "resvq_passes.inc"    // the radix passes over the segment numbers of cns_resvq_run's sort (no HIP in there either)
 #include "buf_slots.h"         // the slots of cns_engine's per-feature buffer sets
 
 using namespace cns;

@@ -24,7 +24,7 @@ namespace cns {
 constexpr u32 kGateBlock = 256;
 constexpr u32 kGateChunk = 256;      // jobs of one workgroup: one per lane
 constexpr u32 kGateLaneMax = 8;      // dependency entries one lane walks alone (DESIGN.md 6)
-constexpr u32 kGateScanSpan = 256;   // per-wave counts one step of k_sort_rowscan takes
+constexpr u32 kGateScanSpan = kSortScanSpan;   // per-wave counts one step of k_sort_rowscan takes
 constexpr u32 kGateUnclaimed = 0xFFFFFFFFu;
 
 struct GateParams {

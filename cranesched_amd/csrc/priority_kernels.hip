@@ -203,6 +203,7 @@ __global__ __launch_bounds__(256) void k_prio_calc(const PrioParams P) {
 // index order; inside a chunk the rank among equal digits comes from wave ballots (match-any over the 8
 // digit bits) + a per-wave count table in LDS, so equal keys never change their relative order.
 constexpr u32 kSortTile = 4096;
+constexpr u32 kSortScanSpan = 256;   // tiles one step of k_sort_rowscan takes (its 256 threads, one tile each); more tiles: a carry between the steps
 
 __global__ __launch_bounds__(256) void k_sort_hist(const u64* __restrict__ keys, u32 n, u32 shift, u32* __restrict__ hist,
                                                    u32 ntiles) {
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(256) void k_sort_rowscan(u32* __restrict__ hist, u3
   u32* row = hist + (size_t)blockIdx.x * ntiles;
   const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   u32 carry = 0;
-  for (u32 c = 0; c < ntiles; c += 256) {
+  for (u32 c = 0; c < ntiles; c += kSortScanSpan) {
     const u32 i = c + threadIdx.x;
     const u32 v = i < ntiles ? row[i] : 0u;
     u32 inc = v;

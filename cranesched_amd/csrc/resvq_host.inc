@@ -199,9 +199,7 @@ static int resvq_run_impl(cns_handle* h, i64 now, const cns_resvq_soa* q, cns_re
     HIPCHK(h, hipGetLastError());
     hipLaunchKernelGGL(k_rq_by_segment, grid(EV2), blk, 0, h->stream, (const u32*)va, kb, vb, EV2);
     HIPCHK(h, hipGetLastError());
-    u32 seg_passes = 1;
-    while (seg_passes < 4 && ((u64)2 * Q - 1) >> (8 * seg_passes)) ++seg_passes;
-    passes(kb, vb, kc, va, seg_passes);                // (key, value) = (segment, position in time order); afterwards in (kb, vb)
+    passes(kb, vb, kc, va, cns_resvq::seg_passes(Q));  // (key, value) = (segment, position in time order); afterwards in (kb, vb)
     HIPCHK(h, hipGetLastError());
     hipLaunchKernelGGL(k_rq_gather, grid(EV2), blk, 0, h->stream, (const u64*)ka, (const u32*)vb, B[RQ_SORTED].as<i64>(), EV2);
     HIPCHK(h, hipGetLastError());
@@ -247,4 +245,12 @@ int cns_resvq_run(cns_handle* h, int64_t now_sec, const cns_resvq_soa* q, cns_re
   const int rc = resvq_run_impl(h, now_sec, q, out, kernel_ms);
   if (rc != 0) drain(h);
   return rc;
+}
+
+int cns_resvq_shape(uint32_t* pick_block, uint32_t* pick_grid, uint32_t* sort_tile, uint32_t* scan_span) {
+  if (pick_block) *pick_block = kRqBlock;
+  if (pick_grid) *pick_grid = kRqPickGrid;
+  if (sort_tile) *sort_tile = kSortTile;
+  if (scan_span) *scan_span = kSortScanSpan;
+  return CNS_OK;
 }

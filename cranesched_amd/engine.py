@@ -44,7 +44,7 @@ PREEMPT_ABI_SYMBOLS = ("cns_select_preempt",)
 # ... and include/crane_gpu_probe/probe.h
 PROBE_ABI_SYMBOLS = ("cns_probe", "cns_probe_upload", "cns_probe_run_resident", "cns_probe_download")
 # ... and include/crane_gpu_resv/resv_probe.h
-RESVQ_ABI_SYMBOLS = ("cns_resvq_set_state", "cns_resvq_run")
+RESVQ_ABI_SYMBOLS = ("cns_resvq_set_state", "cns_resvq_run", "cns_resvq_shape")
 # ... and include/crane_gpu_valid/validity.h
 VALID_ABI_SYMBOLS = ("cns_validate_jobs", "cns_validate_shape")
 # ... and include/crane_gpu_commit/commit_check.h
@@ -93,6 +93,15 @@ def lib():
         L.cns_group_device_of_partition.argtypes = [C.c_void_p, C.c_uint32]
         _LIB = L
     return _LIB
+
+
+def resvq_shape() -> "abi.ResvqShape":
+    """cns_resvq_shape: the constants the reservation what-ifs' kernels are compiled with.  Needs no handle and no GPU."""
+    v = [C.c_uint32(0) for _ in abi.ResvqShape._fields]
+    status = lib().cns_resvq_shape(*[C.byref(x) for x in v])
+    if status != 0:
+        raise EngineError(status, "cns_resvq_shape")
+    return abi.ResvqShape(*[x.value for x in v])
 
 
 class GpuNodeSelector:
@@ -395,6 +404,10 @@ class GpuNodeSelector:
         self._check(self._L.cns_resvq_run(self._h, C.c_int64(now), C.byref(cq), C.byref(co), C.byref(ms)))
         self._resvq_ms = ms.value
         return out.trimmed()
+
+    def resvq_shape(self) -> "abi.ResvqShape":
+        """(pick_block, pick_grid, sort_tile, scan_span) of the reservation what-ifs' kernels: where their paths change."""
+        return resvq_shape()
 
     def resv_query_timing(self) -> dict:
         """HIP-event time of the kernels of the last query_reservations of this object."""

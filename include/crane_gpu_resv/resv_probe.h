@@ -83,6 +83,12 @@ typedef struct cns_resvq_out {
 int cns_resvq_set_state(cns_handle* h, const cns_running_soa* running, const cns_resv_soa* resv);
 /* num_queries == 0 is CNS_OK and writes nothing.  kernel_ms (may be NULL): HIP-event time of the call's kernels. */
 int cns_resvq_run(cns_handle* h, int64_t now_sec, const cns_resvq_soa* q, cns_resvq_out* out, double* kernel_ms);
+/* The constants at which the device code changes path, for tests that put a case on each; no handle, any pointer may be NULL.
+ * pick_block: candidates one step of the pick kernel takes (a list longer than that carries a count between its steps);
+ * pick_grid: workgroups of the pick kernel (more queries than that: a workgroup takes several); sort_tile: event times per tile of
+ * the sort; scan_span: tiles one step of the sort's scan takes (more than scan_span * sort_tile event times: a carry between the
+ * steps).  Always CNS_OK. */
+int cns_resvq_shape(uint32_t* pick_block, uint32_t* pick_grid, uint32_t* sort_tile, uint32_t* scan_span);
 
 #ifdef __cplusplus
 }

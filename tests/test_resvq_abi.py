@@ -15,9 +15,37 @@ def _source():
 def test_header_symbols_exported(built):
     from cranesched_amd import engine
     names = sorted(set(re.findall(r"\b(cns_[a-z_0-9]+)\s*\(", _source())))
-    assert names == sorted(engine.RESVQ_ABI_SYMBOLS) == ["cns_resvq_run", "cns_resvq_set_state"]
+    assert names == sorted(engine.RESVQ_ABI_SYMBOLS) == ["cns_resvq_run", "cns_resvq_set_state", "cns_resvq_shape"]
     for n in names:
         assert hasattr(engine.lib(), n), f"{n} declared in resv_probe.h but not exported"
+
+
+def test_shape_signature_follows_the_header():
+    from cranesched_amd import abi
+    m = re.search(r"\bint cns_resvq_shape\(([^)]*)\);", _source())
+    assert m, "cns_resvq_shape is not declared as returning int"
+    params = [p.strip() for p in m.group(1).split(",")]
+    assert all(p.startswith("uint32_t* ") for p in params), params
+    assert tuple(p.split()[-1] for p in params) == abi.ResvqShape._fields == ("pick_block", "pick_grid", "sort_tile", "scan_span")
+
+
+def test_shape_without_a_handle(built):
+    """No handle, no GPU; null pointers are allowed one by one and all at once; the values are those of the gate's and the sorter's
+    own constants and are what the kernels' layout needs (whole waves, a power-of-two tile of whole blocks)."""
+    from cranesched_amd import engine
+    L = engine.lib()
+    v = [C.c_uint32(0) for _ in range(4)]
+    assert L.cns_resvq_shape(*[C.byref(x) for x in v]) == 0
+    shape = engine.resvq_shape()
+    assert tuple(x.value for x in v) == tuple(shape) == (256, 256, 4096, 256)
+    assert L.cns_resvq_shape(None, None, None, None) == 0
+    for skip in range(4):
+        w = [C.c_uint32(77) for _ in range(4)]
+        assert L.cns_resvq_shape(*[None if i == skip else C.byref(x) for i, x in enumerate(w)]) == 0
+        assert [x.value for x in w] == [77 if i == skip else shape[i] for i in range(4)]
+    assert shape.pick_block % 64 == 0 and shape.pick_grid >= 1 and shape.sort_tile % shape.pick_block == 0 and shape.scan_span >= 64
+    a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    assert L.cns_gate_shape(C.byref(a), C.byref(b), C.byref(c)) == 0 and c.value == shape.scan_span   # one scan kernel serves both
 
 
 def test_struct_mirrors_follow_the_header():
