@@ -779,6 +779,50 @@ class CnsSubmitTiming(C.Structure):
                 ("candidates", C.c_uint64), ("admitted", C.c_uint64), ("rounds", C.c_uint32), ("ordered_fallback", C.c_uint32)]
 
 
+# ---- releases and charges on the usage tables (include/crane_gpu_usage/usage.h) -------------------------------------------
+USAGE_RELEASE, USAGE_CHARGE = 0, 1
+USAGE_CARRY = 1
+USAGE_MAX_JOBS = 1 << 24
+USAGE_BIT_USER_QOS, USAGE_BIT_USER_PART, USAGE_BIT_QOS = 0, 1, 14
+USAGE_SLOTS = 15          # records one row touches at the most = bits of a mask
+
+
+def usage_bit_acct_qos(i):
+    return 2 + 2 * i
+
+
+def usage_bit_acct_part(i):
+    return 3 + 2 * i
+
+
+class CnsUsageTables(C.Structure):
+    _fields_ = [("num_users", C.c_uint32), ("num_user_accts", C.c_uint32), ("num_accounts", C.c_uint32), ("num_qos", C.c_uint32),
+                ("num_partitions", C.c_uint32), ("reserved0", C.c_uint32), ("gres", CnsGresLayout), ("acct_parent", _P),
+                ("user_qos", _P), ("user_part", _P), ("acct_qos", _P), ("acct_part", _P), ("qos_usage", _P),
+                ("user_qos_submit", _P), ("user_part_submit", _P), ("acct_qos_submit", _P), ("acct_part_submit", _P), ("qos_submit", _P),
+                ("user_qos_exists", _P), ("user_part_exists", _P), ("acct_qos_exists", _P), ("acct_part_exists", _P),
+                ("user_exists", _P), ("acct_exists", _P), ("qos_exists", _P)]
+
+
+class CnsUsageJobs(C.Structure):
+    _fields_ = [("num_jobs", C.c_uint64), ("user", _P), ("user_acct", _P), ("account", _P), ("qos", _P), ("partition", _P), ("cpu_raw", _P),
+                ("mem", _P), ("wall_sec", _P), ("jobs_count", _P), ("submit_count", _P), ("name_total", _P), ("class_count", _P), ("skip", _P)]
+
+
+class CnsUsageOut(C.Structure):
+    _fields_ = [("not_found", _P), ("over_free", _P), ("num_clean", _P)]
+
+
+class CnsUsageTablesOut(C.Structure):
+    _fields_ = [(f, _P) for f in ("user_qos", "user_part", "acct_qos", "acct_part", "qos_usage", "user_qos_submit", "user_part_submit",
+                                  "acct_qos_submit", "acct_part_submit", "qos_submit", "user_qos_exists", "user_part_exists",
+                                  "acct_qos_exists", "acct_part_exists", "user_exists", "acct_exists", "qos_exists")]
+
+
+class CnsUsageTiming(C.Structure):
+    _fields_ = [("h2d_ms", C.c_double), ("kernels_ms", C.c_double), ("d2h_ms", C.c_double), ("items", C.c_uint64), ("records", C.c_uint64)]
+
+
 def _csr(lists):
     off = np.zeros(len(lists) + 1, np.uint64)
     off[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64) if len(lists) else []

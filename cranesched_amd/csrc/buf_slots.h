@@ -31,6 +31,12 @@ enum { SB_QOS = 0, SB_PL, SB_PARENT, SB_UPL, SB_APL, SB_UQ, SB_AQ, SB_G, SB_ST_S
        SB_PRE, SB_STATE, SB_STAT, SB_COND, SB_IKEY, SB_ITHR, SB_CODE, SB_TLO, SB_CTR,                                           // per job
        SB_SK0, SB_SK1, SB_SV0, SB_SV1, SB_HIST, SB_SKEY, SB_SITEM, SB_SADD, SB_VAL, SB_TAILS, SB_HEADS, SB_CARRY, SB_COUNT };   // the parallel pass
 
+// cns_engine::d_use (usage_host.inc)
+enum { US_PARENT = 0, US_TAB_SET, US_TAB_CUR, US_TAB_WORK,                                                                        // tables
+       US_JUSER, US_JUA, US_JACCT, US_JQOS, US_JPART, US_JCPU, US_JMEM, US_JWALL, US_JJOBS, US_JSUB, US_JNT, US_JCC, US_JSKIP,     // rows
+       US_DELTA, US_MASK, US_CTR, US_SK0, US_SK1, US_SV0, US_SV1, US_HIST, US_SKEY, US_SITEM,                                     // items
+       US_TAILS, US_TFLAGS, US_CARRY, US_CFLAGS, US_COUNT };                                                                      // the scan
+
 // cns_engine::d_gate (gate_host.inc)
 enum { GT_JOBID = 0, GT_HELD, GT_BEGIN, GT_ISOR, GT_READY, GT_DEPOFF, GT_DEPJOB, GT_DELAY, GT_AP, GT_APFLAGS, GT_APDEAD, GT_APRUN, GT_APLIM,   // jobs
        GT_EVDEPENDENT, GT_EVDEPENDEE, GT_EVSEC, GT_FIRST,                                                                                     // events

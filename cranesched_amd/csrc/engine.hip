@@ -27,6 +27,7 @@
 #include "../../include/crane_gpu_commit/commit_check.h"
 #include "../../include/crane_gpu_submit/submit_limits.h"
 #include "../../include/crane_gpu_gate/pending_gate.h"
+#include "../../include/crane_gpu_usage/usage.h"
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
 #include <limits>
@@ -41,12 +42,14 @@
 #include "valid_kernels.inc"  // can each job of a batch ever run in its partition (include/crane_gpu_valid/validity.h)
 #include "commit_kernels.inc" // the commit loop's resource-changed and preempted-alive checks (include/crane_gpu_commit/commit_check.h)
 #include "submit_kernels.inc" // the submit limits over a batch of submissions (include/crane_gpu_submit/submit_limits.h)
+#include "usage_kernels.inc"  // releases and charges of a batch of jobs on the usage tables (include/crane_gpu_usage/usage.h)
 #include "gate_kernels.inc"   // the dependency-event drain and Phase 1 in front of a cycle (include/crane_gpu_gate/pending_gate.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 #include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
 #include "csr_host.inc"        // the CSR rules of the callers' lists: offsets, sorted lists without a repeat (no HIP in there either)
 #include "snapshot_host.inc"   // the layout of a snapshot: groups, refusals, slots, reservations, node types, running entries (no HIP in there either)
 #include "gate_check_host.inc" // the input rules of cns_gate_pending (no HIP in there either)
+#include "usage_check_host.inc" // the input rules of cns_usage_set_tables / cns_usage_apply (no HIP in there either)
 #include "resvq_passes.inc"    // the radix passes over the segment numbers of cns_resvq_run's sort (no HIP in there either)
 #include "buf_slots.h"         // the slots of cns_engine's per-feature buffer sets
 
@@ -221,6 +224,12 @@ struct cns_engine {
   u32 sub_max_set = 0, sub_max_cur = 0;         // the largest submit count of the tables as set / as the last call left them
   cns_gres_layout sub_lay{};
   cns_submit_timing sub_timing{};
+  // releases and charges on the usage tables (usage_host.inc): three copies of the table, the call's rows, items and masks
+  DevBuf d_use[US_COUNT];
+  bool use_have = false, use_have_cur = false;  // tables set / a cns_usage_apply succeeded since
+  cns_usage_host::Dims use_dims{};
+  u32 use_base[5] = {0, 0, 0, 0, 0}, use_ent[3] = {0, 0, 0};
+  cns_usage_timing use_timing{};
 };
 
 namespace {
@@ -1245,6 +1254,7 @@ int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity
 #include "valid_host.inc"
 #include "commit_host.inc"
 #include "submit_host.inc"
+#include "usage_host.inc"
 #include "gate_host.inc"
 
 }  // extern "C"

@@ -51,6 +51,8 @@ VALID_ABI_SYMBOLS = ("cns_validate_jobs", "cns_validate_shape")
 COMMIT_ABI_SYMBOLS = ("cns_commit_check", "cns_commit_shape")
 # ... and include/crane_gpu_submit/submit_limits.h
 SUBMIT_ABI_SYMBOLS = ("cns_set_submit_limits", "cns_check_submissions", "cns_get_submit_usage", "cns_get_submit_timing", "cns_submit_shape")
+# ... and include/crane_gpu_usage/usage.h
+USAGE_ABI_SYMBOLS = ("cns_usage_set_tables", "cns_usage_apply", "cns_usage_get_tables", "cns_usage_get_timing", "cns_usage_shape")
 # ... and include/crane_gpu_gate/pending_gate.h
 GATE_ABI_SYMBOLS = ("cns_gate_pending", "cns_gate_shape")
 LIMITS_ABI_SYMBOLS = ("cns_set_run_limits", "cns_apply_run_limits", "cns_upload_limit_jobs", "cns_run_limits_resident",
@@ -529,6 +531,49 @@ class GpuNodeSelector:
         """(job_chunk, item_chunk, max_rounds): where the submit kernels' paths change."""
         a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         self._check(self._L.cns_submit_shape(C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    # -- releases and charges on the usage tables (include/crane_gpu_usage/usage.h) ----------------------------------------------
+    def set_usage_tables(self, tables):
+        """The full MetaResource tables (usage.UsageTables): usage, submit counts, nested exists bytes, entity bits.  Needs no node snapshot."""
+        t = tables.to_c()
+        self._check(self._L.cns_usage_set_tables(self._h, C.byref(t)))
+        self._use_tables = tables
+
+    def _usage_apply(self, op, jobs, carry):
+        j = jobs.num_jobs
+        nf, of, clean = np.zeros(max(j, 1), np.uint16), np.zeros(max(j, 1), np.uint16), np.zeros(1, np.uint64)
+        cj = jobs.to_c()
+        co = abi.CnsUsageOut(abi._ptr(nf), abi._ptr(of), abi._ptr(clean))
+        self._check(self._L.cns_usage_apply(self._h, C.c_uint32(op), C.byref(cj), C.c_uint32(abi.USAGE_CARRY if carry else 0), C.byref(co)))
+        return nf[:j], of[:j], int(clean[0])
+
+    def release_usage(self, jobs, carry: bool = False):
+        """DoFreeResource_ (AccountMetaContainer.cpp:1126-1208) for every row of usage.UsageJobs in the order given.
+        -> (not_found, over_free, num_clean): per row the records whose key was gone (:1143, :1172) / that were freed beyond what they
+        held (:1152, :1196), bit layout abi.USAGE_BIT_*.  carry: start from what the previous release / charge left."""
+        return self._usage_apply(abi.USAGE_RELEASE, jobs, carry)
+
+    def charge_usage(self, jobs, carry: bool = False):
+        """DoMallocResource_ (:1067-1124) for every row.  -> (not_found, over_free, num_clean): both masks zero."""
+        return self._usage_apply(abi.USAGE_CHARGE, jobs, carry)
+
+    def usage_tables(self):
+        """usage.UsageState after the last release / charge (after set_usage_tables: as set, records that do not exist zeroed)."""
+        s = self._use_tables.state()
+        o = abi.CnsUsageTablesOut(*s.pointers())
+        self._check(self._L.cns_usage_get_tables(self._h, C.byref(o)))
+        return s
+
+    def usage_timing(self) -> dict:
+        t = abi.CnsUsageTiming()
+        self._check(self._L.cns_usage_get_timing(self._h, C.byref(t)))
+        return {f: getattr(t, f) for f, _ in abi.CnsUsageTiming._fields_}
+
+    def usage_shape(self):
+        """(job_chunk, item_chunk, carry_lanes): where the usage kernels' paths change."""
+        a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._check(self._L.cns_usage_shape(C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
     def device_results(self):

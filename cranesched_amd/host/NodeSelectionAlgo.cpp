@@ -23,6 +23,7 @@
 #include "../../include/crane_gpu_commit/commit_check.h"
 #include "../../include/crane_gpu_submit/submit_limits.h"
 #include "../../include/crane_gpu_gate/pending_gate.h"
+#include "../../include/crane_gpu_usage/usage.h"
 
 namespace crane {
 
@@ -2149,6 +2150,217 @@ bool GpuNodeSelectionAlgo::CheckSubmitLimits(const std::vector<SubmitRequest>& r
   }
   for (const auto& [qname, qix] : qos_ix)
     if (qs2[qix] != qs[qix] || (qex2[qix] && !qex[qix])) meta.qos_meta[qname].submit_jobs_count = qs2[qix];
+  status_ = 0;
+  error_.clear();
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Releases and charges on the usage records (include/crane_gpu_usage/usage.h)
+// ---------------------------------------------------------------------------------------------------------
+bool GpuNodeSelectionAlgo::ReleaseMetaResources(AccountMetaSnapshot* meta, const std::vector<UsageDelta>& frees, std::vector<UsageReport>* report,
+                                                cns_usage_timing* timing) {
+  return ApplyMetaUsage_(CNS_USAGE_RELEASE, "ReleaseMetaResources", meta, frees, report, timing);
+}
+bool GpuNodeSelectionAlgo::ChargeMetaResources(AccountMetaSnapshot* meta, const std::vector<UsageDelta>& charges, cns_usage_timing* timing) {
+  return ApplyMetaUsage_(CNS_USAGE_CHARGE, "ChargeMetaResources", meta, charges, nullptr, timing);
+}
+
+bool GpuNodeSelectionAlgo::ApplyMetaUsage_(uint32_t op, const char* who, AccountMetaSnapshot* meta_ptr, const std::vector<UsageDelta>& deltas,
+                                           std::vector<UsageReport>* report, cns_usage_timing* timing) {
+  Impl& I = *impl_;
+  if (report) report->clear();
+  auto fail = [&](int st, const std::string& msg) { status_ = st; error_ = msg; return false; };
+  if (!meta_ptr) return fail(CNS_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (I.grp) return fail(CNS_ERR_UNSUPPORTED, std::string(who) + " on an algorithm object over several devices");
+  if (!I.h) return fail(status_ ? status_ : CNS_ERR_NO_DEVICE, error_);
+  if (!I.have_snapshot) return fail(CNS_ERR_STATE, std::string(who) + " before SetClusterSnapshot");
+  AccountMetaSnapshot& meta = *meta_ptr;
+  const size_t J = deltas.size();
+  if (report) report->resize(J);
+  if (J == 0) { status_ = 0; error_.clear(); return true; }
+
+  const AccountIndex ax(I, meta);
+  const auto &qos_ix = ax.qos_ix, &acct_ix = ax.acct_ix, &user_ix = ax.user_ix;
+  const auto& ua_ix = ax.ua_ix;
+  const uint32_t Q = ax.Q, A = ax.A, U = ax.U, UA = ax.UA, Pn = ax.Pn;
+  const std::vector<std::string>& part_name = ax.part_name;
+  std::vector<std::string> acct_name(A);
+  for (const auto& [name, ix] : acct_ix) acct_name[ix] = name;
+
+  // ---- the maps -> the full MetaResource tables: usage, submit count, "the map has an entry", "the entity has a record" ----
+  std::vector<cns_usage> uq((size_t)U * Q), up((size_t)UA * Pn), aq((size_t)A * Q), ap((size_t)A * Pn), qu(Q);
+  std::vector<uint32_t> uqs(uq.size(), 0), ups(up.size(), 0), aqs(aq.size(), 0), aps(ap.size(), 0), qs(Q, 0);
+  std::vector<uint8_t> uqe(uq.size(), 0), upe(up.size(), 0), aqe(aq.size(), 0), ape(ap.size(), 0), uex(U, 0), aex(A, 0), qex(Q, 0);
+  auto put = [&](std::vector<cns_usage>& tab, std::vector<uint32_t>& sub, std::vector<uint8_t>& ex, size_t i, const MetaResource& m) {
+    tab[i] = ax.to_usage(m); sub[i] = m.submit_jobs_count; ex[i] = 1;
+  };
+  for (const auto& [uname, stat] : meta.user_meta) {
+    auto uit = user_ix.find(uname);
+    if (uit == user_ix.end()) continue;
+    uex[uit->second] = 1;
+    for (const auto& [qname, m] : stat.qos_to_resource_map) {
+      auto qit = qos_ix.find(qname);
+      if (qit != qos_ix.end()) put(uq, uqs, uqe, (size_t)uit->second * Q + qit->second, m);
+    }
+    for (const auto& [aname, pm] : stat.account_to_partition_to_resource_map) {
+      auto x = ua_ix.find({uname, aname});
+      if (x == ua_ix.end()) continue;
+      for (const auto& [pname, m] : pm) {
+        auto pit = I.part_idx.find(pname);
+        if (pit != I.part_idx.end()) put(up, ups, upe, (size_t)x->second * Pn + pit->second, m);
+      }
+    }
+  }
+  for (const auto& [aname, stat] : meta.account_meta) {
+    auto ait = acct_ix.find(aname);
+    if (ait == acct_ix.end()) continue;
+    aex[ait->second] = 1;
+    for (const auto& [qname, m] : stat.qos_to_resource_map) {
+      auto qit = qos_ix.find(qname);
+      if (qit != qos_ix.end()) put(aq, aqs, aqe, (size_t)ait->second * Q + qit->second, m);
+    }
+    for (const auto& [pname, m] : stat.partition_to_resource_map) {
+      auto pit = I.part_idx.find(pname);
+      if (pit != I.part_idx.end()) put(ap, aps, ape, (size_t)ait->second * Pn + pit->second, m);
+    }
+  }
+  for (const auto& [qname, m] : meta.qos_meta) {
+    auto qit = qos_ix.find(qname);
+    if (qit != qos_ix.end()) { qu[qit->second] = ax.to_usage(m); qs[qit->second] = m.submit_jobs_count; qex[qit->second] = 1; }
+  }
+  cns_usage_tables t{};
+  t.num_users = U; t.num_user_accts = UA; t.num_accounts = A; t.num_qos = Q; t.num_partitions = Pn;
+  t.gres = I.layout;
+  t.acct_parent = ax.parent.data();
+  t.user_qos = uq.data(); t.user_part = up.data(); t.acct_qos = aq.data(); t.acct_part = ap.data(); t.qos_usage = qu.data();
+  t.user_qos_submit = uqs.data(); t.user_part_submit = ups.data(); t.acct_qos_submit = aqs.data(); t.acct_part_submit = aps.data(); t.qos_submit = qs.data();
+  t.user_qos_exists = uqe.data(); t.user_part_exists = upe.data(); t.acct_qos_exists = aqe.data(); t.acct_part_exists = ape.data();
+  t.user_exists = uex.data(); t.acct_exists = aex.data(); t.qos_exists = qex.data();
+  int st = cns_usage_set_tables(I.h, &t);
+  if (st != 0) return fail(st, cns_last_error(I.h));
+
+  // ---- the deltas: names -> dense ids; zero-count GRES entries are dropped (to_usage keeps only counts) ----
+  std::vector<uint32_t> user(J, 0), ua(J, CNS_LIM_NONE), acct(J, 0), qosv(J, 0), part(J, 0), jc(J, 0), sc(J, 0);
+  std::vector<int64_t> cpu(J, 0), wall(J, 0);
+  std::vector<uint64_t> mem(J, 0), nt(J * CNS_MAX_GRES_NAMES, 0), cc(J * CNS_MAX_GRES_CLASSES, 0);
+  std::vector<uint8_t> skip(J, 0);
+  for (size_t i = 0; i < J; ++i) {
+    const UsageDelta& d = deltas[i];
+    auto uit = user_ix.find(d.username);
+    auto qit = qos_ix.find(d.qos);
+    auto ait = acct_ix.find(d.account);
+    auto pit = I.part_idx.find(d.partition_id);
+    if (uit == user_ix.end() || qit == qos_ix.end() || ait == acct_ix.end() || pit == I.part_idx.end()) {
+      if (op == CNS_USAGE_CHARGE) return fail(CNS_ERR_INVALID_ARG, std::string(who) + ": delta " + std::to_string(i) + " names an unknown user, account, QoS or partition");
+      skip[i] = 1;
+      if (report) (*report)[i].skipped = true;
+      continue;
+    }
+    auto xit = ua_ix.find({d.username, d.account});
+    if (xit == ua_ix.end() && op == CNS_USAGE_CHARGE)
+      return fail(CNS_ERR_INVALID_ARG, std::string(who) + ": delta " + std::to_string(i) + ": the account is not one of the user's");
+    user[i] = uit->second; acct[i] = ait->second; qosv[i] = qit->second; part[i] = pit->second;
+    if (xit != ua_ix.end()) ua[i] = xit->second;
+    MetaResource m;
+    m.resource = d.resource; m.jobs_count = d.jobs_count; m.wall_time = d.time_limit;
+    const cns_usage u = ax.to_usage(m);
+    cpu[i] = u.cpu_raw; mem[i] = u.mem; wall[i] = u.wall_sec; jc[i] = u.jobs_count; sc[i] = d.submit_count;
+    for (uint32_t n = 0; n < CNS_MAX_GRES_NAMES; ++n) nt[i * CNS_MAX_GRES_NAMES + n] = u.name_total[n];
+    for (uint32_t g = 0; g < CNS_MAX_GRES_CLASSES; ++g) cc[i * CNS_MAX_GRES_CLASSES + g] = u.class_count[g];
+  }
+  cns_usage_jobs jb{};
+  jb.num_jobs = J;
+  jb.user = user.data(); jb.user_acct = ua.data(); jb.account = acct.data(); jb.qos = qosv.data(); jb.partition = part.data();
+  jb.cpu_raw = cpu.data(); jb.mem = mem.data(); jb.wall_sec = wall.data(); jb.jobs_count = jc.data(); jb.submit_count = sc.data();
+  jb.name_total = nt.data(); jb.class_count = cc.data(); jb.skip = skip.data();
+  std::vector<uint16_t> nf(J, 0), of(J, 0);
+  cns_usage_out uo{nf.data(), of.data(), nullptr};
+  st = cns_usage_apply(I.h, op, &jb, 0, &uo);
+  if (st != 0) return fail(st, cns_last_error(I.h));
+  if (timing) cns_usage_get_timing(I.h, timing);
+
+  // ---- the reference's messages per record, in its order: user (qos, partition), the chain's accounts (qos, partition), the QoS ----
+  if (report)
+    for (size_t i = 0; i < J; ++i) {
+      UsageReport& r = (*report)[i];
+      r.not_found_bits = nf[i]; r.over_free_bits = of[i];
+      if (!(nf[i] | of[i])) continue;
+      auto say = [&](uint32_t bit, const std::string& what) {
+        if (nf[i] >> bit & 1) r.not_found.push_back(what);
+        if (of[i] >> bit & 1) r.over_free.push_back(what);
+      };
+      say(CNS_USAGE_BIT_USER_QOS, "user " + deltas[i].username);
+      say(CNS_USAGE_BIT_USER_PART, "user " + deltas[i].username);
+      uint32_t a = acct[i];
+      for (uint32_t k = 0; k < CNS_LIM_MAX_CHAIN && a != CNS_LIM_NONE; ++k, a = ax.parent[a]) {
+        say(CNS_USAGE_BIT_ACCT_QOS(k), "account " + acct_name[a]);
+        say(CNS_USAGE_BIT_ACCT_PART(k), "account " + acct_name[a]);
+      }
+      say(CNS_USAGE_BIT_QOS, "qos " + deltas[i].qos);
+    }
+
+  // ---- the tables back into the caller's maps: values, erased entries erased, created records created ----
+  std::vector<uint8_t> uqe2(uqe.size()), upe2(upe.size()), aqe2(aqe.size()), ape2(ape.size()), uex2(U), aex2(A), qex2(Q);
+  cns_usage_tables_out o{};
+  o.user_qos = uq.data(); o.user_part = up.data(); o.acct_qos = aq.data(); o.acct_part = ap.data(); o.qos_usage = qu.data();
+  o.user_qos_submit = uqs.data(); o.user_part_submit = ups.data(); o.acct_qos_submit = aqs.data(); o.acct_part_submit = aps.data(); o.qos_submit = qs.data();
+  o.user_qos_exists = uqe2.data(); o.user_part_exists = upe2.data(); o.acct_qos_exists = aqe2.data(); o.acct_part_exists = ape2.data();
+  o.user_exists = uex2.data(); o.acct_exists = aex2.data(); o.qos_exists = qex2.data();
+  st = cns_usage_get_tables(I.h, &o);
+  if (st != 0) return fail(st, cns_last_error(I.h));
+  auto from_usage = [&](const cns_usage& u, uint32_t submit) {
+    MetaResource m;
+    m.resource.cpu_count = cpu_t::from_raw(u.cpu_raw);
+    m.resource.memory_bytes = u.mem;
+    m.wall_time = u.wall_sec;
+    m.jobs_count = u.jobs_count;
+    m.submit_jobs_count = submit;
+    for (const auto& [name, id] : I.name_id)
+      if (u.name_total[id]) m.resource.gres_map[name].total = u.name_total[id];
+    for (size_t c = 0; c < I.classes.size(); ++c)
+      if (u.class_count[c]) m.resource.gres_map[I.classes[c].first].specified[I.classes[c].second] = u.class_count[c];
+    return m;
+  };
+  // one nested entry: erased where it went, written where it is (a release changes nothing else; a charge creates)
+  auto sync = [&](auto& map, const std::string& key, bool was, bool is, const cns_usage& u, uint32_t submit) {
+    if (is) map[key] = from_usage(u, submit);
+    else if (was) map.erase(key);
+  };
+  for (const auto& [uname, uix] : user_ix) {
+    if (!uex2[uix]) continue;
+    MetaResourceStat& stat = meta.user_meta[uname];
+    for (const auto& [qname, qix] : qos_ix) {
+      const size_t i = (size_t)uix * Q + qix;
+      sync(stat.qos_to_resource_map, qname, uqe[i], uqe2[i], uq[i], uqs[i]);
+    }
+  }
+  for (const auto& [key, x] : ua_ix) {
+    auto uit = meta.user_meta.find(key.first);
+    if (uit == meta.user_meta.end()) continue;
+    for (uint32_t pp = 0; pp < Pn; ++pp) {
+      const size_t i = (size_t)x * Pn + pp;
+      if (upe2[i]) uit->second.account_to_partition_to_resource_map[key.second][part_name[pp]] = from_usage(up[i], ups[i]);
+      else if (upe[i]) {
+        auto ait = uit->second.account_to_partition_to_resource_map.find(key.second);
+        if (ait != uit->second.account_to_partition_to_resource_map.end()) ait->second.erase(part_name[pp]);   // the inner map stays, empty (:1159)
+      }
+    }
+  }
+  for (const auto& [aname, aix] : acct_ix) {
+    if (!aex2[aix]) continue;
+    MetaResourceStat& stat = meta.account_meta[aname];
+    for (const auto& [qname, qix] : qos_ix) {
+      const size_t i = (size_t)aix * Q + qix;
+      sync(stat.qos_to_resource_map, qname, aqe[i], aqe2[i], aq[i], aqs[i]);
+    }
+    for (uint32_t pp = 0; pp < Pn; ++pp) {
+      const size_t i = (size_t)aix * Pn + pp;
+      sync(stat.partition_to_resource_map, part_name[pp], ape[i], ape2[i], ap[i], aps[i]);
+    }
+  }
+  for (const auto& [qname, qix] : qos_ix)
+    if (qex2[qix]) meta.qos_meta[qname] = from_usage(qu[qix], qs[qix]);
   status_ = 0;
   error_.clear();
   return true;

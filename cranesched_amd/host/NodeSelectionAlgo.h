@@ -33,6 +33,7 @@
 struct cns_engine;
 struct cns_group_info;
 struct cns_submit_timing;
+struct cns_usage_timing;
 
 namespace crane {
 
@@ -513,7 +514,7 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   // as ERR_INVALID_USER / ERR_INVALID_ACCOUNT / ERR_INVALID_QOS / ERR_INVALID_PARTITION with the same code and nothing checked.
   // Written: `meta`'s submit_jobs_count of every record an admitted request touched and the records an admission created
   // (DoMallocResource_, :1067-1124); jobs_count, resource and wall_time stay.  An admitted job's time_limit is rewritten as :119 does.
-  // UserAddJob (:3476), qos_priority (:116) and the frees stay with the caller.  false on an engine error (no device, no snapshot, several
+  // UserAddJob (:3476) and qos_priority (:116) stay with the caller; the frees are ReleaseMetaResources.  false on an engine error (no device, no snapshot, several
   // devices: CNS_ERR_UNSUPPORTED, counts that could pass UINT32_MAX, a chain of more than 6 accounts): `out` is empty, nothing is written and
   // Ok() / LastStatus() / LastError() say why; nothing is thrown.
   struct SubmitRequest {
@@ -528,6 +529,76 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   };
   bool CheckSubmitLimits(const std::vector<SubmitRequest>& requests, AccountMetaSnapshot* meta, std::vector<SubmitAnswer>* out,
                          cns_submit_timing* timing = nullptr);
+
+  // ---- releases and charges on the usage records (include/crane_gpu_usage/usage.h) -----------------------------------------------------
+  // AccountMetaContainer::DoFreeResource_ (AccountMetaContainer.cpp:1126-1208) / DoMallocResource_ (:1067-1124) for every delta IN THE
+  // ORDER GIVEN: one delta per Free... / Malloc... call of the reference, built by the maker named after that call.  `meta` is packed to
+  // dense indices as CheckAndMallocMetaResource / CheckSubmitLimits pack it (zero-count GRES entries of a delta are dropped, as everywhere),
+  // the whole batch runs on the device, and the maps of `meta` are written back: user_meta, account_meta and qos_meta hold what the
+  // reference's per-job loop leaves: values subtracted or zeroed, erased nested entries erased, for a charge the created records and
+  // entities.  report[j] (releases) lists per record the reference's two messages: `not_found` (:1143, :1172) and `over_free` (:1152,
+  // :1196), each as "<entity type> <entity name>" with the entity type of the message ("user", "account", "qos").
+  // A delta with an unknown user, account, QoS or partition is not applied (report[j].skipped; a charge of one fails the call: the
+  // reference would create records under names AccountManager does not know).  A (user, account) pair that is not in
+  // meta.user_accounts is the reference's "account not found in the user's account list" (:1172).
+  // UserAddJob / UserReduceJob (:169, :1207) stay with the caller.  false on an engine error (no device: CNS_ERR_NO_DEVICE, several
+  // devices: CNS_ERR_UNSUPPORTED, no snapshot, an all-zero delta, a charge that would pass a 32-bit count): nothing is written and
+  // Ok() / LastStatus() / LastError() say why; nothing is thrown.
+  struct UsageDelta {
+    std::string username, account, qos;
+    PartitionId partition_id;
+    ResourceView resource;
+    uint32_t jobs_count{0}, submit_count{0};
+    int64_t time_limit{0};
+    static UsageDelta Of(const std::string& username, const std::string& account, const std::string& qos, const PartitionId& partition_id) {
+      UsageDelta d;
+      d.username = username; d.account = account; d.qos = qos; d.partition_id = partition_id;
+      return d;
+    }
+    // FreeMetaResource(const JobInCtld&), :243-254: {allocated_res_view, 1, IsArrayChild() ? 0 : 1, time_limit}
+    static UsageDelta FreeMetaResource(const std::string& username, const std::string& account, const std::string& qos, const PartitionId& partition_id,
+                                       const ResourceView& allocated_res_view, int64_t time_limit, bool is_array_child) {
+      UsageDelta d = Of(username, account, qos, partition_id);
+      d.resource = allocated_res_view; d.jobs_count = 1; d.submit_count = is_array_child ? 0u : 1u; d.time_limit = time_limit;
+      return d;
+    }
+    // FreeMetaRunningResource, :256-269 (a requeue): {allocated_res_view, 1, 0, time_limit}
+    static UsageDelta FreeMetaRunningResource(const std::string& username, const std::string& account, const std::string& qos, const PartitionId& partition_id,
+                                              const ResourceView& allocated_res_view, int64_t time_limit) {
+      return FreeMetaResource(username, account, qos, partition_id, allocated_res_view, time_limit, true);
+    }
+    // FreeMetaResource(const PdJobInScheduler&), :271-283: {allocated_res.View(), 1, 0, time_limit}
+    static UsageDelta FreeMetaResource(const PdJobInScheduler& job, const ResourceView& allocated_res_view) {
+      return FreeMetaResource(job.username, job.account, job.qos, job.partition_id, allocated_res_view, job.time_limit, true);
+    }
+    // FreeMetaSubmitResource, :226-241: {0, 0, count, 0}; count == 0 is no call (:228)
+    static UsageDelta FreeMetaSubmitResource(const std::string& username, const std::string& account, const std::string& qos, const PartitionId& partition_id,
+                                             uint32_t count) {
+      UsageDelta d = Of(username, account, qos, partition_id);
+      d.submit_count = count;
+      return d;
+    }
+    // MallocMetaSubmitResource, :139-153: {0, 0, count, 0}
+    static UsageDelta MallocMetaSubmitResource(const std::string& username, const std::string& account, const std::string& qos, const PartitionId& partition_id,
+                                               uint32_t count) {
+      return FreeMetaSubmitResource(username, account, qos, partition_id, count);
+    }
+    // MallocMetaResourceToRecoveredRunningJob, :155-178: {allocated_res_view, 1, IsArrayChild() ? 0 : 1, time_limit}
+    static UsageDelta MallocMetaResourceToRecoveredRunningJob(const std::string& username, const std::string& account, const std::string& qos,
+                                                              const PartitionId& partition_id, const ResourceView& allocated_res_view, int64_t time_limit,
+                                                              bool is_array_child) {
+      return FreeMetaResource(username, account, qos, partition_id, allocated_res_view, time_limit, is_array_child);
+    }
+  };
+  struct UsageReport {
+    bool skipped{false};                    // an unknown name: not applied
+    uint16_t not_found_bits{0}, over_free_bits{0};
+    std::vector<std::string> not_found;     // "<entity type> <entity name>", in the reference's order of records
+    std::vector<std::string> over_free;
+  };
+  bool ReleaseMetaResources(AccountMetaSnapshot* meta, const std::vector<UsageDelta>& frees, std::vector<UsageReport>* report = nullptr,
+                            cns_usage_timing* timing = nullptr);
+  bool ChargeMetaResources(AccountMetaSnapshot* meta, const std::vector<UsageDelta>& charges, cns_usage_timing* timing = nullptr);
 
   // ---- event-fed mirror of the running allocations -------------------------------------------------
   // Instead of re-deriving the running jobs' allocations from the vector NodeSelect is handed every cycle, the adapter
@@ -652,6 +723,8 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   std::unique_ptr<Impl> impl_;
   void SelectPacked_(const TimeSec& now, const std::vector<std::unique_ptr<PdJobInScheduler>>& pending_jobs,
                      const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs);
+  bool ApplyMetaUsage_(uint32_t op, const char* who, AccountMetaSnapshot* meta, const std::vector<UsageDelta>& deltas, std::vector<UsageReport>* report,
+                       cns_usage_timing* timing);
   IPrioritySorter* sorter_{nullptr};
   std::unordered_map<std::string, License> licenses_;
   uint64_t batch_{0};

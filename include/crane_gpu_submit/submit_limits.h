@@ -66,8 +66,8 @@
  * call reads and writes device buffers of its own: a cycle, cns_validate_jobs or cns_apply_run_limits before or after it behaves exactly
  * as without it.  Ownership, errors, threading: as in node_select.h.  There is no CPU fallback.
  *
- * With the caller: the uid / user / account lookups and the partition permission (:3400-3456), UserAddJob, job.qos_priority (:116), and
- * the frees (FreeMetaSubmitResource) when a job leaves the queue.
+ * With the caller: the uid / user / account lookups and the partition permission (:3400-3456), UserAddJob and job.qos_priority (:116).
+ * The frees (FreeMetaSubmitResource) when a job leaves the queue are cns_usage_apply, ../crane_gpu_usage/usage.h.
  */
 #ifndef CRANE_GPU_SUBMIT_LIMITS_H_
 #define CRANE_GPU_SUBMIT_LIMITS_H_
