@@ -823,6 +823,27 @@ class CnsUsageTiming(C.Structure):
     _fields_ = [("h2d_ms", C.c_double), ("kernels_ms", C.c_double), ("d2h_ms", C.c_double), ("items", C.c_uint64), ("records", C.c_uint64)]
 
 
+# ---- the running set kept on the device between two cycles (include/crane_gpu_running/running.h) ----------------------------
+class CnsRunningStep(C.Structure):
+    _fields_ = [("num_retire", C.c_uint64), ("retire_ids", _P), ("num_jobs", C.c_uint64), ("now_sec", C.c_int64), ("job_id", _P),
+                ("admit", _P), ("reservation", _P)]
+
+
+class CnsRunningStepOut(C.Structure):
+    _fields_ = [("found", _P), ("num_retired", _P), ("num_admitted", _P)]
+
+
+class CnsRunningLedger(C.Structure):
+    _fields_ = [("capacity_jobs", C.c_uint64), ("capacity_allocs", C.c_uint64), ("num_jobs", _P), ("num_allocs", _P)] + \
+               [(f, _P) for f in ("job_id", "end_sec", "reservation", "alloc_offsets", "alloc_node", "alloc_cpu_raw", "alloc_mem",
+                                  "alloc_core_lo", "alloc_core_hi", "alloc_core_w2", "alloc_core_w3", "alloc_gres")]
+
+
+class CnsRunningTiming(C.Structure):
+    _fields_ = [("h2d_ms", C.c_double), ("kernels_ms", C.c_double), ("d2h_ms", C.c_double), ("jobs", C.c_uint64), ("allocs", C.c_uint64),
+                ("pairs", C.c_uint64)]
+
+
 def _csr(lists):
     off = np.zeros(len(lists) + 1, np.uint64)
     off[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64) if len(lists) else []

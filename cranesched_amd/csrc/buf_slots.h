@@ -42,6 +42,13 @@ enum { GT_JOBID = 0, GT_HELD, GT_BEGIN, GT_ISOR, GT_READY, GT_DEPOFF, GT_DEPJOB,
        GT_EVDEPENDENT, GT_EVDEPENDEE, GT_EVSEC, GT_FIRST,                                                                                     // events
        GT_CODE, GT_READYOUT, GT_ERASED, GT_WAVES, GT_TOTAL, GT_PENDING, GT_COUNTS, GT_COUNT };                                                // results
 
+// cns_engine::d_rl (running_host.inc)
+enum { RL_ID = 0, RL_END, RL_RESV, RL_OFF, RL_NODE, RL_RES,                                                 // the ledger
+       RL_WID, RL_WEND, RL_WRESV, RL_WOFF, RL_WNODE, RL_WRES,                                               // the call's copy of it
+       RL_RET, RL_FOUND, RL_JID, RL_ADMIT, RL_JRESV,                                                        // the call's lists
+       RL_WROWS0, RL_WENTS0, RL_WROWS1, RL_WENTS1, RL_TOT, RL_NSOFF, RL_NS, RL_WEXP,                        // counts, the node -> slots CSR
+       RL_K0, RL_K1, RL_V0, RL_V1, RL_HIST, RL_RNOFF, RL_RNEND, RL_RNRES, RL_FLAG, RL_COUNT };              // pairs, the per-slot tables
+
 // cns_engine::d_pre (engine.hip: a cycle with preemption)
 enum { B_QPOFF, B_QP, B_PJQOS, B_PJQP, B_PJPRIO, B_PJREC0, B_PJK, B_PJEND, B_RNJOB, B_ENTSLOT, B_ENTGONE, B_RJQOS, B_RJQP,
        B_RJSTART, B_RJEND, B_RJPRE, B_RJOFF, B_RJENT, B_HEAD, B_RECNEXT, B_RECORIG, B_RECSLOT, B_RECGONE, B_MISC, B_COUNT };

@@ -28,6 +28,7 @@
 #include "../../include/crane_gpu_submit/submit_limits.h"
 #include "../../include/crane_gpu_gate/pending_gate.h"
 #include "../../include/crane_gpu_usage/usage.h"
+#include "../../include/crane_gpu_running/running.h"
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
 #include <limits>
@@ -44,12 +45,14 @@
 #include "submit_kernels.inc" // the submit limits over a batch of submissions (include/crane_gpu_submit/submit_limits.h)
 #include "usage_kernels.inc"  // releases and charges of a batch of jobs on the usage tables (include/crane_gpu_usage/usage.h)
 #include "gate_kernels.inc"   // the dependency-event drain and Phase 1 in front of a cycle (include/crane_gpu_gate/pending_gate.h)
+#include "running_kernels.inc" // the running set kept on the device between two cycles: retire, admit, rebuild (include/crane_gpu_running/running.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 #include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
 #include "csr_host.inc"        // the CSR rules of the callers' lists: offsets, sorted lists without a repeat (no HIP in there either)
 #include "snapshot_host.inc"   // the layout of a snapshot: groups, refusals, slots, reservations, node types, running entries (no HIP in there either)
 #include "gate_check_host.inc" // the input rules of cns_gate_pending (no HIP in there either)
 #include "usage_check_host.inc" // the input rules of cns_usage_set_tables / cns_usage_apply (no HIP in there either)
+#include "running_check_host.inc" // the input rules of cns_running_seed / cns_running_advance (no HIP in there either)
 #include "resvq_passes.inc"    // the radix passes over the segment numbers of cns_resvq_run's sort (no HIP in there either)
 #include "buf_slots.h"         // the slots of cns_engine's per-feature buffer sets
 
@@ -230,6 +233,15 @@ struct cns_engine {
   cns_usage_host::Dims use_dims{};
   u32 use_base[5] = {0, 0, 0, 0, 0}, use_ent[3] = {0, 0, 0};
   cns_usage_timing use_timing{};
+  // the running set kept on the device (running_host.inc): two copies of the ledger, the call's lists, counts and pairs, the per-slot
+  // tables of the call (swapped with d_rn_off / d_rn_end / d_rn_res when it succeeded)
+  DevBuf d_rl[RL_COUNT];
+  bool rl_have = false;                         // a ledger is seeded (cns_set_running and a changed num_nodes drop it)
+  bool rl_dev = false;                          // d_rn_* were built from the ledger: h->run holds no entries for them
+  u32 rl_R = 0, rl_A = 0, rl_N = 0;             // its rows and allocations; the num_nodes it was seeded under
+  u64 lay_gen = 0, rl_lay_gen = ~0ull;          // uploads of the snapshot so far; the one RL_NSOFF / RL_NS were derived from
+  u32 rl_fan = 1;                               // slots of the node in most partitions
+  cns_running_timing rl_timing{};
 };
 
 namespace {
@@ -557,6 +569,7 @@ int upload_running(cns_engine* h) {
 int upload_snapshot(cns_engine* h) {
   const cns_snapshot::ResvLayout& X = h->rlay;
   (void)cns_snapshot::build_running(h->lay, X, nullptr, h->run);
+  ++h->lay_gen; h->rl_dev = false;   // (a ledger survives; its per-slot tables come back with the next cns_running_advance)
   if (h->lay.shared) {
     if (int rc = upload(h, h->d_slot_block, X.slot_block)) return rc;
     if (int rc = upload(h, h->d_sib_off, X.sib_off)) return rc;
@@ -704,6 +717,7 @@ int cns_set_running(cns_handle* h, const cns_running_soa* rn) {
   cns_snapshot::RunLayout run;
   if (const cns_snapshot::Status st = cns_snapshot::build_running(h->lay, h->rlay, rn, run)) return fail(h, st.code, st.msg);
   h->run = std::move(run);
+  h->rl_have = h->rl_dev = false;   // (the ledger of cns_running_seed describes another set now)
   if (int rc = upload_running(h)) return rc;
   h->have_run = false;
   return CNS_OK;
@@ -976,6 +990,7 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
   }
   if (!jobs || !out || !pout) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: null argument");
   if (!h->have_nodes) return fail(h, CNS_ERR_STATE, "cns_select_preempt before cns_set_nodes");
+  if (h->rl_dev) return fail(h, CNS_ERR_STATE, "cns_select_preempt: the running tables were built on the device (cns_running_seed / cns_running_advance); hand the running set in with cns_set_running first");
   struct PreCall { cns_engine* h; ~PreCall() { h->pre_call = false; } } pre_call{h};   // (run_resident_once notes it: cns_probe refuses such a state)
   h->pre_call = true;
   const u64 J = jobs->num_jobs;
@@ -1256,6 +1271,7 @@ int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity
 #include "submit_host.inc"
 #include "usage_host.inc"
 #include "gate_host.inc"
+#include "running_host.inc"
 
 }  // extern "C"
 

@@ -55,6 +55,8 @@ SUBMIT_ABI_SYMBOLS = ("cns_set_submit_limits", "cns_check_submissions", "cns_get
 USAGE_ABI_SYMBOLS = ("cns_usage_set_tables", "cns_usage_apply", "cns_usage_get_tables", "cns_usage_get_timing", "cns_usage_shape")
 # ... and include/crane_gpu_gate/pending_gate.h
 GATE_ABI_SYMBOLS = ("cns_gate_pending", "cns_gate_shape")
+# ... and include/crane_gpu_running/running.h
+RUNNING_ABI_SYMBOLS = ("cns_running_seed", "cns_running_advance", "cns_running_get", "cns_running_get_timing", "cns_running_shape")
 LIMITS_ABI_SYMBOLS = ("cns_set_run_limits", "cns_apply_run_limits", "cns_upload_limit_jobs", "cns_run_limits_resident",
                       "cns_download_limits", "cns_get_limit_timing", "cns_get_usage", "cns_limits_shape")
 
@@ -575,6 +577,77 @@ class GpuNodeSelector:
         a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         self._check(self._L.cns_usage_shape(C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    # -- the running set kept on the device between two cycles (include/crane_gpu_running/running.h) -----------------------------
+    def seed_running(self, running: "abi.Running | None", job_ids=None):
+        """The running set into the device ledger, job_ids[R] naming its rows; the per-slot running tables are derived from it on the
+        device and end up exactly as set_running(running) would leave them.  After set_nodes / set_reservations."""
+        if running is None or len(running.end_sec) == 0:
+            self._check(self._L.cns_running_seed(self._h, None, None))
+            return
+        ids = abi._arr(job_ids, np.uint32, len(running.end_sec))
+        r = running.to_c()
+        self._check(self._L.cns_running_seed(self._h, C.byref(r), abi._ptr(ids)))
+
+    def advance_running(self, retire_ids=(), now: "int | None" = None, job_ids=None, admit=None, reservation=None):
+        """One cycle boundary on the device ledger: the rows that carry one of retire_ids are erased (stably), then — when job_ids is
+        given, one id per job of the last node_select's queue — every job with admit[j] != 0 (None: every job) that the cycle started at
+        `now` is appended with its placements, then the per-slot running tables are rebuilt against the current layout.
+        -> (found[K] uint8, num_retired, num_admitted).  Nothing to retire and nothing to admit: the rebuild alone (what follows
+        set_nodes / set_reservations)."""
+        ret = abi._arr(np.asarray(retire_ids, np.uint32).reshape(-1), np.uint32)
+        k = len(ret)
+        found, nret, nadm = np.zeros(max(k, 1), np.uint8), np.zeros(1, np.uint64), np.zeros(1, np.uint64)
+        s = abi.CnsRunningStep()
+        s.num_retire, s.retire_ids = k, abi._ptr(ret) if k else None
+        keep = [ret]
+        if job_ids is not None:
+            ids = abi._arr(job_ids, np.uint32)
+            s.num_jobs, s.now_sec, s.job_id = len(ids), int(now), abi._ptr(ids)
+            keep.append(ids)
+            if admit is not None:
+                adm = abi._arr(admit, np.uint8, len(ids))
+                s.admit = abi._ptr(adm)
+                keep.append(adm)
+            if reservation is not None:
+                rv = abi._arr(reservation, np.uint32, len(ids))
+                s.reservation = abi._ptr(rv)
+                keep.append(rv)
+        o = abi.CnsRunningStepOut(abi._ptr(found), abi._ptr(nret), abi._ptr(nadm))
+        self._check(self._L.cns_running_advance(self._h, C.byref(s), C.byref(o)))
+        return found[:k], int(nret[0]), int(nadm[0])
+
+    def running_ledger(self):
+        """The device ledger -> (abi.Running, job_ids): its rows in ledger order, every plane."""
+        nj, na = np.zeros(1, np.uint64), np.zeros(1, np.uint64)
+        o = abi.CnsRunningLedger()
+        o.num_jobs, o.num_allocs = abi._ptr(nj), abi._ptr(na)
+        self._check(self._L.cns_running_get(self._h, C.byref(o)))
+        r, a = int(nj[0]), int(na[0])
+        ids, end, resv, off = np.zeros(max(r, 1), np.uint32), np.zeros(max(r, 1), np.int64), np.zeros(max(r, 1), np.uint32), np.zeros(r + 1, np.uint32)
+        node, cpu = np.zeros(max(a, 1), np.uint32), np.zeros(max(a, 1), np.int64)
+        u64 = {f: np.zeros(max(a, 1), np.uint64) for f in ("alloc_mem", "alloc_core_lo", "alloc_core_hi", "alloc_core_w2", "alloc_core_w3", "alloc_gres")}
+        o.capacity_jobs, o.capacity_allocs = r, a
+        o.job_id, o.end_sec, o.reservation, o.alloc_offsets = abi._ptr(ids), abi._ptr(end), abi._ptr(resv), abi._ptr(off)
+        o.alloc_node, o.alloc_cpu_raw = abi._ptr(node), abi._ptr(cpu)
+        for f, v in u64.items():
+            setattr(o, f, abi._ptr(v))
+        self._check(self._L.cns_running_get(self._h, C.byref(o)))
+        run = abi.Running(end_sec=end[:r], alloc_offsets=off, alloc_node=node[:a], alloc_cpu_raw=cpu[:a], alloc_mem=u64["alloc_mem"][:a],
+                          alloc_core_lo=u64["alloc_core_lo"][:a], alloc_core_hi=u64["alloc_core_hi"][:a], alloc_gres=u64["alloc_gres"][:a],
+                          reservation=resv[:r], alloc_core_w2=u64["alloc_core_w2"][:a], alloc_core_w3=u64["alloc_core_w3"][:a])
+        return run, ids[:r]
+
+    def running_timing(self) -> dict:
+        t = abi.CnsRunningTiming()
+        self._check(self._L.cns_running_get_timing(self._h, C.byref(t)))
+        return {f: getattr(t, f) for f, _ in abi.CnsRunningTiming._fields_}
+
+    def running_shape(self):
+        """(job_chunk, lane_max_allocs, sort_tile, scan_span): where the running ledger's kernels change path."""
+        v = [C.c_uint32(0) for _ in range(4)]
+        self._check(self._L.cns_running_shape(*[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def device_results(self):
         p, n = C.c_void_p(), C.c_uint64()

@@ -24,6 +24,7 @@
 #include "../../include/crane_gpu_submit/submit_limits.h"
 #include "../../include/crane_gpu_gate/pending_gate.h"
 #include "../../include/crane_gpu_usage/usage.h"
+#include "../../include/crane_gpu_running/running.h"
 
 namespace crane {
 
@@ -85,6 +86,10 @@ struct GpuNodeSelectionAlgo::Impl {
   std::vector<std::vector<SlotId>> class_bit_slot;          // per class: bit offset -> slot path
   cns_gres_layout layout{};
   bool have_snapshot = false;
+  // the running set kept on the device (include/crane_gpu_running/running.h): on; the per-slot tables must be rebuilt from the ledger
+  // before the next cycle (a snapshot was pushed since); the `now` of the last cycle
+  bool resident_running = false, resident_stale = false;
+  int64_t last_now = 0;
   bool resvq_stale = true;   // the engine's per-node tables of the reservation what-ifs are older than the packed running set / the snapshot
   std::vector<const PdJobInScheduler*> last_ord;                      // the jobs of the last cns_select, in its order
   std::unordered_map<const PdJobInScheduler*, uint64_t> last_index;  // job -> its index there (built when the run-limit pass asks)
@@ -122,6 +127,7 @@ struct GpuNodeSelectionAlgo::Impl {
     nd.core_w2 = n_w2.data(); nd.core_w3 = n_w3.data();
     nd.unsupported = n_unsup.empty() ? nullptr : n_unsup.data();
     resvq_stale = true;
+    resident_stale = true;
     int st = grp ? cns_group_set_nodes(grp, &nd) : cns_set_nodes(h, &nd);
     if (st != 0) { err = grp ? cns_group_last_error(grp) : cns_last_error(h); return st; }
     if (!v_start.empty()) {
@@ -1119,8 +1125,69 @@ void GpuNodeSelectionAlgo::NodeSelect(const TimeSec& now,
                                       const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs,
                                       const std::vector<std::unique_ptr<PdJobInScheduler>>& pending_jobs) {
   // ---- running jobs (JobScheduler.cpp:6681-6709), packed incrementally -----------------------------------------
-  if (impl_->h && impl_->have_snapshot) impl_->pack_running(running_jobs);
+  if (impl_->h && impl_->have_snapshot && !impl_->resident_running) impl_->pack_running(running_jobs);
   SelectPacked_(now, pending_jobs, running_jobs);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The running set kept on the device between two cycles (include/crane_gpu_running/running.h)
+// ---------------------------------------------------------------------------------------------------------
+void GpuNodeSelectionAlgo::UseResidentRunning(bool on) { impl_->resident_running = on; }
+bool GpuNodeSelectionAlgo::ResidentRunning() const { return impl_->resident_running; }
+
+bool GpuNodeSelectionAlgo::SeedRunning(const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs) {
+  Impl& I = *impl_;
+  auto fail = [&](int st, const std::string& msg) { status_ = st; error_ = msg; return false; };
+  if (I.grp) return fail(CNS_ERR_UNSUPPORTED, "SeedRunning on an algorithm object over several devices");
+  if (!I.h) return fail(status_ ? status_ : CNS_ERR_NO_DEVICE, error_);
+  if (!I.have_snapshot) return fail(CNS_ERR_STATE, "SeedRunning before SetClusterSnapshot");
+  I.pack_running(running_jobs);   // (the packer of a cycle: dense node indices, core and GRES masks, the reservation's index)
+  if (I.run_overflow) return fail(CNS_ERR_UNSUPPORTED, "a running job holds a core id >= 256");
+  std::vector<uint32_t> ids(I.r_src.size() + 1);
+  for (size_t r = 0; r < I.r_src.size(); ++r) ids[r] = I.r_src[r]->job_id;
+  const cns_running_soa rs = I.running_soa();
+  const int st = cns_running_seed(I.h, rs.num_jobs ? &rs : nullptr, ids.data());
+  if (st != 0) return fail(st, cns_last_error(I.h));
+  I.resident_stale = false;
+  status_ = 0; error_.clear();
+  return true;
+}
+
+bool GpuNodeSelectionAlgo::AdvanceRunning(const std::vector<job_id_t>& finished_job_ids, const std::vector<const PdJobInScheduler*>& admitted,
+                                          uint64_t* num_retired, uint64_t* num_admitted) {
+  Impl& I = *impl_;
+  auto fail = [&](int st, const std::string& msg) { status_ = st; error_ = msg; return false; };
+  if (I.grp) return fail(CNS_ERR_UNSUPPORTED, "AdvanceRunning on an algorithm object over several devices");
+  if (!I.h) return fail(status_ ? status_ : CNS_ERR_NO_DEVICE, error_);
+  if (!I.have_snapshot) return fail(CNS_ERR_STATE, "AdvanceRunning before SetClusterSnapshot");
+  std::vector<uint32_t> ret(finished_job_ids.begin(), finished_job_ids.end());
+  std::vector<uint8_t> found(ret.size() + 1, 0);
+  cns_running_step in{};
+  in.num_retire = ret.size(); in.retire_ids = ret.data();
+  std::vector<uint32_t> ids;
+  std::vector<uint8_t> mask;
+  if (!admitted.empty()) {   // the mask over the last cycle's queue, in its order
+    if (I.last.jobs != I.last_ord.size() || I.last_ord.empty()) return fail(CNS_ERR_STATE, "AdvanceRunning: admitted jobs without a NodeSelect that succeeded");
+    const size_t J = I.last_ord.size();
+    std::unordered_set<const PdJobInScheduler*> want(admitted.begin(), admitted.end());
+    ids.resize(J); mask.assign(J, 0);
+    size_t hit = 0;
+    for (size_t j = 0; j < J; ++j) {
+      ids[j] = I.last_ord[j]->job_id;
+      if (want.count(I.last_ord[j])) { mask[j] = 1; ++hit; }
+    }
+    if (hit != want.size()) return fail(CNS_ERR_INVALID_ARG, "AdvanceRunning: an admitted job is no job of the last NodeSelect");
+    in.num_jobs = J; in.now_sec = I.last_now; in.job_id = ids.data(); in.admit = mask.data(); in.reservation = I.packed.jresv.data();
+  }
+  uint64_t nret = 0, nadm = 0;
+  const cns_running_step_out out{found.data(), &nret, &nadm};
+  const int st = cns_running_advance(I.h, &in, &out);
+  if (st != 0) return fail(st, cns_last_error(I.h));
+  I.resident_stale = false;
+  if (num_retired) *num_retired = nret;
+  if (num_admitted) *num_admitted = nadm;
+  status_ = 0; error_.clear();
+  return true;
 }
 
 // the cycle proper, on the running allocations already packed in Impl::r_*
@@ -1169,11 +1236,23 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
     if (I.snap_overflow) return fail_all(CNS_ERR_UNSUPPORTED, I.snap_error);   // the refused snapshot's own message, every cycle
     return fail_all(CNS_ERR_STATE, "NodeSelect before SetClusterSnapshot");
   }
-  if (I.packed_from_mirror ? I.mirror_ovf != 0 : I.run_overflow)   // (judged on the records of THIS cycle's running set, cached or fresh)
-    return fail_all(CNS_ERR_UNSUPPORTED, "a running job holds a core id >= 256");
-  const cns_running_soa rs = I.running_soa();
-  int st = I.grp ? cns_group_set_running(I.grp, rs.num_jobs ? &rs : nullptr) : cns_set_running(I.h, rs.num_jobs ? &rs : nullptr);
-  if (st != 0) return fail_all(st, I.grp ? cns_group_last_error(I.grp) : cns_last_error(I.h));
+  int st = 0;
+  if (I.resident_running) {   // the cycle runs on the device ledger: nothing of the running set is handed in
+    if (I.grp) return fail_all(CNS_ERR_UNSUPPORTED, "resident running on an algorithm object over several devices");
+    if (I.preempt_enabled) return fail_all(CNS_ERR_STATE, "preemption needs the running jobs themselves: turn resident running off (UseResidentRunning(false)) for such a snapshot");
+    if (I.resident_stale) {   // a snapshot was pushed since the last boundary: the per-slot tables again, from the ledger
+      const cns_running_step none{};
+      st = cns_running_advance(I.h, &none, nullptr);
+      if (st != 0) return fail_all(st, cns_last_error(I.h));
+      I.resident_stale = false;
+    }
+  } else {
+    if (I.packed_from_mirror ? I.mirror_ovf != 0 : I.run_overflow)   // (judged on the records of THIS cycle's running set, cached or fresh)
+      return fail_all(CNS_ERR_UNSUPPORTED, "a running job holds a core id >= 256");
+    const cns_running_soa rs = I.running_soa();
+    st = I.grp ? cns_group_set_running(I.grp, rs.num_jobs ? &rs : nullptr) : cns_set_running(I.h, rs.num_jobs ? &rs : nullptr);
+    if (st != 0) return fail_all(st, I.grp ? cns_group_last_error(I.grp) : cns_last_error(I.h));
+  }
 
   // ---- pending jobs, in the sorter's order (JobScheduler.cpp:6735) ---------------------------------------
   std::vector<PdJobInScheduler*> ord;
@@ -1255,6 +1334,7 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
     for (uint32_t i = 0; i < po.num_preempting; ++i) I.preempting.insert(po_set[i]);
   }
   I.last_ord.assign(ord.begin(), ord.end());
+  I.last_now = now;
   I.refused.clear();
   for (size_t j = 0; j < J; ++j) if (out.reason[j] == CNS_REASON_ENGINE_REFUSED) I.refused.push_back(ord[j]);
   S.jobs = J;

@@ -600,6 +600,26 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
                             cns_usage_timing* timing = nullptr);
   bool ChargeMetaResources(AccountMetaSnapshot* meta, const std::vector<UsageDelta>& charges, cns_usage_timing* timing = nullptr);
 
+  // ---- the running set kept on the device between two cycles (include/crane_gpu_running/running.h) -------------------------
+  // With resident running ON, NodeSelect(now, running_jobs, pending_jobs) does not hand the running set to the engine and ignores the
+  // CONTENTS of running_jobs (a multifactor sorter still reads them): the cycle runs on the device ledger.  The caller seeds the ledger
+  // once and, behind every cycle, tells it what the commit loop did:
+  //   SeedRunning(running_jobs)                          the whole set, once (and again after a restart); the vector's order is the
+  //                                                      ledger's order (a job whose reservation is unknown is left out, as in a cycle)
+  //   AdvanceRunning(finished_job_ids, admitted)         FreeResourceFromNode for the jobs that ended (CranedMetaContainer.cpp:226-277;
+  //                                                      an unknown id changes nothing, :248-253), MallocResourceFromNode for the
+  //                                                      jobs of the LAST NodeSelect that the commit loop started (JobScheduler.cpp:
+  //                                                      1575-1628): their placements are read on the device.  `admitted` names them
+  //                                                      by pointer, in any order; a job the cycle did not start now never enters.
+  // A new snapshot (SetClusterSnapshot, a craned state flip) keeps the ledger while the node count stays; the next NodeSelect rebuilds
+  // the per-slot tables from it first.  Default: off — NodeSelect hands the running set in as before.  One device only; a cycle with
+  // preemption needs the running jobs themselves and is refused while this is on.
+  void UseResidentRunning(bool on);
+  bool ResidentRunning() const;
+  bool SeedRunning(const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs);
+  bool AdvanceRunning(const std::vector<job_id_t>& finished_job_ids, const std::vector<const PdJobInScheduler*>& admitted,
+                      uint64_t* num_retired = nullptr, uint64_t* num_admitted = nullptr);
+
   // ---- event-fed mirror of the running allocations -------------------------------------------------
   // Instead of re-deriving the running jobs' allocations from the vector NodeSelect is handed every cycle, the adapter
   // can be told what the meta container is told: the same calls, at the same places (JobScheduler.cpp:1590-1612 for the
