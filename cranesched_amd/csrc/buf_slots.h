@@ -5,6 +5,26 @@
 enum { JR_LIMIT = 0, JR_NCPU, JR_NMEM, JR_TCPU, JR_TMEM, JR_K, JR_NTASKS, JR_TMIN, JR_TMAX, JR_EXCL, JR_GTOT, JR_GSPEC, JR_INCL_OFF, JR_EXCL_OFF,
        JR_PLACE_OFF, JR_GROUPED, JR_COUNT };
 
+// cns_engine::d_prio (priority_host.inc)
+enum { PR_SUBMIT = 0, PR_QOS, PR_PART, PR_NODENUM, PR_CPU, PR_MEM, PR_ACCT, PR_CACHED,                                          // jobs: pending
+       PR_RSTART, PR_RQOS, PR_RPART, PR_RNODENUM, PR_RCPU, PR_RMEM, PR_RACCT,                                                   // jobs: running
+       PR_ACCOFF, PR_ACCJOBS, PR_PRESENT, PR_BOUNDS, PR_ACCVAL,                                                                 // tables
+       PR_PRIO, PR_K0, PR_K1, PR_V0, PR_V1, PR_HIST, PR_TERMS, PR_COUNT };                                                      // scratch
+
+// cns_engine::d_lim (limits_host.inc)
+enum { LM_LIM = 0, LM_QFLAGS, LM_PARENT, LM_LEVEL, LM_UPL, LM_APL, LM_USAGE0, LM_EXISTS0, LM_USAGE, LM_EXISTS,                  // tables
+       LM_SEL, LM_USER, LM_UA, LM_ACCT, LM_QOS, LM_PART, LM_TL, LM_SKIP, LM_PLACEOFF,                                           // jobs
+       LM_BLKCNT, LM_BLKOFF, LM_CTR, LM_RECADD, LM_RECC, LM_RECL, LM_RECEN, LM_RECJOB, LM_RECMETA, LM_OUT, LM_COUNT };          // scratch
+
+// cns_engine::d_limpar (limits_host.inc): the parallel pass of the admission
+enum { LP_K0 = 0, LP_K1, LP_V0, LP_V1, LP_HIST,                                                                                 // scratch: the sort
+       LP_SKEY, LP_SK, LP_SL, LP_SEN, LP_SSLOT, LP_SADD,                                                                        // scratch: the sorted items
+       LP_STATE, LP_FLAGS, LP_JOBKEY, LP_TAILS, LP_HEADS, LP_CARRY, LP_COUNT };                                                 // scratch: the rounds
+
+// cns_engine::d_step (steps_call.inc)
+enum { ST_NODEOFF = 0, ST_NODEIDX, ST_AVAIL, ST_STEPOFF, ST_STEPS, ST_INCL, ST_EXCL,                                            // jobs
+       ST_SCHEDULED, ST_ONODE, ST_ONT, ST_OALLOC, ST_TNODE, ST_TALLOC, ST_COUNT };                                              // results
+
 // cns_engine::d_pb (probe_host.inc): what the probes need besides their job table (cns_engine::pt)
 enum { PB_PARAMS = 0, PB_PART, PB_CTR, PB_HEAP, PB_FAULT, PB_COUNT };
 

@@ -35,6 +35,7 @@
 #include "engine_params.h"
 #include <rccl/rccl.h>          // several devices: group_host.inc (the engine library links RCCL)
 #include "select_kernels.hip"  // single translation unit: kernels + their launches (no -fgpu-rdc needed)
+#include "sort_kernels.inc"    // the stable pair sort and the ordered scan of per-wave counts that every later kernel file builds on
 #include "priority_kernels.hip"
 #include "limits_kernels.hip"
 #include "steps_kernels.hip"
@@ -53,6 +54,7 @@
 #include "gate_check_host.inc" // the input rules of cns_gate_pending (no HIP in there either)
 #include "usage_check_host.inc" // the input rules of cns_usage_set_tables / cns_usage_apply (no HIP in there either)
 #include "running_check_host.inc" // the input rules of cns_running_seed / cns_running_advance (no HIP in there either)
+#include "sort_host.inc"       // the arithmetic of the pair sort: passes, tiles, histogram bytes (no HIP in there either)
 #include "resvq_passes.inc"    // the radix passes over the segment numbers of cns_resvq_run's sort (no HIP in there either)
 #include "buf_slots.h"         // the slots of cns_engine's per-feature buffer sets
 
@@ -203,12 +205,12 @@ struct cns_engine {
   bool pass_waits = false;                      // a kernel the last pass launched has workgroups that wait for each other (k_wide, k_giant)
   u32 wide_retries = 0;                         // cycles that were re-run on k_pipe / k_select after a k_wide fault (lifetime of the handle)
   // MultiFactorPriority (priority_host.inc)
-  DevBuf d_prio[27];
+  DevBuf d_prio[PR_COUNT];
   double prio_ms = 0.0;
   u64 prio_bytes = 0;
   // run-limit admission (limits_host.inc)
-  DevBuf d_lim[29], d_limpar[17];
-  DevBuf d_step[13];  // step scheduler (steps_call.inc)
+  DevBuf d_lim[LM_COUNT], d_limpar[LP_COUNT];
+  DevBuf d_step[ST_COUNT];  // step scheduler (steps_call.inc)
   // preemption (include/crane_gpu/preempt.h): what cns_set_running kept of the running set, and the cycle's tables
   std::set<void*> host_bufs;                    // page-locked host buffers handed out by cns_host_alloc
   bool pre_active = false;                      // the next run is a cycle with preemption (general path of k_select only)
@@ -277,6 +279,7 @@ int upload(cns_engine* h, DevBuf& b, const std::vector<T>& v) { return stage(h, 
 using cns_jobs_host::align16;
 
 #include "job_table.inc"   // the steps of a JobTable: check, lists_check, stage, route, layout, pack, reset, bind, download
+#include "sort_call.inc"   // the launches of sort_kernels.inc: sort_pairs, sort_index_pairs, scan_counts
 
 int build_gres(cns_engine* h, const cns_gres_layout& g) {
   GresDev d{};

@@ -72,7 +72,7 @@ static int gate_impl(cns_handle* h, i64 now, const cns_gate_jobs* jb, const cns_
     }
     hipLaunchKernelGGL(k_gate_jobs, dim3(grid), dim3(kGateBlock), 0, h->stream, P);
     HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_sort_rowscan, dim3(1), dim3(256), 0, h->stream, P.wave_count, waves, B[GT_TOTAL].as<u32>());
+    scan_counts(h->stream, P.wave_count, waves, B[GT_TOTAL].as<u32>());
     HIPCHK(h, hipGetLastError());
     hipLaunchKernelGGL(k_gate_scatter, dim3(grid), dim3(kGateBlock), 0, h->stream, (const uint8_t*)P.code, J, (const u32*)P.wave_count, P.pending);
     HIPCHK(h, hipGetLastError());

@@ -11,7 +11,7 @@
 //                   its lane; a longer one is handed to its wave, 64 entries per step, the fold by a wave min / max, the erased count by
 //                   a ballot (k_cc_check's hand-off).  Then the first failing check in the reference's order; code, ready_sec, dep_erased,
 //                   the per-wave count of OK jobs, the counts per code and of claimed entries.
-//   k_sort_rowscan  (priority_kernels.hip, unchanged, one workgroup) the exclusive scan of the per-wave counts, kGateScanSpan per step
+//   k_sort_rowscan  (sort_kernels.inc, one workgroup: scan_counts of sort_call.inc) the exclusive scan of the per-wave counts, kGateScanSpan per step
 //   k_gate_scatter  pending[base of the wave + rank inside the wave] = row: the flag again from code, the rank by mbcnt.  No atomic
 //                   decides a position: the list is in row order whatever the schedule.
 // No workgroup waits for another; the gate's own kernels use no LDS and no barrier; every store is a plain vector store or a returnless

@@ -135,20 +135,20 @@ int cns_set_run_limits(cns_handle* h, const cns_limit_tables* t) {
   h->lim_base[4] = (u32)base;    put(t->qos_usage, nullptr, Q);
   std::vector<u32> parent(t->acct_parent, t->acct_parent + A);
   if (parent.empty()) { parent.push_back(kNone); level.push_back(0); }
-  DevBuf* b = h->d_lim;  // 0 lim, 1 qflags, 2 parent, 3 level, 4 user_part_limit, 5 acct_part_limit, 6 usage0, 7 exists0, 8 usage, 9 exists
-  if (int rc = upload(h, b[0], lim)) return rc;
-  if (int rc = upload(h, b[1], qflags)) return rc;
-  if (int rc = upload(h, b[2], parent)) return rc;
-  if (int rc = upload(h, b[3], level)) return rc;
+  DevBuf* b = h->d_lim;  // (buf_slots.h)
+  if (int rc = upload(h, b[LM_LIM], lim)) return rc;
+  if (int rc = upload(h, b[LM_QFLAGS], qflags)) return rc;
+  if (int rc = upload(h, b[LM_PARENT], parent)) return rc;
+  if (int rc = upload(h, b[LM_LEVEL], level)) return rc;
   h->lim_has_upl = t->user_part_limit != nullptr && UA * Pn > 0;
   h->lim_has_apl = t->acct_part_limit != nullptr && A * Pn > 0;
   std::vector<u32> upl, apl;  // kept alive until the stream is drained below
-  if (h->lim_has_upl) { upl.assign(t->user_part_limit, t->user_part_limit + UA * Pn); if (int rc = upload(h, b[4], upl)) return rc; }
-  if (h->lim_has_apl) { apl.assign(t->acct_part_limit, t->acct_part_limit + A * Pn); if (int rc = upload(h, b[5], apl)) return rc; }
-  if (int rc = upload(h, b[6], usage)) return rc;
-  if (int rc = upload(h, b[7], exists)) return rc;
-  HIPCHK(h, b[8].ensure(usage.size() * 8));
-  HIPCHK(h, b[9].ensure(exists.size()));
+  if (h->lim_has_upl) { upl.assign(t->user_part_limit, t->user_part_limit + UA * Pn); if (int rc = upload(h, b[LM_UPL], upl)) return rc; }
+  if (h->lim_has_apl) { apl.assign(t->acct_part_limit, t->acct_part_limit + A * Pn); if (int rc = upload(h, b[LM_APL], apl)) return rc; }
+  if (int rc = upload(h, b[LM_USAGE0], usage)) return rc;
+  if (int rc = upload(h, b[LM_EXISTS0], exists)) return rc;
+  HIPCHK(h, b[LM_USAGE].ensure(usage.size() * 8));
+  HIPCHK(h, b[LM_EXISTS].ensure(exists.size()));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->lim_U = (u32)U; h->lim_UA = (u32)UA; h->lim_A = (u32)A; h->lim_Q = (u32)Q; h->lim_Pn = (u32)Pn; h->lim_NR = NR;
   h->lim_level = level;
@@ -175,30 +175,30 @@ int cns_upload_limit_jobs(cns_handle* h, const cns_limit_job_soa* jb) {
   }
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  DevBuf* b = h->d_lim;  // 10 sel, 11 user, 12 ua, 13 account, 14 qos, 15 part, 16 tl, 17 skip, 18 place_off, 19.. scratch
+  DevBuf* b = h->d_lim;
   // job keys of skipped jobs may be anything: they are never dereferenced on the device
-  if (jb->select_index) { if (int rc = stage(h, b[10], jb->select_index, J * 8)) return rc; }
-  if (int rc = stage(h, b[11], jb->user, J * 4)) return rc;
-  if (int rc = stage(h, b[12], jb->user_acct, J * 4)) return rc;
-  if (int rc = stage(h, b[13], jb->account, J * 4)) return rc;
-  if (int rc = stage(h, b[14], jb->qos, J * 4)) return rc;
-  if (int rc = stage(h, b[15], jb->partition, J * 4)) return rc;
-  if (int rc = stage(h, b[16], jb->time_limit_sec, J * 8)) return rc;
-  if (jb->skip) { if (int rc = stage(h, b[17], jb->skip, J)) return rc; }
-  if (int rc = stage(h, b[18], h->q.h_place.p, h->q.h_place.p ? (size_t)(h->q.J + 1) * 8 : 0)) return rc;
+  if (jb->select_index) { if (int rc = stage(h, b[LM_SEL], jb->select_index, J * 8)) return rc; }
+  if (int rc = stage(h, b[LM_USER], jb->user, J * 4)) return rc;
+  if (int rc = stage(h, b[LM_UA], jb->user_acct, J * 4)) return rc;
+  if (int rc = stage(h, b[LM_ACCT], jb->account, J * 4)) return rc;
+  if (int rc = stage(h, b[LM_QOS], jb->qos, J * 4)) return rc;
+  if (int rc = stage(h, b[LM_PART], jb->partition, J * 4)) return rc;
+  if (int rc = stage(h, b[LM_TL], jb->time_limit_sec, J * 8)) return rc;
+  if (jb->skip) { if (int rc = stage(h, b[LM_SKIP], jb->skip, J)) return rc; }
+  if (int rc = stage(h, b[LM_PLACEOFF], h->q.h_place.p, h->q.h_place.p ? (size_t)(h->q.J + 1) * 8 : 0)) return rc;
   h->lim_has_sel = jb->select_index != nullptr;
   h->lim_has_skip = jb->skip != nullptr;
   const u64 nb = (J + 255) / 256, Jc = std::max<u64>(J, 1);
-  HIPCHK(h, b[19].ensure(std::max<u64>(nb, 1) * 4));   // blk_cnt
-  HIPCHK(h, b[20].ensure(std::max<u64>(nb, 1) * 8));   // blk_off
-  HIPCHK(h, b[21].ensure(32));                         // total, admitted, n_items, undecided
-  HIPCHK(h, b[22].ensure(Jc * 16 * 8));                // rec_add
-  HIPCHK(h, b[23].ensure(Jc * 16 * 4));                // rec_c
-  HIPCHK(h, b[24].ensure(Jc * 16 * 4));                // rec_l
-  HIPCHK(h, b[25].ensure(Jc * 16 * 4));                // rec_en
-  HIPCHK(h, b[26].ensure(Jc * 4));                     // rec_job
-  HIPCHK(h, b[27].ensure(Jc * 4));                     // rec_meta
-  HIPCHK(h, b[28].ensure(Jc));                         // out
+  HIPCHK(h, b[LM_BLKCNT].ensure(std::max<u64>(nb, 1) * 4));
+  HIPCHK(h, b[LM_BLKOFF].ensure(std::max<u64>(nb, 1) * 8));
+  HIPCHK(h, b[LM_CTR].ensure(32));   // total, admitted, n_items, undecided
+  HIPCHK(h, b[LM_RECADD].ensure(Jc * 16 * 8));
+  HIPCHK(h, b[LM_RECC].ensure(Jc * 16 * 4));
+  HIPCHK(h, b[LM_RECL].ensure(Jc * 16 * 4));
+  HIPCHK(h, b[LM_RECEN].ensure(Jc * 16 * 4));
+  HIPCHK(h, b[LM_RECJOB].ensure(Jc * 4));
+  HIPCHK(h, b[LM_RECMETA].ensure(Jc * 4));
+  HIPCHK(h, b[LM_OUT].ensure(Jc));
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   float ms = 0;
@@ -222,20 +222,20 @@ int cns_run_limits_resident(cns_handle* h) {
   memset(&P, 0, sizeof P);
   P.J = h->lim_J; P.Q = h->lim_Q; P.Pn = h->lim_Pn;
   P.base_uq = h->lim_base[0]; P.base_up = h->lim_base[1]; P.base_aq = h->lim_base[2]; P.base_ap = h->lim_base[3]; P.base_g = h->lim_base[4];
-  P.sel = h->lim_has_sel ? b[10].as<u64>() : nullptr;
-  P.user = b[11].as<u32>(); P.ua = b[12].as<u32>(); P.account = b[13].as<u32>(); P.qos = b[14].as<u32>(); P.part = b[15].as<u32>();
-  P.tl = b[16].as<i64>(); P.skip = h->lim_has_skip ? b[17].as<uint8_t>() : nullptr;
-  P.acct_parent = b[2].as<u32>(); P.acct_level = b[3].as<u32>(); P.qos_flags = b[1].as<u32>();
-  P.user_part_limit = h->lim_has_upl ? b[4].as<u32>() : nullptr;
-  P.acct_part_limit = h->lim_has_apl ? b[5].as<u32>() : nullptr;
-  P.lim = b[0].as<LimRec>();
-  P.usage = b[8].as<i64>(); P.exists = b[9].as<uint8_t>();
+  P.sel = h->lim_has_sel ? b[LM_SEL].as<u64>() : nullptr;
+  P.user = b[LM_USER].as<u32>(); P.ua = b[LM_UA].as<u32>(); P.account = b[LM_ACCT].as<u32>(); P.qos = b[LM_QOS].as<u32>(); P.part = b[LM_PART].as<u32>();
+  P.tl = b[LM_TL].as<i64>(); P.skip = h->lim_has_skip ? b[LM_SKIP].as<uint8_t>() : nullptr;
+  P.acct_parent = b[LM_PARENT].as<u32>(); P.acct_level = b[LM_LEVEL].as<u32>(); P.qos_flags = b[LM_QFLAGS].as<u32>();
+  P.user_part_limit = h->lim_has_upl ? b[LM_UPL].as<u32>() : nullptr;
+  P.acct_part_limit = h->lim_has_apl ? b[LM_APL].as<u32>() : nullptr;
+  P.lim = b[LM_LIM].as<LimRec>();
+  P.usage = b[LM_USAGE].as<i64>(); P.exists = b[LM_EXISTS].as<uint8_t>();
   const char* rb = h->q.results.as<char>();
-  P.o_reason = (const uint8_t*)(rb + h->q.ro.reason); P.place_off = b[18].as<u64>(); P.o_node = (const u32*)(rb + h->q.ro.node);
+  P.o_reason = (const uint8_t*)(rb + h->q.ro.reason); P.place_off = b[LM_PLACEOFF].as<u64>(); P.o_node = (const u32*)(rb + h->q.ro.node);
   P.o_cpu = (const i64*)(rb + h->q.ro.cpu); P.o_mem = (const u64*)(rb + h->q.ro.mem); P.o_gres = (const u64*)(rb + h->q.ro.gres);
-  P.blk_cnt = b[19].as<u32>(); P.blk_off = b[20].as<u64>(); P.total = b[21].as<u64>(); P.admitted = b[21].as<u64>() + 1;
-  P.rec_add = b[22].as<i64>(); P.rec_c = b[23].as<u32>(); P.rec_l = b[24].as<u32>(); P.rec_en = b[25].as<u32>();
-  P.rec_job = b[26].as<u32>(); P.rec_meta = b[27].as<u32>(); P.out = b[28].as<uint8_t>();
+  P.blk_cnt = b[LM_BLKCNT].as<u32>(); P.blk_off = b[LM_BLKOFF].as<u64>(); P.total = b[LM_CTR].as<u64>(); P.admitted = b[LM_CTR].as<u64>() + 1;
+  P.rec_add = b[LM_RECADD].as<i64>(); P.rec_c = b[LM_RECC].as<u32>(); P.rec_l = b[LM_RECL].as<u32>(); P.rec_en = b[LM_RECEN].as<u32>();
+  P.rec_job = b[LM_RECJOB].as<u32>(); P.rec_meta = b[LM_RECMETA].as<u32>(); P.out = b[LM_OUT].as<uint8_t>();
   const LimCompMap m = lim_comp_map(h);
   for (u32 g = 0; g < 8; ++g) {
     P.lay.class_mask[g] = g < m.ncls ? h->gres.class_mask[g] : 0;
@@ -248,67 +248,55 @@ int cns_run_limits_resident(cns_handle* h) {
   const bool force_seq = mode_env && std::string(mode_env) == "seq";
   P.NR = (u32)h->lim_NR;
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  HIPCHK(h, hipMemcpyAsync(b[8].p, b[6].p, std::max<u64>(h->lim_NR, 1) * 128, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(b[9].p, b[7].p, std::max<u64>(h->lim_NR, 1), hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemsetAsync(b[21].p, 0, 32, h->stream));   // total, admitted, n_items, undecided
+  HIPCHK(h, hipMemcpyAsync(b[LM_USAGE].p, b[LM_USAGE0].p, std::max<u64>(h->lim_NR, 1) * 128, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(b[LM_EXISTS].p, b[LM_EXISTS0].p, std::max<u64>(h->lim_NR, 1), hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemsetAsync(b[LM_CTR].p, 0, 32, h->stream));   // total, admitted, n_items, undecided
   u64 res[2] = {0, 0};
   u32 rounds = 0;
   bool used_seq = false;
   if (nb) {
     hipLaunchKernelGGL(k_lim_flags, dim3(nb), dim3(256), 0, h->stream, P);
     hipLaunchKernelGGL(k_lim_scan, dim3(1), dim3(kLimScanThreads), 0, h->stream, P, nb);
-    HIPCHK(h, hipMemcpyAsync(res, b[21].p, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(res, b[LM_CTR].p, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));   // M sizes the item stream of the parallel pass
   }
   const u64 M = res[0];
   const u64 n = M * 16;
-  DevBuf* pb = h->d_limpar;  // 0/1 keys, 2/3 vals, 4 hist, 5 s_key, 6 s_k, 7 s_l, 8 s_en, 9 s_slot, 10 s_add, 11 state, 12 flags,
-                             // 13 jobkey, 14 tails, 15 heads, 16 carry
+  DevBuf* pb = h->d_limpar;
   const bool par = M > 0 && !force_seq && n < 0xFFFFFFF0ull;
   if (par) {
-    HIPCHK(h, pb[0].ensure(n * 8));
-    P.item_key = pb[0].as<u64>();
+    HIPCHK(h, pb[LP_K0].ensure(n * 8));
+    P.item_key = pb[LP_K0].as<u64>();
   }
   if (M) hipLaunchKernelGGL(k_lim_build, dim3(nb), dim3(256), 0, h->stream, P);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
   if (par) {
-    const u32 n32 = (u32)n, ntiles = (n32 + kSortTile - 1) / kSortTile;
-    HIPCHK(h, pb[1].ensure(n * 8)); HIPCHK(h, pb[2].ensure(n * 4)); HIPCHK(h, pb[3].ensure(n * 4));
-    HIPCHK(h, pb[4].ensure(((size_t)256 * ntiles + 256) * 4));
-    for (u32 x = 5; x <= 9; ++x) HIPCHK(h, pb[x].ensure(n * 4));
-    HIPCHK(h, pb[10].ensure(n * 128));
-    HIPCHK(h, pb[11].ensure(M)); HIPCHK(h, pb[12].ensure(M * 4)); HIPCHK(h, pb[13].ensure(M * 4));
-    HIPCHK(h, pb[14].ensure((size_t)kParChunks * 256)); HIPCHK(h, pb[15].ensure(kParChunks)); HIPCHK(h, pb[16].ensure((size_t)kParChunks * 256));
+    const u32 n32 = (u32)n;
+    HIPCHK(h, pb[LP_K1].ensure(n * 8)); HIPCHK(h, pb[LP_V0].ensure(n * 4)); HIPCHK(h, pb[LP_V1].ensure(n * 4));
+    HIPCHK(h, pb[LP_HIST].ensure(cns_sort::hist_bytes(cns_sort::tiles(n32, kSortTile))));
+    for (int x : {LP_SKEY, LP_SK, LP_SL, LP_SEN, LP_SSLOT}) HIPCHK(h, pb[x].ensure(n * 4));
+    HIPCHK(h, pb[LP_SADD].ensure(n * 128));
+    HIPCHK(h, pb[LP_STATE].ensure(M)); HIPCHK(h, pb[LP_FLAGS].ensure(M * 4)); HIPCHK(h, pb[LP_JOBKEY].ensure(M * 4));
+    HIPCHK(h, pb[LP_TAILS].ensure((size_t)kParChunks * 256)); HIPCHK(h, pb[LP_HEADS].ensure(kParChunks)); HIPCHK(h, pb[LP_CARRY].ensure((size_t)kParChunks * 256));
     // (candidate, slot) items sorted by usage record, stable: inside a record the candidates stay in commit-loop order
-    hipLaunchKernelGGL(k_iota, dim3((n32 + 255) / 256), dim3(256), 0, h->stream, pb[2].as<u32>(), n32);
-    u64* kin = pb[0].as<u64>(); u64* kout = pb[1].as<u64>();
-    u32* vin = pb[2].as<u32>(); u32* vout = pb[3].as<u32>();
-    u32* hist = pb[4].as<u32>();
-    u32* rowtot = hist + (size_t)256 * ntiles;
-    u32 bits = 0;
-    while ((h->lim_NR >> bits) != 0) ++bits;
-    for (u32 pass = 0; pass * 8 < bits; ++pass) {
-      hipLaunchKernelGGL(k_sort_hist, dim3(ntiles), dim3(256), 0, h->stream, kin, n32, pass * 8, hist, ntiles);
-      hipLaunchKernelGGL(k_sort_rowscan, dim3(256), dim3(256), 0, h->stream, hist, ntiles, rowtot);
-      hipLaunchKernelGGL(k_sort_scatter, dim3(ntiles), dim3(256), 0, h->stream, kin, vin, kout, vout, n32, pass * 8, hist, ntiles, rowtot);
-      std::swap(kin, kout);
-      std::swap(vin, vout);
-    }
+    u64* kin = pb[LP_K0].as<u64>(); u64* kout = pb[LP_K1].as<u64>();
+    u32* vin = pb[LP_V0].as<u32>(); u32* vout = pb[LP_V1].as<u32>();
+    sort_index_pairs(h->stream, n32, cns_sort::key_passes(h->lim_NR), kin, vin, kout, vout, pb[LP_HIST].as<u32>());
     ParParams R;
     memset(&R, 0, sizeof R);
-    u64* ctr = b[21].as<u64>();
+    u64* ctr = b[LM_CTR].as<u64>();
     R.n_items = ctr + 2; R.total = ctr; R.undecided = ctr + 3; R.admitted = ctr + 1;
-    R.s_key = pb[5].as<u32>(); R.s_k = pb[6].as<u32>(); R.s_l = pb[7].as<u32>(); R.s_en = pb[8].as<u32>(); R.s_slot = pb[9].as<u32>();
-    R.s_add = pb[10].as<i64>(); R.state = pb[11].as<uint8_t>(); R.flags = pb[12].as<u32>(); R.jobkey = pb[13].as<u32>();
-    R.tails = pb[14].as<i64>(); R.heads = pb[15].as<uint8_t>(); R.carry = pb[16].as<i64>();
-    R.lim = P.lim; R.usage0 = b[6].as<i64>(); R.exists0 = b[7].as<uint8_t>(); R.usage = P.usage; R.exists = P.exists;
+    R.s_key = pb[LP_SKEY].as<u32>(); R.s_k = pb[LP_SK].as<u32>(); R.s_l = pb[LP_SL].as<u32>(); R.s_en = pb[LP_SEN].as<u32>(); R.s_slot = pb[LP_SSLOT].as<u32>();
+    R.s_add = pb[LP_SADD].as<i64>(); R.state = pb[LP_STATE].as<uint8_t>(); R.flags = pb[LP_FLAGS].as<u32>(); R.jobkey = pb[LP_JOBKEY].as<u32>();
+    R.tails = pb[LP_TAILS].as<i64>(); R.heads = pb[LP_HEADS].as<uint8_t>(); R.carry = pb[LP_CARRY].as<i64>();
+    R.lim = P.lim; R.usage0 = b[LM_USAGE0].as<i64>(); R.exists0 = b[LM_EXISTS0].as<uint8_t>(); R.usage = P.usage; R.exists = P.exists;
     R.rec_meta = P.rec_meta; R.rec_job = P.rec_job; R.out = P.out;
     hipLaunchKernelGGL(k_par_gather, dim3((unsigned)((n * 16 + 255) / 256)), dim3(256), 0, h->stream, (const u64*)kin, (const u32*)vin, n,
-                       P.NR, P, pb[5].as<u32>(), pb[6].as<u32>(), pb[7].as<u32>(), pb[8].as<u32>(), pb[9].as<u32>(), pb[10].as<i64>(), ctr + 2);
-    HIPCHK(h, hipMemsetAsync(pb[11].p, 0, M, h->stream));
-    HIPCHK(h, hipMemsetAsync(pb[12].p, 0, M * 4, h->stream));
-    HIPCHK(h, hipMemsetAsync(pb[13].p, 0xFF, M * 4, h->stream));
+                       P.NR, P, pb[LP_SKEY].as<u32>(), pb[LP_SK].as<u32>(), pb[LP_SL].as<u32>(), pb[LP_SEN].as<u32>(), pb[LP_SSLOT].as<u32>(), pb[LP_SADD].as<i64>(), ctr + 2);
+    HIPCHK(h, hipMemsetAsync(pb[LP_STATE].p, 0, M, h->stream));
+    HIPCHK(h, hipMemsetAsync(pb[LP_FLAGS].p, 0, M * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(pb[LP_JOBKEY].p, 0xFF, M * 4, h->stream));
     const dim3 cg(kParChunks * 16 / 256), jg((unsigned)((M + 255) / 256));
     u64 und = M;
     while (und && rounds < kLimMaxRounds) {
@@ -336,7 +324,7 @@ int cns_run_limits_resident(cns_handle* h) {
   }
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-  HIPCHK(h, hipMemcpyAsync(res, b[21].p, 16, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(res, b[LM_CTR].p, 16, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   float a = 0, c = 0;
   HIPCHK(h, hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
@@ -356,7 +344,7 @@ int cns_download_limits(cns_handle* h, uint8_t* out, uint64_t* num_admitted) {
   if (!h->lim_have_run) return fail(h, CNS_ERR_STATE, "cns_download_limits before a successful run");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  if (h->lim_J) HIPCHK(h, hipMemcpyAsync(out, h->d_lim[28].p, h->lim_J, hipMemcpyDeviceToHost, h->stream));
+  if (h->lim_J) HIPCHK(h, hipMemcpyAsync(out, h->d_lim[LM_OUT].p, h->lim_J, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   float ms = 0;
@@ -397,8 +385,8 @@ int cns_get_usage(cns_handle* h, cns_usage* uq, uint8_t* uqe, cns_usage* up, uin
   const u64 NR = std::max<u64>(h->lim_NR, 1);
   std::vector<i64> usage(NR * 16);
   std::vector<uint8_t> exists(NR);
-  HIPCHK(h, hipMemcpy(usage.data(), h->d_lim[8].p, NR * 128, hipMemcpyDeviceToHost));
-  HIPCHK(h, hipMemcpy(exists.data(), h->d_lim[9].p, NR, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(usage.data(), h->d_lim[LM_USAGE].p, NR * 128, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(exists.data(), h->d_lim[LM_EXISTS].p, NR, hipMemcpyDeviceToHost));
   const LimCompMap m = lim_comp_map(h);
   const u64 cnt[5] = {(u64)h->lim_U * h->lim_Q, (u64)h->lim_UA * h->lim_Pn, (u64)h->lim_A * h->lim_Q, (u64)h->lim_A * h->lim_Pn, h->lim_Q};
   cns_usage* outs[5] = {uq, up, aq, ap, qu};

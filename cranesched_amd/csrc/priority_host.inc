@@ -40,28 +40,27 @@ int cns_priority_order(cns_handle* h, int64_t now_sec, const cns_priority_config
   }
 
   // ---- upload ----
-  DevBuf* pb = h->d_prio;  // 0..7 pending, 8..14 running, 15 acc_off, 16 acc_jobs, 17 present, 18 bounds, 19 acc_val,
-                           // 20 prio, 21/22 keys ping-pong, 23/24 vals ping-pong, 25 hist
-  if (int rc = stage(h, pb[0], pd->submit_sec, (size_t)J * 8)) return rc;
-  if (int rc = stage(h, pb[1], pd->qos_priority, (size_t)J * 4)) return rc;
-  if (int rc = stage(h, pb[2], pd->partition_priority, (size_t)J * 4)) return rc;
-  if (int rc = stage(h, pb[3], pd->node_num, (size_t)J * 4)) return rc;
-  if (int rc = stage(h, pb[4], pd->total_cpu_raw, (size_t)J * 8)) return rc;
-  if (int rc = stage(h, pb[5], pd->total_mem, (size_t)J * 8)) return rc;
-  if (int rc = stage(h, pb[6], pd->account, (size_t)J * 4)) return rc;
-  if (pd->cached_priority) { if (int rc = stage(h, pb[7], pd->cached_priority, (size_t)J * 8)) return rc; }
+  DevBuf* pb = h->d_prio;  // (buf_slots.h)
+  if (int rc = stage(h, pb[PR_SUBMIT], pd->submit_sec, (size_t)J * 8)) return rc;
+  if (int rc = stage(h, pb[PR_QOS], pd->qos_priority, (size_t)J * 4)) return rc;
+  if (int rc = stage(h, pb[PR_PART], pd->partition_priority, (size_t)J * 4)) return rc;
+  if (int rc = stage(h, pb[PR_NODENUM], pd->node_num, (size_t)J * 4)) return rc;
+  if (int rc = stage(h, pb[PR_CPU], pd->total_cpu_raw, (size_t)J * 8)) return rc;
+  if (int rc = stage(h, pb[PR_MEM], pd->total_mem, (size_t)J * 8)) return rc;
+  if (int rc = stage(h, pb[PR_ACCT], pd->account, (size_t)J * 4)) return rc;
+  if (pd->cached_priority) { if (int rc = stage(h, pb[PR_CACHED], pd->cached_priority, (size_t)J * 8)) return rc; }
   if (R) {
-    if (int rc = stage(h, pb[8], rn->start_sec, (size_t)R * 8)) return rc;
-    if (int rc = stage(h, pb[9], rn->qos_priority, (size_t)R * 4)) return rc;
-    if (int rc = stage(h, pb[10], rn->partition_priority, (size_t)R * 4)) return rc;
-    if (int rc = stage(h, pb[11], rn->node_num, (size_t)R * 4)) return rc;
-    if (int rc = stage(h, pb[12], rn->alloc_cpu_raw, (size_t)R * 8)) return rc;
-    if (int rc = stage(h, pb[13], rn->alloc_mem, (size_t)R * 8)) return rc;
-    if (int rc = stage(h, pb[14], rn->account, (size_t)R * 4)) return rc;
+    if (int rc = stage(h, pb[PR_RSTART], rn->start_sec, (size_t)R * 8)) return rc;
+    if (int rc = stage(h, pb[PR_RQOS], rn->qos_priority, (size_t)R * 4)) return rc;
+    if (int rc = stage(h, pb[PR_RPART], rn->partition_priority, (size_t)R * 4)) return rc;
+    if (int rc = stage(h, pb[PR_RNODENUM], rn->node_num, (size_t)R * 4)) return rc;
+    if (int rc = stage(h, pb[PR_RCPU], rn->alloc_cpu_raw, (size_t)R * 8)) return rc;
+    if (int rc = stage(h, pb[PR_RMEM], rn->alloc_mem, (size_t)R * 8)) return rc;
+    if (int rc = stage(h, pb[PR_RACCT], rn->account, (size_t)R * 4)) return rc;
   }
-  if (int rc = stage(h, pb[15], acc_off.data(), acc_off.size() * 4)) return rc;
-  if (int rc = stage(h, pb[16], acc_jobs.data(), (size_t)R * 4)) return rc;
-  if (int rc = stage(h, pb[17], present.data(), present.size())) return rc;
+  if (int rc = stage(h, pb[PR_ACCOFF], acc_off.data(), acc_off.size() * 4)) return rc;
+  if (int rc = stage(h, pb[PR_ACCJOBS], acc_jobs.data(), (size_t)R * 4)) return rc;
+  if (int rc = stage(h, pb[PR_PRESENT], present.data(), present.size())) return rc;
   PrioBounds B0{};
   B0.age_max = 0; B0.age_min = ~0ull; B0.mem_max = 0; B0.mem_min = ~0ull;
   B0.cpus_max_bits = 0;  // bits of 0.0
@@ -71,31 +70,30 @@ int cns_priority_order(cns_handle* h, int64_t now_sec, const cns_priority_config
   }
   B0.sv_max = 0.0; B0.sv_min = 4294967295.0;
   B0.qos_max = 0; B0.qos_min = ~0u; B0.part_max = 0; B0.part_min = ~0u; B0.nn_max = 0; B0.nn_min = ~0u;
-  if (int rc = stage(h, pb[18], &B0, sizeof B0)) return rc;
-  HIPCHK(h, pb[19].ensure((size_t)std::max<u32>(A, 1) * 8));
-  HIPCHK(h, pb[20].ensure((size_t)J * 8));
-  HIPCHK(h, pb[21].ensure((size_t)J * 8));
-  HIPCHK(h, pb[22].ensure((size_t)J * 8));
-  HIPCHK(h, pb[23].ensure((size_t)J * 4));
-  HIPCHK(h, pb[24].ensure((size_t)J * 4));
-  const u32 ntiles = (J + kSortTile - 1) / kSortTile;
-  HIPCHK(h, pb[25].ensure((size_t)256 * (ntiles + 1) * 4));  // [digit][tile] table + 256 row totals
-  HIPCHK(h, pb[26].ensure((size_t)std::max<u32>(R, 1) * 8));
+  if (int rc = stage(h, pb[PR_BOUNDS], &B0, sizeof B0)) return rc;
+  HIPCHK(h, pb[PR_ACCVAL].ensure((size_t)std::max<u32>(A, 1) * 8));
+  HIPCHK(h, pb[PR_PRIO].ensure((size_t)J * 8));
+  HIPCHK(h, pb[PR_K0].ensure((size_t)J * 8));
+  HIPCHK(h, pb[PR_K1].ensure((size_t)J * 8));
+  HIPCHK(h, pb[PR_V0].ensure((size_t)J * 4));
+  HIPCHK(h, pb[PR_V1].ensure((size_t)J * 4));
+  HIPCHK(h, pb[PR_HIST].ensure(cns_sort::hist_bytes(cns_sort::tiles(J, kSortTile))));  // [digit][tile] table + 256 row totals
+  HIPCHK(h, pb[PR_TERMS].ensure((size_t)std::max<u32>(R, 1) * 8));
 
   PrioParams P{};
   P.now = now_sec; P.max_age = cfg->max_age_sec;
   P.w_age = cfg->weight_age; P.w_fair = cfg->weight_fair_share; P.w_size = cfg->weight_job_size;
   P.w_part = cfg->weight_partition; P.w_qos = cfg->weight_qos; P.favor_small = cfg->favor_small ? 1u : 0u;
   P.J = J; P.R = R; P.A = A;
-  P.submit = pb[0].as<i64>(); P.qos = pb[1].as<u32>(); P.part = pb[2].as<u32>(); P.node_num = pb[3].as<u32>();
-  P.cpu_raw = pb[4].as<i64>(); P.mem = pb[5].as<u64>(); P.account = pb[6].as<u32>();
-  P.cached = pd->cached_priority ? pb[7].as<double>() : nullptr;
-  P.r_start = pb[8].as<i64>(); P.r_qos = pb[9].as<u32>(); P.r_part = pb[10].as<u32>(); P.r_node_num = pb[11].as<u32>();
-  P.r_cpu_raw = pb[12].as<i64>(); P.r_mem = pb[13].as<u64>(); P.r_account = pb[14].as<u32>();
-  P.acc_off = pb[15].as<u32>(); P.acc_jobs = pb[16].as<u32>(); P.acc_present = pb[17].as<uint8_t>();
-  P.bounds = pb[18].as<PrioBounds>(); P.acc_val = pb[19].as<double>(); P.prio = pb[20].as<double>();
-  P.keys = pb[21].as<u64>();
-  P.terms = pb[26].as<double>();
+  P.submit = pb[PR_SUBMIT].as<i64>(); P.qos = pb[PR_QOS].as<u32>(); P.part = pb[PR_PART].as<u32>(); P.node_num = pb[PR_NODENUM].as<u32>();
+  P.cpu_raw = pb[PR_CPU].as<i64>(); P.mem = pb[PR_MEM].as<u64>(); P.account = pb[PR_ACCT].as<u32>();
+  P.cached = pd->cached_priority ? pb[PR_CACHED].as<double>() : nullptr;
+  P.r_start = pb[PR_RSTART].as<i64>(); P.r_qos = pb[PR_RQOS].as<u32>(); P.r_part = pb[PR_RPART].as<u32>(); P.r_node_num = pb[PR_RNODENUM].as<u32>();
+  P.r_cpu_raw = pb[PR_RCPU].as<i64>(); P.r_mem = pb[PR_RMEM].as<u64>(); P.r_account = pb[PR_RACCT].as<u32>();
+  P.acc_off = pb[PR_ACCOFF].as<u32>(); P.acc_jobs = pb[PR_ACCJOBS].as<u32>(); P.acc_present = pb[PR_PRESENT].as<uint8_t>();
+  P.bounds = pb[PR_BOUNDS].as<PrioBounds>(); P.acc_val = pb[PR_ACCVAL].as<double>(); P.prio = pb[PR_PRIO].as<double>();
+  P.keys = pb[PR_K0].as<u64>();
+  P.terms = pb[PR_TERMS].as<double>();
 
   // ---- device work ----
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
@@ -107,19 +105,9 @@ int cns_priority_order(cns_handle* h, int64_t now_sec, const cns_priority_config
     hipLaunchKernelGGL(k_prio_service_bounds, dim3(1), dim3(256), 0, h->stream, P);
   }
   hipLaunchKernelGGL(k_prio_calc, dim3((J + 255) / 256), dim3(256), 0, h->stream, P);
-  hipLaunchKernelGGL(k_iota, dim3((J + 255) / 256), dim3(256), 0, h->stream, pb[23].as<u32>(), J);
-  u64* kin = pb[21].as<u64>(); u64* kout = pb[22].as<u64>();
-  u32* vin = pb[23].as<u32>(); u32* vout = pb[24].as<u32>();
-  u32* rowtot = pb[25].as<u32>() + (size_t)256 * ntiles;
-  for (u32 pass = 0; pass < 8; ++pass) {
-    const u32 shift = pass * 8;
-    hipLaunchKernelGGL(k_sort_hist, dim3(ntiles), dim3(256), 0, h->stream, kin, J, shift, pb[25].as<u32>(), ntiles);
-    hipLaunchKernelGGL(k_sort_rowscan, dim3(256), dim3(256), 0, h->stream, pb[25].as<u32>(), ntiles, rowtot);
-    hipLaunchKernelGGL(k_sort_scatter, dim3(ntiles), dim3(256), 0, h->stream, kin, vin, kout, vout, J, shift,
-                       pb[25].as<u32>(), ntiles, rowtot);
-    std::swap(kin, kout);
-    std::swap(vin, vout);
-  }
+  u64* kin = pb[PR_K0].as<u64>(); u64* kout = pb[PR_K1].as<u64>();
+  u32* vin = pb[PR_V0].as<u32>(); u32* vout = pb[PR_V1].as<u32>();
+  sort_index_pairs(h->stream, J, 8, kin, vin, kout, vout, pb[PR_HIST].as<u32>());   // the keys use all 64 bits: 8 passes, whatever J
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
   HIPCHK(h, hipMemcpyAsync(order_out, vin, (size_t)J * 4, hipMemcpyDeviceToHost, h->stream));

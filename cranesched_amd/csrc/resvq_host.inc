@@ -1,6 +1,6 @@
 // Host side of include/crane_gpu_resv/resv_probe.h.  Included by engine.hip inside extern "C".
 // Host work: validation, the per-node CSR of the reservations (a few entries per node), the buffers.  latest_end, the codes, the pick
-// and the earliest-start search run on the device (resvq_kernels.inc; the sort is the radix passes of priority_kernels.hip).  Everything
+// and the earliest-start search run on the device (resvq_kernels.inc; the sort is the radix passes of sort_kernels.inc).  Everything
 // lives in cns_engine::d_rq: no flag and no buffer of the cycle or of the probes is read or written, only the node count of cns_set_nodes
 // (cns_engine::N together with have_nodes).  No CPU fallback.
 
@@ -137,7 +137,7 @@ static int resvq_run_impl(cns_handle* h, i64 now, const cns_resvq_soa* q, cns_re
   const u64 cap = rq_interval_cap();
   if (intervals > cap)
     return fail(h, CNS_ERR_UNSUPPORTED, "cns_resvq_run: " + std::to_string(intervals) + " intervals in the earliest-start queries of one call, the limit is " + std::to_string(cap));
-  const u32 EV = (u32)intervals, EV2 = 2 * EV, ntiles = (EV2 + kSortTile - 1) / kSortTile;
+  const u32 EV = (u32)intervals, EV2 = 2 * EV;
   seg_off[Q] = EV;
   if (any_earliest) ev_off[L] = EV;
 
@@ -161,7 +161,7 @@ static int resvq_run_impl(cns_handle* h, i64 now, const cns_resvq_soa* q, cns_re
     if (int rc = stage(h, B[RQ_SEGOFF], seg_off.data(), ((size_t)Q + 1) * 4)) return rc;
     for (int b : {RQ_KA, RQ_KB, RQ_KC, RQ_SORTED}) HIPCHK(h, B[b].ensure((size_t)EV2 * 8));
     for (int b : {RQ_VA, RQ_VB}) HIPCHK(h, B[b].ensure((size_t)EV2 * 4));
-    HIPCHK(h, B[RQ_HIST].ensure(((size_t)256 * ntiles + 256) * 4));
+    HIPCHK(h, B[RQ_HIST].ensure(cns_sort::hist_bytes(cns_sort::tiles(EV2, kSortTile))));
   }
   RqParams P{};
   P.N = N; P.latest = B[RQ_LATEST].as<i64>(); P.rv_off = B[RQ_RVOFF].as<u32>(); P.rv_st = B[RQ_RVST].as<i64>(); P.rv_ed = B[RQ_RVED].as<i64>();
@@ -182,24 +182,13 @@ static int resvq_run_impl(cns_handle* h, i64 now, const cns_resvq_soa* q, cns_re
     HIPCHK(h, hipGetLastError());
     // all 2 EV event times by (segment, time), stable LSD passes: the 8 digits of the time, then the digits of the segment number
     u32* hist = B[RQ_HIST].as<u32>();
-    u32* rowtot = hist + (size_t)256 * ntiles;
-    auto passes = [&](u64*& kin, u32*& vin, u64*& kout, u32*& vout, u32 n_pass) {
-      for (u32 pass = 0; pass < n_pass; ++pass) {
-        hipLaunchKernelGGL(k_sort_hist, dim3(ntiles), dim3(256), 0, h->stream, (const u64*)kin, EV2, pass * 8, hist, ntiles);
-        hipLaunchKernelGGL(k_sort_rowscan, dim3(256), dim3(256), 0, h->stream, hist, ntiles, rowtot);
-        hipLaunchKernelGGL(k_sort_scatter, dim3(ntiles), dim3(256), 0, h->stream, (const u64*)kin, (const u32*)vin, kout, vout, EV2, pass * 8,
-                           (const u32*)hist, ntiles, (const u32*)rowtot);
-        std::swap(kin, kout);
-        std::swap(vin, vout);
-      }
-    };
     u64 *ka = B[RQ_KA].as<u64>(), *kb = B[RQ_KB].as<u64>(), *kc = B[RQ_KC].as<u64>();
     u32 *va = B[RQ_VA].as<u32>(), *vb = B[RQ_VB].as<u32>();
-    passes(ka, va, kb, vb, 8);                         // an even number of passes: the times in order are in RQ_KA again, their segments in RQ_VA
+    sort_pairs(h->stream, EV2, 8, ka, va, kb, vb, hist);                         // an even number of passes: the times in order are in RQ_KA again, their segments in RQ_VA
     HIPCHK(h, hipGetLastError());
     hipLaunchKernelGGL(k_rq_by_segment, grid(EV2), blk, 0, h->stream, (const u32*)va, kb, vb, EV2);
     HIPCHK(h, hipGetLastError());
-    passes(kb, vb, kc, va, cns_resvq::seg_passes(Q));  // (key, value) = (segment, position in time order); afterwards in (kb, vb)
+    sort_pairs(h->stream, EV2, cns_resvq::seg_passes(Q), kb, vb, kc, va, hist);  // (key, value) = (segment, position in time order); afterwards in (kb, vb)
     HIPCHK(h, hipGetLastError());
     hipLaunchKernelGGL(k_rq_gather, grid(EV2), blk, 0, h->stream, (const u64*)ka, (const u32*)vb, B[RQ_SORTED].as<i64>(), EV2);
     HIPCHK(h, hipGetLastError());

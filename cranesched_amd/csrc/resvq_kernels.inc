@@ -5,7 +5,7 @@
 // A call:
 //   earliest mode only — (the host lays out the event slots: 1 + reservations on its node per found candidate, one segment per query)
 //                        k_rq_emit   per candidate: the starts at which it BECOMES free (plus) and at which it stops being free (minus)
-//                        one sort of all event times by (segment, time): the stable radix passes of priority_kernels.hip (k_sort_hist,
+//                        one sort of all event times by (segment, time): the stable radix passes of sort_kernels.inc (k_sort_hist,
 //                        k_sort_rowscan, k_sort_scatter: three kernels per 8-bit digit) over the time, k_rq_by_segment, the same passes
 //                        over the segment number, k_rq_gather
 //                        k_rq_first  per plus time: free count there = plus times <= t  -  minus times <= t; the least t with count >= k

@@ -59,16 +59,15 @@ static int run_rebuild(cns_handle* h, int first, u32 R, u32 A, u32* pairs, bool*
     HIPCHK(h, B[RL_WEXP].ensure((size_t)waves * 4));
     E.wave_cnt = B[RL_WEXP].as<u32>();
     hipLaunchKernelGGL(k_run_expand<false>, dim3(grid), dim3(kRunBlock), 0, h->stream, E);
-    hipLaunchKernelGGL(k_sort_rowscan, dim3(1), dim3(256), 0, h->stream, E.wave_cnt, waves, B[RL_TOT].as<u32>() + 4);
+    scan_counts(h->stream, E.wave_cnt, waves, B[RL_TOT].as<u32>() + 4);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(&M, B[RL_TOT].as<u32>() + 4, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));   // the number of pairs sizes the sort
     if ((u64)M > (u64)A * h->rl_fan) return fail(h, CNS_ERR_HIP, "the expansion counted more (slot, allocation) pairs than the layout allows");
   }
-  const u32 ntiles = (M + kSortTile - 1) / kSortTile;
   HIPCHK(h, B[RL_K0].ensure((size_t)M * 8)); HIPCHK(h, B[RL_K1].ensure((size_t)M * 8));
   HIPCHK(h, B[RL_V0].ensure((size_t)M * 4)); HIPCHK(h, B[RL_V1].ensure((size_t)M * 4));
-  HIPCHK(h, B[RL_HIST].ensure(((size_t)256 * ntiles + 256) * 4));
+  HIPCHK(h, B[RL_HIST].ensure(cns_sort::hist_bytes(cns_sort::tiles(M, kSortTile))));
   HIPCHK(h, B[RL_RNOFF].ensure(((size_t)S + 1) * 4));
   HIPCHK(h, B[RL_RNEND].ensure((size_t)std::max<u32>(M, 1) * sizeof(i64)));
   HIPCHK(h, B[RL_RNRES].ensure((size_t)std::max<u32>(M, 1) * sizeof(Res)));
@@ -81,18 +80,7 @@ static int run_rebuild(cns_handle* h, int first, u32 R, u32 A, u32* pairs, bool*
     hipLaunchKernelGGL(k_run_expand<true>, dim3(grid), dim3(kRunBlock), 0, h->stream, E);
     HIPCHK(h, hipGetLastError());
     // (slot, entry) pairs sorted by slot, stable: inside a slot the entries stay in ledger order
-    u32* hist = B[RL_HIST].as<u32>();
-    u32* rowtot = hist + (size_t)256 * ntiles;
-    u32 bits = 0;
-    while (((u64)S >> bits) != 0) ++bits;
-    for (u32 pass = 0; pass * 8 < bits; ++pass) {
-      hipLaunchKernelGGL(k_sort_hist, dim3(ntiles), dim3(256), 0, h->stream, (const u64*)kin, M, pass * 8, hist, ntiles);
-      hipLaunchKernelGGL(k_sort_rowscan, dim3(256), dim3(256), 0, h->stream, hist, ntiles, rowtot);
-      hipLaunchKernelGGL(k_sort_scatter, dim3(ntiles), dim3(256), 0, h->stream, (const u64*)kin, (const u32*)vin, kout, vout, M, pass * 8, (const u32*)hist, ntiles,
-                         (const u32*)rowtot);
-      std::swap(kin, kout);
-      std::swap(vin, vout);
-    }
+    sort_pairs(h->stream, M, cns_sort::key_passes(S), kin, vin, kout, vout, B[RL_HIST].as<u32>());
     HIPCHK(h, hipGetLastError());
   }
   RunFill F;
@@ -197,8 +185,8 @@ static int advance_impl(cns_handle* h, const cns_running_step* in, const cns_run
     S.wave_rows = B[RL_WROWS0].as<u32>(); S.wave_ents = B[RL_WENTS0].as<u32>();
     S.base = nullptr;
     hipLaunchKernelGGL(k_run_keep<false>, dim3(grid), dim3(kRunBlock), 0, h->stream, S);
-    hipLaunchKernelGGL(k_sort_rowscan, dim3(1), dim3(256), 0, h->stream, S.wave_rows, waves, tot + 0);
-    hipLaunchKernelGGL(k_sort_rowscan, dim3(1), dim3(256), 0, h->stream, S.wave_ents, waves, tot + 1);
+    scan_counts(h->stream, S.wave_rows, waves, tot + 0);
+    scan_counts(h->stream, S.wave_ents, waves, tot + 1);
     hipLaunchKernelGGL(k_run_compact<false>, dim3(grid), dim3(kRunBlock), 0, h->stream, S);
     HIPCHK(h, hipGetLastError());
   }
@@ -220,8 +208,8 @@ static int advance_impl(cns_handle* h, const cns_running_step* in, const cns_run
     S.wave_rows = B[RL_WROWS1].as<u32>(); S.wave_ents = B[RL_WENTS1].as<u32>();
     S.base = tot;
     hipLaunchKernelGGL(k_run_keep<true>, dim3(grid), dim3(kRunBlock), 0, h->stream, S);
-    hipLaunchKernelGGL(k_sort_rowscan, dim3(1), dim3(256), 0, h->stream, S.wave_rows, waves, tot + 2);
-    hipLaunchKernelGGL(k_sort_rowscan, dim3(1), dim3(256), 0, h->stream, S.wave_ents, waves, tot + 3);
+    scan_counts(h->stream, S.wave_rows, waves, tot + 2);
+    scan_counts(h->stream, S.wave_ents, waves, tot + 3);
     hipLaunchKernelGGL(k_run_compact<true>, dim3(grid), dim3(kRunBlock), 0, h->stream, S);
     HIPCHK(h, hipGetLastError());
   }

@@ -6,7 +6,7 @@
 //   k_run_keep<false>     one workgroup per kRunChunk consecutive ledger rows, one lane per row, four independent waves (k_gate_jobs'
 //                         shape): a bisection of the sorted retire ids; a hit stores found[position] = 1 (equal values from several lanes
 //                         are harmless) and drops the row.  Per wave one count of kept rows and one of kept allocation entries.
-//   k_sort_rowscan        (priority_kernels.hip, unchanged, one workgroup) the exclusive scan of each count array in place,
+//   k_sort_rowscan        (sort_kernels.inc, one workgroup: scan_counts of sort_call.inc) the exclusive scan of each count array in place,
 //                         kRunScanSpan per step: the ordered compaction of cns_gate_pending.  No atomic hands out a position.
 //   k_run_compact<false>  the row goes to base + mbcnt rank, its allocations to base + the wave prefix over the lanes' entry counts.  A
 //                         row of at most kRunLaneMax entries is copied by its own lane; a wider one is handed to its wave, 64 entries
@@ -21,7 +21,7 @@
 //                         slot, by bisection of that reservation's ascending slot range (ResvLayout::resv_slot) — counted per wave.
 //   k_sort_rowscan        the ordered scan of the per-wave counts
 //   k_run_expand<true>    the (slot, entry) pairs in entry order
-//   k_sort_hist / k_sort_rowscan / k_sort_scatter   (unchanged) the stable LSD sort of the pairs by slot, ceil(bits(S) / 8) passes:
+//   k_sort_hist / k_sort_rowscan / k_sort_scatter   (sort_kernels.inc: sort_pairs of sort_call.inc) the stable LSD sort of the pairs by slot, ceil(bits(S) / 8) passes:
 //                         per slot the entries stay in ledger order, which is build_running's order
 //   k_run_fill            per sorted pair rn_end / rn_res; per slot rn_off as a lower bound in the sorted keys, and the time map's
 //                         capacity check, a failure recorded in a flag word.  No atomics.

@@ -14,47 +14,47 @@ int cns_schedule_steps(cns_handle* h, const cns_step_job_soa* jb, const cns_step
   std::vector<StepRec>& recs = pk.recs;
   std::vector<Res>& avail = pk.avail;
   HIPCHK(h, hipSetDevice(h->device));
-  DevBuf* b = h->d_step;  // 0 node_off, 1 node_idx, 2 avail, 3 step_off, 4 steps, 5 incl, 6 excl, 7 scheduled, 8 o_node, 9 o_nt, 10 o_alloc, 11 t_node, 12 t_alloc
-  if (int rc = stage(h, b[0], jb->node_offsets, ((size_t)Jn + 1) * 4)) return rc;
-  if (int rc = stage(h, b[1], jb->node_idx, (size_t)Nn * 4)) return rc;
-  if (int rc = upload(h, b[2], avail)) return rc;
-  if (int rc = stage(h, b[3], jb->step_offsets, ((size_t)Jn + 1) * 4)) return rc;
-  if (int rc = upload(h, b[4], recs)) return rc;
-  if (int rc = stage(h, b[5], st->incl_nodes, (size_t)n_incl * 4)) return rc;
-  if (int rc = stage(h, b[6], st->excl_nodes, (size_t)n_excl * 4)) return rc;
+  DevBuf* b = h->d_step;  // (buf_slots.h)
+  if (int rc = stage(h, b[ST_NODEOFF], jb->node_offsets, ((size_t)Jn + 1) * 4)) return rc;
+  if (int rc = stage(h, b[ST_NODEIDX], jb->node_idx, (size_t)Nn * 4)) return rc;
+  if (int rc = upload(h, b[ST_AVAIL], avail)) return rc;
+  if (int rc = stage(h, b[ST_STEPOFF], jb->step_offsets, ((size_t)Jn + 1) * 4)) return rc;
+  if (int rc = upload(h, b[ST_STEPS], recs)) return rc;
+  if (int rc = stage(h, b[ST_INCL], st->incl_nodes, (size_t)n_incl * 4)) return rc;
+  if (int rc = stage(h, b[ST_EXCL], st->excl_nodes, (size_t)n_excl * 4)) return rc;
   const size_t pl = std::max<u64>(places, 1), tk = std::max<u64>(tasks, 1);
-  HIPCHK(h, b[7].ensure(std::max<u32>(S, 1))); HIPCHK(h, b[8].ensure(pl * 4)); HIPCHK(h, b[9].ensure(pl * 4)); HIPCHK(h, b[10].ensure(pl * sizeof(Res)));
-  HIPCHK(h, b[11].ensure(tk * 4)); HIPCHK(h, b[12].ensure(tk * sizeof(Res)));
-  HIPCHK(h, hipMemsetAsync(b[7].p, 0, std::max<u32>(S, 1), h->stream));
-  HIPCHK(h, hipMemsetAsync(b[8].p, 0xFF, pl * 4, h->stream));
-  HIPCHK(h, hipMemsetAsync(b[9].p, 0, pl * 4, h->stream));
-  HIPCHK(h, hipMemsetAsync(b[10].p, 0, pl * sizeof(Res), h->stream));
-  HIPCHK(h, hipMemsetAsync(b[11].p, 0xFF, tk * 4, h->stream));
-  HIPCHK(h, hipMemsetAsync(b[12].p, 0, tk * sizeof(Res), h->stream));
+  HIPCHK(h, b[ST_SCHEDULED].ensure(std::max<u32>(S, 1))); HIPCHK(h, b[ST_ONODE].ensure(pl * 4)); HIPCHK(h, b[ST_ONT].ensure(pl * 4)); HIPCHK(h, b[ST_OALLOC].ensure(pl * sizeof(Res)));
+  HIPCHK(h, b[ST_TNODE].ensure(tk * 4)); HIPCHK(h, b[ST_TALLOC].ensure(tk * sizeof(Res)));
+  HIPCHK(h, hipMemsetAsync(b[ST_SCHEDULED].p, 0, std::max<u32>(S, 1), h->stream));
+  HIPCHK(h, hipMemsetAsync(b[ST_ONODE].p, 0xFF, pl * 4, h->stream));
+  HIPCHK(h, hipMemsetAsync(b[ST_ONT].p, 0, pl * 4, h->stream));
+  HIPCHK(h, hipMemsetAsync(b[ST_OALLOC].p, 0, pl * sizeof(Res), h->stream));
+  HIPCHK(h, hipMemsetAsync(b[ST_TNODE].p, 0xFF, tk * 4, h->stream));
+  HIPCHK(h, hipMemsetAsync(b[ST_TALLOC].p, 0, tk * sizeof(Res), h->stream));
   StepParams P;
   memset(&P, 0, sizeof P);
   P.num_jobs = Jn;
-  P.node_off = b[0].as<u32>(); P.node_idx = b[1].as<u32>(); P.avail = b[2].as<Res>(); P.step_off = b[3].as<u32>();
-  P.steps = b[4].as<StepRec>(); P.incl = b[5].as<u32>(); P.excl = b[6].as<u32>();
-  P.scheduled = b[7].as<uint8_t>(); P.o_node = b[8].as<u32>(); P.o_nt = b[9].as<u32>(); P.o_alloc = b[10].as<Res>();
-  P.t_node = b[11].as<u32>(); P.t_alloc = b[12].as<Res>();
+  P.node_off = b[ST_NODEOFF].as<u32>(); P.node_idx = b[ST_NODEIDX].as<u32>(); P.avail = b[ST_AVAIL].as<Res>(); P.step_off = b[ST_STEPOFF].as<u32>();
+  P.steps = b[ST_STEPS].as<StepRec>(); P.incl = b[ST_INCL].as<u32>(); P.excl = b[ST_EXCL].as<u32>();
+  P.scheduled = b[ST_SCHEDULED].as<uint8_t>(); P.o_node = b[ST_ONODE].as<u32>(); P.o_nt = b[ST_ONT].as<u32>(); P.o_alloc = b[ST_OALLOC].as<Res>();
+  P.t_node = b[ST_TNODE].as<u32>(); P.t_alloc = b[ST_TALLOC].as<Res>();
   P.gres = h->gres;
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
   if (Jn) hipLaunchKernelGGL(k_sched_steps, dim3((Jn + 63) / 64), dim3(64), 0, h->stream, P);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
   std::vector<Res> o_alloc(pl), t_alloc(tk);
-  HIPCHK(h, hipMemcpyAsync(out->scheduled, b[7].p, S, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(out->scheduled, b[ST_SCHEDULED].p, S, hipMemcpyDeviceToHost, h->stream));
   if (places) {
-    HIPCHK(h, hipMemcpyAsync(out->node_idx, b[8].p, places * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(out->node_ntasks, b[9].p, places * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(o_alloc.data(), b[10].p, places * sizeof(Res), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out->node_idx, b[ST_ONODE].p, places * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out->node_ntasks, b[ST_ONT].p, places * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(o_alloc.data(), b[ST_OALLOC].p, places * sizeof(Res), hipMemcpyDeviceToHost, h->stream));
   }
   if (tasks) {
-    HIPCHK(h, hipMemcpyAsync(out->task_node, b[11].p, tasks * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(t_alloc.data(), b[12].p, tasks * sizeof(Res), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(out->task_node, b[ST_TNODE].p, tasks * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(t_alloc.data(), b[ST_TALLOC].p, tasks * sizeof(Res), hipMemcpyDeviceToHost, h->stream));
   }
-  if (Nn) HIPCHK(h, hipMemcpyAsync(avail.data(), b[2].p, (size_t)Nn * sizeof(Res), hipMemcpyDeviceToHost, h->stream));
+  if (Nn) HIPCHK(h, hipMemcpyAsync(avail.data(), b[ST_AVAIL].p, (size_t)Nn * sizeof(Res), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (u64 i = 0; i < places; ++i) {
     out->node_cpu_raw[i] = o_alloc[i].cpu; out->node_mem[i] = o_alloc[i].mem; out->node_core_lo[i] = o_alloc[i].clo;

@@ -157,26 +157,14 @@ static int submit_impl(cns_handle* h, const cns_job_soa* jb, const cns_submit_ke
   u32 rounds = 0;
   bool decided = false;
   if (par) {
-    const u32 n32 = (u32)n, ntiles = (n32 + kSortTile - 1) / kSortTile;
+    const u32 n32 = (u32)n;
     HIPCHK(h, B[SB_SK1].ensure(n * 8)); HIPCHK(h, B[SB_SV0].ensure(n * 4)); HIPCHK(h, B[SB_SV1].ensure(n * 4));
-    HIPCHK(h, B[SB_HIST].ensure(((size_t)256 * ntiles + 256) * 4));
+    HIPCHK(h, B[SB_HIST].ensure(cns_sort::hist_bytes(cns_sort::tiles(n32, kSortTile))));
     HIPCHK(h, B[SB_SKEY].ensure(n * 4)); HIPCHK(h, B[SB_SITEM].ensure(n * 4)); HIPCHK(h, B[SB_SADD].ensure(n * 4)); HIPCHK(h, B[SB_VAL].ensure(n * 8));
     // (job, position) items sorted by table index, stable: inside a record the jobs stay in arrival order
-    hipLaunchKernelGGL(k_iota, dim3((n32 + 255) / 256), dim3(256), 0, h->stream, B[SB_SV0].as<u32>(), n32);
     u64* kin = B[SB_SK0].as<u64>(); u64* kout = B[SB_SK1].as<u64>();
     u32* vin = B[SB_SV0].as<u32>(); u32* vout = B[SB_SV1].as<u32>();
-    u32* hist = B[SB_HIST].as<u32>();
-    u32* rowtot = hist + (size_t)256 * ntiles;
-    u32 bits = 0;
-    while (((u64)NK >> bits) != 0) ++bits;
-    for (u32 pass = 0; pass * 8 < bits; ++pass) {
-      hipLaunchKernelGGL(k_sort_hist, dim3(ntiles), dim3(256), 0, h->stream, (const u64*)kin, n32, pass * 8, hist, ntiles);
-      hipLaunchKernelGGL(k_sort_rowscan, dim3(256), dim3(256), 0, h->stream, hist, ntiles, rowtot);
-      hipLaunchKernelGGL(k_sort_scatter, dim3(ntiles), dim3(256), 0, h->stream, (const u64*)kin, (const u32*)vin, kout, vout, n32, pass * 8, (const u32*)hist, ntiles,
-                         (const u32*)rowtot);
-      std::swap(kin, kout);
-      std::swap(vin, vout);
-    }
+    sort_index_pairs(h->stream, n32, cns_sort::key_passes(NK), kin, vin, kout, vout, B[SB_HIST].as<u32>());
     hipLaunchKernelGGL(k_sub_gather, dim3((n32 + 255) / 256), dim3(256), 0, h->stream, (const u64*)kin, (const u32*)vin, n32, NK, P.count, B[SB_SKEY].as<u32>(),
                        B[SB_SITEM].as<u32>(), B[SB_SADD].as<u32>(), P.ctr);
     HIPCHK(h, hipGetLastError());

@@ -80,10 +80,10 @@ static int usage_impl(cns_handle* h, u32 op, const cns_usage_jobs* jb, u32 flags
   }
   const u32 NR = (u32)D.NR, NK = (u32)(D.NR + D.NE);
   const size_t n = (size_t)J * kUseSlots, tab_bytes = use_tab_bytes(h), rec_bytes = (size_t)NR * kUseComp * 8;
-  const u32 n32 = (u32)n, ntiles = (n32 + kSortTile - 1) / kSortTile;
+  const u32 n32 = (u32)n;
   HIPCHK(h, B[US_DELTA].ensure((size_t)J * kUseComp * 8)); HIPCHK(h, B[US_MASK].ensure((size_t)J * 4)); HIPCHK(h, B[US_CTR].ensure(64));
   HIPCHK(h, B[US_SK0].ensure(n * 8)); HIPCHK(h, B[US_SK1].ensure(n * 8)); HIPCHK(h, B[US_SV0].ensure(n * 4)); HIPCHK(h, B[US_SV1].ensure(n * 4));
-  HIPCHK(h, B[US_HIST].ensure(((size_t)256 * ntiles + 256) * 4)); HIPCHK(h, B[US_SKEY].ensure(n * 4)); HIPCHK(h, B[US_SITEM].ensure(n * 4));
+  HIPCHK(h, B[US_HIST].ensure(cns_sort::hist_bytes(cns_sort::tiles(n32, kSortTile)))); HIPCHK(h, B[US_SKEY].ensure(n * 4)); HIPCHK(h, B[US_SITEM].ensure(n * 4));
   HIPCHK(h, hipMemsetAsync(B[US_CTR].p, 0, 64, h->stream));
   const DevBuf& src = carry ? B[US_TAB_CUR] : B[US_TAB_SET];
   if (tab_bytes) HIPCHK(h, hipMemcpyAsync(B[US_TAB_WORK].p, src.p, tab_bytes, hipMemcpyDeviceToDevice, h->stream));
@@ -105,21 +105,9 @@ static int usage_impl(cns_handle* h, u32 op, const cns_usage_jobs* jb, u32 flags
   hipLaunchKernelGGL(k_use_items, dim3((J + kUseChunk - 1) / kUseChunk), dim3(256), 0, h->stream, P);
 
   // (row, slot) items sorted by record id, stable: inside a record the rows stay in call order
-  hipLaunchKernelGGL(k_iota, dim3((n32 + 255) / 256), dim3(256), 0, h->stream, B[US_SV0].as<u32>(), n32);
   u64* kin = B[US_SK0].as<u64>(); u64* kout = B[US_SK1].as<u64>();
   u32* vin = B[US_SV0].as<u32>(); u32* vout = B[US_SV1].as<u32>();
-  u32* hist = B[US_HIST].as<u32>();
-  u32* rowtot = hist + (size_t)256 * ntiles;
-  u32 bits = 0;
-  while (((u64)NK >> bits) != 0) ++bits;
-  for (u32 pass = 0; pass * 8 < bits; ++pass) {
-    hipLaunchKernelGGL(k_sort_hist, dim3(ntiles), dim3(256), 0, h->stream, (const u64*)kin, n32, pass * 8, hist, ntiles);
-    hipLaunchKernelGGL(k_sort_rowscan, dim3(256), dim3(256), 0, h->stream, hist, ntiles, rowtot);
-    hipLaunchKernelGGL(k_sort_scatter, dim3(ntiles), dim3(256), 0, h->stream, (const u64*)kin, (const u32*)vin, kout, vout, n32, pass * 8, (const u32*)hist, ntiles,
-                       (const u32*)rowtot);
-    std::swap(kin, kout);
-    std::swap(vin, vout);
-  }
+  sort_index_pairs(h->stream, n32, cns_sort::key_passes(NK), kin, vin, kout, vout, B[US_HIST].as<u32>());
   u64* ctr = B[US_CTR].as<u64>();
   hipLaunchKernelGGL(k_use_gather, dim3((n32 + 255) / 256), dim3(256), 0, h->stream, (const u64*)kin, (const u32*)vin, n32, NK, B[US_SKEY].as<u32>(),
                      B[US_SITEM].as<u32>(), ctr);

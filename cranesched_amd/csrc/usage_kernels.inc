@@ -15,7 +15,7 @@
 //   k_use_items  row-parallel, one lane per row: the row's delta as 17 u64, its up to 15 record ids (slot x = bit x of the masks), the
 //                bits that need no table value (:1172), and for a charge the entity bytes.  A release reads the entity bytes, which it
 //                never changes.
-//   k_sort_* / k_iota (priority_kernels.hip): the (record id, row * 15 + slot) items sorted by record id, stable: inside a record the
+//   k_sort_* / k_iota (sort_kernels.inc): the (record id, row * 15 + slot) items sorted by record id, stable: inside a record the
 //                rows stay in call order.  k_use_gather: the sorted streams, and how many items carry a record.
 //   k_use_tails, k_use_carry, k_use_eval: the segmented inclusive scan of the 17 components over the sorted items (a segment = one
 //                record), in three launches: per chunk its last segment's sums, one workgroup over the chunk tails, the re-walk with the

@@ -1,10 +1,10 @@
 """Deterministic scenarios for the reservation what-ifs (include/crane_gpu_resv/resv_probe.h) that sit ON the seams of the device code
-(csrc/resvq_kernels.inc, csrc/resvq_host.inc, the radix sort of csrc/priority_kernels.hip), where tests/resvq_case.py's random
+(csrc/resvq_kernels.inc, csrc/resvq_host.inc, the radix sort of csrc/sort_kernels.inc), where tests/resvq_case.py's random
 scenarios never go: times over the whole signed 64-bit range, long chains of blocked ranges per node, empty lists and jobs without an
 allocation, every number of radix passes over the segment numbers, a sort wider than one step of its scan, one handle across sizes.
 
 Every generator returns a Seam (cluster, running, resv, queries, now).  The constants come from cns_resvq_shape (`shape`, an
-abi.ResvqShape) and from csrc/resvq_passes.inc (the digit width), never from a literal here.  The truth stays resvq_pyref.answer:
+abi.ResvqShape) and from csrc/sort_host.inc (the digit width), never from a literal here.  The truth stays resvq_pyref.answer:
 expected() evaluates it once per DISTINCT query — queries are answered independently of one another — and replicates the answers.
 
 Used by tests/test_resvq_seams.py (no GPU: do the generators hit what they name?) and tests/test_gpu_resvq_seams.py."""
@@ -31,8 +31,8 @@ Seam = namedtuple("Seam", ("cluster", "running", "resv", "queries", "now"))
 
 
 def digit_bits() -> int:
-    """The digit width of the sort's passes, from the routine that counts them (csrc/resvq_passes.inc)."""
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cranesched_amd", "csrc", "resvq_passes.inc")).read()
+    """The digit width of the sort's passes, from the file that defines it for every caller of the sort (csrc/sort_host.inc)."""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cranesched_amd", "csrc", "sort_host.inc")).read()
     return int(re.search(r"kDigitBits = (\d+);", src).group(1))
 
 
