@@ -844,6 +844,17 @@ class CnsRunningTiming(C.Structure):
                 ("pairs", C.c_uint64)]
 
 
+# include/crane_gpu_running/running_preempt.h
+class CnsPreemptIndexOut(C.Structure):
+    _fields_ = [("capacity_entries", C.c_uint64), ("capacity_rows", C.c_uint64), ("num_entries", _P), ("num_rows", _P)] + \
+               [(f, _P) for f in ("ent_job", "ent_slot", "ent_end", "rj_off", "rj_ent", "rj_end", "rj_preempting")]
+
+
+class CnsRunningPreemptTiming(C.Structure):
+    _fields_ = [("setup_ms", C.c_double), ("index_ms", C.c_double), ("mark_ms", C.c_double), ("entries", C.c_uint64), ("rows", C.c_uint64),
+                ("index_built", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
 def _csr(lists):
     off = np.zeros(len(lists) + 1, np.uint64)
     off[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64) if len(lists) else []

@@ -69,6 +69,11 @@ enum { RL_ID = 0, RL_END, RL_RESV, RL_OFF, RL_NODE, RL_RES,                     
        RL_WROWS0, RL_WENTS0, RL_WROWS1, RL_WENTS1, RL_TOT, RL_NSOFF, RL_NS, RL_WEXP,                        // counts, the node -> slots CSR
        RL_K0, RL_K1, RL_V0, RL_V1, RL_HIST, RL_RNOFF, RL_RNEND, RL_RNRES, RL_FLAG, RL_COUNT };              // pairs, the per-slot tables
 
+// cns_engine::d_rp (running_preempt_host.inc): the sorted (slot, allocation) pairs of the last rebuild, the index built from them,
+// the call's lists and tables
+enum { RP_KEYS = 0, RP_VALS, RP_ENTJOB, RP_ENTSLOT, RP_K0, RP_K1, RP_V0, RP_V1, RP_HIST, RP_RJOFF, RP_RJENT,   // per rebuild
+       RP_GIVEN, RP_SET, RP_FOUND, RP_FLAG, RP_RJPRE, RP_RJEND, RP_ENTEND, RP_COUNT };                         // per call
+
 // cns_engine::d_pre (engine.hip: a cycle with preemption)
 enum { B_QPOFF, B_QP, B_PJQOS, B_PJQP, B_PJPRIO, B_PJREC0, B_PJK, B_PJEND, B_RNJOB, B_ENTSLOT, B_ENTGONE, B_RJQOS, B_RJQP,
        B_RJSTART, B_RJEND, B_RJPRE, B_RJOFF, B_RJENT, B_HEAD, B_RECNEXT, B_RECORIG, B_RECSLOT, B_RECGONE, B_MISC, B_COUNT };

@@ -10,8 +10,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <set>
 #include <string>
@@ -29,6 +31,7 @@
 #include "../../include/crane_gpu_gate/pending_gate.h"
 #include "../../include/crane_gpu_usage/usage.h"
 #include "../../include/crane_gpu_running/running.h"
+#include "../../include/crane_gpu_running/running_preempt.h"
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
 #include <limits>
@@ -47,6 +50,7 @@
 #include "usage_kernels.inc"  // releases and charges of a batch of jobs on the usage tables (include/crane_gpu_usage/usage.h)
 #include "gate_kernels.inc"   // the dependency-event drain and Phase 1 in front of a cycle (include/crane_gpu_gate/pending_gate.h)
 #include "running_kernels.inc" // the running set kept on the device between two cycles: retire, admit, rebuild (include/crane_gpu_running/running.h)
+#include "running_preempt_kernels.inc" // a cycle with preemption on that set: the entry index, the job -> entries CSR, the marks and the end patch (include/crane_gpu_running/running_preempt.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 #include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
 #include "csr_host.inc"        // the CSR rules of the callers' lists: offsets, sorted lists without a repeat (no HIP in there either)
@@ -54,6 +58,7 @@
 #include "gate_check_host.inc" // the input rules of cns_gate_pending (no HIP in there either)
 #include "usage_check_host.inc" // the input rules of cns_usage_set_tables / cns_usage_apply (no HIP in there either)
 #include "running_check_host.inc" // the input rules of cns_running_seed / cns_running_advance (no HIP in there either)
+#include "running_preempt_check_host.inc" // the input rules of cns_running_select_preempt (no HIP in there either)
 #include "sort_host.inc"       // the arithmetic of the pair sort: passes, tiles, histogram bytes (no HIP in there either)
 #include "resvq_passes.inc"    // the radix passes over the segment numbers of cns_resvq_run's sort (no HIP in there either)
 #include "buf_slots.h"         // the slots of cns_engine's per-feature buffer sets
@@ -244,6 +249,17 @@ struct cns_engine {
   u64 lay_gen = 0, rl_lay_gen = ~0ull;          // uploads of the snapshot so far; the one RL_NSOFF / RL_NS were derived from
   u32 rl_fan = 1;                               // slots of the node in most partitions
   cns_running_timing rl_timing{};
+  // a cycle with preemption on that set (running_preempt_host.inc): the sorted pairs of the rebuild the per-slot tables came from, the
+  // index built from them, the call's lists and tables
+  DevBuf d_rp[RP_COUNT];
+  u32 rl_M = 0;                                 // (slot, allocation) pairs of that rebuild: the entries of the per-slot tables
+  int rl_sorted_side = 0;                       // run_rebuild: which of RL_K0 / RL_K1 (RL_V0 / RL_V1) holds the sorted pairs
+  bool rp_index = false;                        // RP_ENTJOB .. RP_RJENT describe the current per-slot tables
+  bool rp_call = false;                         // RP_RJPRE, RP_RJEND, RP_ENTEND are those of a cns_running_select_preempt on that index
+  bool run_preempt_rl = false;                  // the last successful cycle was such a call with preemption enabled (the admit step is served behind it)
+  std::chrono::steady_clock::time_point pre_t0{};   // entry of the last cns_select_preempt / cns_running_select_preempt with preemption enabled
+  cns_running_preempt_timing rp_timing{};       // ... what it spent in front of its cycle
+  const i64* rn_end_bound = nullptr;            // the per-slot end times of the next run when they are not d_rn_end (the patched copy of such a call)
 };
 
 namespace {
@@ -365,7 +381,7 @@ void fill_params(cns_engine* h, KParams& K, i64 now, const RunKnobs& kn = RunKno
   K.dip_t = h->d_dipt.as<u32>(); K.dip_cm = h->d_dipcm.as<u32>(); K.dip_g = h->d_dipg.as<u32>();
   if (h->lay.shared) { K.f_len = h->d_flen.as<u32>(); K.tag_off = h->d_tag_off.as<u32>(); K.tag_base = h->d_tag_base.as<u32>(); }
   K.rn_off = h->d_rn_off.as<u32>();
-  K.rn_end = h->d_rn_end.as<i64>();
+  K.rn_end = h->rn_end_bound ? h->rn_end_bound : h->d_rn_end.as<i64>();
   K.rn_res = h->d_rn_res.as<Res>();
   K.pj_off = h->d_pj_off.as<u64>();
   table_bind(h, h->q, K);
@@ -572,7 +588,7 @@ int upload_running(cns_engine* h) {
 int upload_snapshot(cns_engine* h) {
   const cns_snapshot::ResvLayout& X = h->rlay;
   (void)cns_snapshot::build_running(h->lay, X, nullptr, h->run);
-  ++h->lay_gen; h->rl_dev = false;   // (a ledger survives; its per-slot tables come back with the next cns_running_advance)
+  ++h->lay_gen; h->rl_dev = false; h->rp_index = h->rp_call = false;   // (a ledger survives; its per-slot tables come back with the next cns_running_advance)
   if (h->lay.shared) {
     if (int rc = upload(h, h->d_slot_block, X.slot_block)) return rc;
     if (int rc = upload(h, h->d_sib_off, X.sib_off)) return rc;
@@ -720,7 +736,7 @@ int cns_set_running(cns_handle* h, const cns_running_soa* rn) {
   cns_snapshot::RunLayout run;
   if (const cns_snapshot::Status st = cns_snapshot::build_running(h->lay, h->rlay, rn, run)) return fail(h, st.code, st.msg);
   h->run = std::move(run);
-  h->rl_have = h->rl_dev = false;   // (the ledger of cns_running_seed describes another set now)
+  h->rl_have = h->rl_dev = false; h->rp_index = h->rp_call = false;   // (the ledger of cns_running_seed describes another set now)
   if (int rc = upload_running(h)) return rc;
   h->have_run = false;
   return CNS_OK;
@@ -784,7 +800,7 @@ static int run_resident_once(cns_handle* h, int64_t now, const RunKnobs& kn, boo
     // k_select partitions too, and a second pass over a first pass's per-slot job lists (slot_head / rec_next), hidden
     // candidates (ent_gone / rec_gone) and preempted pairs (out_cnt) would loop on a self-linked list or report pairs twice.
     DevBuf* B = h->d_pre;
-    HIPCHK(h, hipMemsetAsync(B[B_ENTGONE].p, 0, std::max<size_t>(h->run.ent_job.size(), 1), h->stream));
+    HIPCHK(h, hipMemsetAsync(B[B_ENTGONE].p, 0, std::max<size_t>(h->rl_dev ? (size_t)h->rl_M : h->run.ent_job.size(), 1), h->stream));
     HIPCHK(h, hipMemsetAsync(B[B_HEAD].p, 0xFF, (size_t)std::max<u32>(h->rlay.S, 1) * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(B[B_RECGONE].p, 0, std::max<u64>(h->q.places, 1), h->stream));
     HIPCHK(h, hipMemsetAsync(h->pre_params.out_cnt, 0, 16, h->stream));
@@ -893,6 +909,7 @@ static int run_resident_once(cns_handle* h, int64_t now, const RunKnobs& kn, boo
   }
   h->have_run = true;
   h->run_preempt = h->pre_call;
+  h->run_preempt_rl = false;   // (cns_running_select_preempt sets it behind its cycle)
   return CNS_OK;
 }
 
@@ -971,6 +988,130 @@ int cns_select(cns_handle* h, int64_t now, const cns_job_soa* jobs, cns_placemen
   return cns_download(h, out);
 }
 
+// The cycle of cns_select_preempt / cns_running_select_preempt behind their setup of the running side: the queue is uploaded, the
+// end times of the preempting rows are bound.  R running jobs, A entries of the per-slot tables, set_in: the ids of the preempting set
+// that still run.  bind_running puts the running side's tables on the device and names them in the parameter block.
+static int pre_cycle(cns_handle* h, int64_t now, const cns_job_soa* jobs, const cns_preempt_soa* pre, cns_placement_soa* out, cns_preempt_out* pout,
+                     const u32 R, const u32 A, const std::vector<u32>& set_in, const std::string& who, const std::function<int(PreParams&)>& bind_running) {
+  const u64 J = jobs->num_jobs;
+  // No pending job's qos may preempt anything: TryPreempt_ returns at :6385 for every job, so the cycle is the plain one
+  // (with the preempting jobs ending at now + 1) and runs on the pipelined kernels.
+  bool any_list = false;
+  for (u64 j = 0; j < J && !any_list; ++j) {
+    const u32 q = pre->pd_qos[j];
+    any_list = q < pre->num_qos && pre->qos_preempt_offsets[q + 1] > pre->qos_preempt_offsets[q];
+  }
+  const auto setup_done = [h] { h->rp_timing.setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h->pre_t0).count(); };
+  if (!any_list) {
+    setup_done();
+    int rc = cns_run_resident(h, now);
+    if (rc) return rc;
+    if (int rc3 = cns_download(h, out)) return rc3;
+    for (u64 j = 0; j <= J; ++j) pout->offsets[j] = 0;
+    pout->num_cancelled = 0;
+    pout->num_preempting = 0;
+    std::set<u32> keep(set_in.begin(), set_in.end());
+    for (u32 id : keep) {
+      if (pout->num_preempting >= pout->preempting_capacity) return fail(h, CNS_ERR_INVALID_ARG, who + ": preempting_capacity too small");
+      pout->preempting_job_ids[pout->num_preempting++] = id;
+    }
+    return CNS_OK;
+  }
+  // qos preempt lists, pending-job fields (by queue index)
+  std::vector<u32> qp_off(pre->num_qos + 1, 0), qp;
+  for (u32 q = 0; q < pre->num_qos; ++q) {
+    for (u32 i = pre->qos_preempt_offsets[q]; i < pre->qos_preempt_offsets[q + 1]; ++i) qp.push_back(pre->qos_preempt[i]);
+    qp_off[q + 1] = (u32)qp.size();
+  }
+  if (qp.empty()) qp.push_back(0);
+  std::vector<u32> pj_qos(std::max<u64>(J, 1), 0), pj_qprio(std::max<u64>(J, 1), 0);
+  std::vector<double> pj_prio(std::max<u64>(J, 1), 0.0);
+  for (u64 j = 0; j < J; ++j) { pj_qos[j] = pre->pd_qos[j]; pj_qprio[j] = pre->pd_qos_priority[j]; pj_prio[j] = pre->pd_priority[j]; }
+  const u64 places = std::max<u64>(h->q.places, 1);
+  // work buffers per partition (documented in include/crane_gpu/preempt.h): candidate / chosen lists sized for every running
+  // job plus every pending job of the cycle (at most all of them hold resources on one job's nodes), bounded by 64 Mi entries
+  // over all partitions; segment-tree pools of 65 536 nodes.  Exceeding either is CNS_ERR_UNSUPPORTED, not a device fault.
+  const u32 pool_nodes = 1u << 16;
+  const u32 cand_cap = (u32)std::max<u64>(4096, std::min<u64>((u64)R + J + 1, (64ull << 20) / std::max<u32>(h->rlay.P, 1)));
+  const u32 out_cap = (u32)std::min<u64>(4 * (J + R) + 64, 1u << 28);
+  DevBuf* B = h->d_pre;
+  if (int rc = upload(h, B[B_QPOFF], qp_off)) return rc;
+  if (int rc = upload(h, B[B_QP], qp)) return rc;
+  if (int rc = upload(h, B[B_PJQOS], pj_qos)) return rc;
+  if (int rc = upload(h, B[B_PJQP], pj_qprio)) return rc;
+  if (int rc = upload(h, B[B_PJPRIO], pj_prio)) return rc;
+  HIPCHK(h, B[B_PJREC0].ensure(std::max<u64>(J, 1) * 4)); HIPCHK(h, B[B_PJK].ensure(std::max<u64>(J, 1) * 4)); HIPCHK(h, B[B_PJEND].ensure(std::max<u64>(J, 1) * 8));
+  HIPCHK(h, B[B_ENTGONE].ensure(std::max<u32>(A, 1)));   // (zeroed at the start of every pass: run_resident_once)
+  HIPCHK(h, B[B_HEAD].ensure((size_t)std::max<u32>(h->rlay.S, 1) * 4));
+  HIPCHK(h, B[B_RECNEXT].ensure(places * 4)); HIPCHK(h, B[B_RECORIG].ensure(places * 4)); HIPCHK(h, B[B_RECSLOT].ensure(places * 4));
+  HIPCHK(h, B[B_RECGONE].ensure(places));
+  // one block for: segment-tree pools | candidate lists | chosen lists | output counter | output pairs
+  const size_t pool_b = (size_t)h->rlay.P * pool_nodes * sizeof(PreNode), cand_b = (size_t)h->rlay.P * cand_cap * 4;
+  const size_t off_cand = align16(pool_b), off_chosen = off_cand + align16(cand_b), off_cnt = off_chosen + align16(cand_b), off_out = off_cnt + 16;
+  HIPCHK(h, B[B_MISC].ensure(off_out + (size_t)out_cap * 8));
+  char* misc = B[B_MISC].as<char>();
+  PreParams& Q = h->pre_params;
+  Q = PreParams{};
+  Q.enabled = 1; Q.num_qos = pre->num_qos;
+  Q.qp_off = B[B_QPOFF].as<u32>(); Q.qp = B[B_QP].as<u32>();
+  Q.pj_qos = B[B_PJQOS].as<u32>(); Q.pj_qprio = B[B_PJQP].as<u32>(); Q.pj_prio = B[B_PJPRIO].as<double>();
+  Q.pj_rec0 = B[B_PJREC0].as<u32>(); Q.pj_k = B[B_PJK].as<u32>(); Q.pj_end = B[B_PJEND].as<i64>();
+  Q.ent_gone = B[B_ENTGONE].as<uint8_t>();
+  if (int rc = bind_running(Q)) return rc;   // the running side: entry -> job and slot, per job its fields, end, mark and entries
+  Q.slot_head = B[B_HEAD].as<u32>(); Q.rec_next = B[B_RECNEXT].as<u32>(); Q.rec_orig = B[B_RECORIG].as<u32>();
+  Q.rec_slot = B[B_RECSLOT].as<u32>(); Q.rec_gone = B[B_RECGONE].as<uint8_t>();
+  Q.pool = misc; Q.pool_nodes = pool_nodes; Q.cand_cap = cand_cap;
+  Q.cand = (u32*)(misc + off_cand); Q.chosen = (u32*)(misc + off_chosen);
+  Q.out_cnt = (u32*)(misc + off_cnt); Q.out = (u32*)(misc + off_out); Q.out_cap = out_cap;
+  // CNS_PREEMPT_TREE=literal: TryPreempt_ on the node-for-node trees only (else: the fall-back of a call that runs out of compressed records)
+  { const char* tr = getenv("CNS_PREEMPT_TREE"); Q.literal_tree = (tr && !strcmp(tr, "literal")) ? 1u : ((tr && !strcmp(tr, "tiny")) ? 2u : 0u); }   // tiny: a handful of compressed records per call, the rest falls back
+  // the partitions that have a pending job whose qos may preempt: only they run on k_select's general path (run_resident_once)
+  h->pre_part.assign(h->rlay.P, 0);
+  for (u64 j = 0; j < J; ++j) {
+    const u32 q = pre->pd_qos[j];
+    if (j < h->q.job_part.size() && h->q.job_part[(size_t)j] != kNone && q < pre->num_qos && pre->qos_preempt_offsets[q + 1] > pre->qos_preempt_offsets[q])
+      h->pre_part[h->q.job_part[(size_t)j]] = 1;
+  }
+  h->pre_active = true;
+  setup_done();
+  int rc = cns_run_resident(h, now);
+  h->pre_active = false;
+  if (rc) return rc;
+  if (int rc3 = cns_download(h, out)) return rc3;
+  // ---- the preempted lists: (pending job, reference) pairs in push_back order per job -> CSR by job ------------------
+  u32 cnt = 0;
+  HIPCHK(h, hipMemcpy(&cnt, misc + off_cnt, 4, hipMemcpyDeviceToHost));
+  if (cnt > out_cap) return fail(h, CNS_ERR_UNSUPPORTED, who + ": more preemptions than the result buffer holds");
+  std::vector<u32> pairs((size_t)cnt * 2 + 2);
+  if (cnt) HIPCHK(h, hipMemcpy(pairs.data(), misc + off_out, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+  if (cnt > pout->capacity) return fail(h, CNS_ERR_INVALID_ARG, who + ": cns_preempt_out::capacity too small");
+  for (u64 j = 0; j <= J; ++j) pout->offsets[j] = 0;
+  for (u32 i = 0; i < cnt; ++i) pout->offsets[pairs[2 * i] + 1]++;
+  for (u64 j = 0; j < J; ++j) pout->offsets[j + 1] += pout->offsets[j];
+  {
+    std::vector<u64> cur(pout->offsets, pout->offsets + J);
+    for (u32 i = 0; i < cnt; ++i) pout->preempted[cur[pairs[2 * i]]++] = pairs[2 * i + 1];   // append order = push_back order within a job
+  }
+  // m_preempting_set_ / EnqueuePreemptCancel (:6786-6793), in queue order
+  std::set<u32> pset(set_in.begin(), set_in.end());
+  pout->num_cancelled = 0;
+  for (u64 j = 0; j < J; ++j)
+    for (u64 x = pout->offsets[j]; x < pout->offsets[j + 1]; ++x) {
+      const u32 ref = pout->preempted[x];
+      if (ref & CNS_PREEMPT_REF_PENDING) continue;
+      const u32 id = pre->rn_job_id[ref];
+      if (!pset.insert(id).second) continue;
+      if (pout->num_cancelled >= pout->cancel_capacity) return fail(h, CNS_ERR_INVALID_ARG, who + ": cancel_capacity too small");
+      pout->cancelled_job_ids[pout->num_cancelled++] = id;
+    }
+  pout->num_preempting = 0;
+  for (u32 id : pset) {
+    if (pout->num_preempting >= pout->preempting_capacity) return fail(h, CNS_ERR_INVALID_ARG, who + ": preempting_capacity too small");
+    pout->preempting_job_ids[pout->num_preempting++] = id;
+  }
+  return CNS_OK;
+}
+
 // include/crane_gpu/preempt.h.  TryPreempt_ (JobScheduler.cpp:6378-6505) releases resources inside a cycle, which the
 // pipelined kernels exclude by construction (node state monotone within a cycle: caches, predicted tiles, decoupled
 // commits).  A cycle with preemption enabled therefore runs k_select with every job on its general path
@@ -996,6 +1137,8 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
   if (h->rl_dev) return fail(h, CNS_ERR_STATE, "cns_select_preempt: the running tables were built on the device (cns_running_seed / cns_running_advance); hand the running set in with cns_set_running first");
   struct PreCall { cns_engine* h; ~PreCall() { h->pre_call = false; } } pre_call{h};   // (run_resident_once notes it: cns_probe refuses such a state)
   h->pre_call = true;
+  h->pre_t0 = std::chrono::steady_clock::now();
+  h->rp_timing = cns_running_preempt_timing{};
   const u64 J = jobs->num_jobs;
   const u32 R = h->run.R;
   if (J && (!pre->pd_qos || !pre->pd_qos_priority || !pre->pd_priority)) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: missing pending-job array");
@@ -1045,129 +1188,22 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
     }
   } restore_end{h, false};
   if (patched) { restore_end.armed = true; if (int rc = upload(h, h->d_rn_end, ent_end)) return rc; }
-  // No pending job's qos may preempt anything: TryPreempt_ returns at :6385 for every job, so the cycle is the plain one
-  // (with the preempting jobs ending at now + 1) and runs on the pipelined kernels.
-  bool any_list = false;
-  for (u64 j = 0; j < J && !any_list; ++j) {
-    const u32 q = pre->pd_qos[j];
-    any_list = q < pre->num_qos && pre->qos_preempt_offsets[q + 1] > pre->qos_preempt_offsets[q];
-  }
-  if (!any_list) {
-    int rc = cns_run_resident(h, now);
-    if (rc) return rc;
-    if (int rc3 = cns_download(h, out)) return rc3;
-    for (u64 j = 0; j <= J; ++j) pout->offsets[j] = 0;
-    pout->num_cancelled = 0;
-    pout->num_preempting = 0;
-    std::set<u32> keep(set_in.begin(), set_in.end());
-    for (u32 id : keep) {
-      if (pout->num_preempting >= pout->preempting_capacity) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: preempting_capacity too small");
-      pout->preempting_job_ids[pout->num_preempting++] = id;
-    }
-    return CNS_OK;
-  }
-  // qos preempt lists, pending-job fields (by queue index)
-  std::vector<u32> qp_off(pre->num_qos + 1, 0), qp;
-  for (u32 q = 0; q < pre->num_qos; ++q) {
-    for (u32 i = pre->qos_preempt_offsets[q]; i < pre->qos_preempt_offsets[q + 1]; ++i) qp.push_back(pre->qos_preempt[i]);
-    qp_off[q + 1] = (u32)qp.size();
-  }
-  if (qp.empty()) qp.push_back(0);
-  std::vector<u32> pj_qos(std::max<u64>(J, 1), 0), pj_qprio(std::max<u64>(J, 1), 0);
-  std::vector<double> pj_prio(std::max<u64>(J, 1), 0.0);
-  for (u64 j = 0; j < J; ++j) { pj_qos[j] = pre->pd_qos[j]; pj_qprio[j] = pre->pd_qos_priority[j]; pj_prio[j] = pre->pd_priority[j]; }
-  const u64 places = std::max<u64>(h->q.places, 1);
-  // work buffers per partition (documented in include/crane_gpu/preempt.h): candidate / chosen lists sized for every running
-  // job plus every pending job of the cycle (at most all of them hold resources on one job's nodes), bounded by 64 Mi entries
-  // over all partitions; segment-tree pools of 65 536 nodes.  Exceeding either is CNS_ERR_UNSUPPORTED, not a device fault.
-  const u32 pool_nodes = 1u << 16;
-  const u32 cand_cap = (u32)std::max<u64>(4096, std::min<u64>((u64)R + J + 1, (64ull << 20) / std::max<u32>(h->rlay.P, 1)));
-  const u32 out_cap = (u32)std::min<u64>(4 * (J + R) + 64, 1u << 28);
-  DevBuf* B = h->d_pre;
-  if (int rc = upload(h, B[B_QPOFF], qp_off)) return rc;
-  if (int rc = upload(h, B[B_QP], qp)) return rc;
-  if (int rc = upload(h, B[B_PJQOS], pj_qos)) return rc;
-  if (int rc = upload(h, B[B_PJQP], pj_qprio)) return rc;
-  if (int rc = upload(h, B[B_PJPRIO], pj_prio)) return rc;
-  HIPCHK(h, B[B_PJREC0].ensure(std::max<u64>(J, 1) * 4)); HIPCHK(h, B[B_PJK].ensure(std::max<u64>(J, 1) * 4)); HIPCHK(h, B[B_PJEND].ensure(std::max<u64>(J, 1) * 8));
-  if (int rc = upload_some(h, B[B_RNJOB], h->run.ent_job)) return rc;
-  if (int rc = upload_some(h, B[B_ENTSLOT], h->run.ent_slot)) return rc;
-  HIPCHK(h, B[B_ENTGONE].ensure(std::max<u32>(A, 1)));   // (zeroed at the start of every pass: run_resident_once)
-  if (int rc = upload(h, B[B_RJQOS], rj_qos)) return rc;
-  if (int rc = upload(h, B[B_RJQP], rj_qprio)) return rc;
-  if (int rc = upload(h, B[B_RJSTART], rj_start)) return rc;
-  if (int rc = upload(h, B[B_RJEND], rj_end)) return rc;
-  if (int rc = upload(h, B[B_RJPRE], rj_pre)) return rc;
-  if (int rc = upload(h, B[B_RJOFF], rj_off)) return rc;
-  if (int rc = upload(h, B[B_RJENT], rj_ent)) return rc;
-  HIPCHK(h, B[B_HEAD].ensure((size_t)std::max<u32>(h->rlay.S, 1) * 4));
-  HIPCHK(h, B[B_RECNEXT].ensure(places * 4)); HIPCHK(h, B[B_RECORIG].ensure(places * 4)); HIPCHK(h, B[B_RECSLOT].ensure(places * 4));
-  HIPCHK(h, B[B_RECGONE].ensure(places));
-  // one block for: segment-tree pools | candidate lists | chosen lists | output counter | output pairs
-  const size_t pool_b = (size_t)h->rlay.P * pool_nodes * sizeof(PreNode), cand_b = (size_t)h->rlay.P * cand_cap * 4;
-  const size_t off_cand = align16(pool_b), off_chosen = off_cand + align16(cand_b), off_cnt = off_chosen + align16(cand_b), off_out = off_cnt + 16;
-  HIPCHK(h, B[B_MISC].ensure(off_out + (size_t)out_cap * 8));
-  char* misc = B[B_MISC].as<char>();
-  PreParams& Q = h->pre_params;
-  Q = PreParams{};
-  Q.enabled = 1; Q.num_qos = pre->num_qos;
-  Q.qp_off = B[B_QPOFF].as<u32>(); Q.qp = B[B_QP].as<u32>();
-  Q.pj_qos = B[B_PJQOS].as<u32>(); Q.pj_qprio = B[B_PJQP].as<u32>(); Q.pj_prio = B[B_PJPRIO].as<double>();
-  Q.pj_rec0 = B[B_PJREC0].as<u32>(); Q.pj_k = B[B_PJK].as<u32>(); Q.pj_end = B[B_PJEND].as<i64>();
-  Q.rn_job = B[B_RNJOB].as<u32>(); Q.ent_slot = B[B_ENTSLOT].as<u32>(); Q.ent_gone = B[B_ENTGONE].as<uint8_t>();
-  Q.rj_qos = B[B_RJQOS].as<u32>(); Q.rj_qprio = B[B_RJQP].as<u32>(); Q.rj_start = B[B_RJSTART].as<i64>(); Q.rj_end = B[B_RJEND].as<i64>();
-  Q.rj_preempting = B[B_RJPRE].as<uint8_t>(); Q.rj_off = B[B_RJOFF].as<u32>(); Q.rj_ent = B[B_RJENT].as<u32>();
-  Q.slot_head = B[B_HEAD].as<u32>(); Q.rec_next = B[B_RECNEXT].as<u32>(); Q.rec_orig = B[B_RECORIG].as<u32>();
-  Q.rec_slot = B[B_RECSLOT].as<u32>(); Q.rec_gone = B[B_RECGONE].as<uint8_t>();
-  Q.pool = misc; Q.pool_nodes = pool_nodes; Q.cand_cap = cand_cap;
-  Q.cand = (u32*)(misc + off_cand); Q.chosen = (u32*)(misc + off_chosen);
-  Q.out_cnt = (u32*)(misc + off_cnt); Q.out = (u32*)(misc + off_out); Q.out_cap = out_cap;
-  // CNS_PREEMPT_TREE=literal: TryPreempt_ on the node-for-node trees only (else: the fall-back of a call that runs out of compressed records)
-  { const char* tr = getenv("CNS_PREEMPT_TREE"); Q.literal_tree = (tr && !strcmp(tr, "literal")) ? 1u : ((tr && !strcmp(tr, "tiny")) ? 2u : 0u); }   // tiny: a handful of compressed records per call, the rest falls back
-  // the partitions that have a pending job whose qos may preempt: only they run on k_select's general path (run_resident_once)
-  h->pre_part.assign(h->rlay.P, 0);
-  for (u64 j = 0; j < J; ++j) {
-    const u32 q = pre->pd_qos[j];
-    if (j < h->q.job_part.size() && h->q.job_part[(size_t)j] != kNone && q < pre->num_qos && pre->qos_preempt_offsets[q + 1] > pre->qos_preempt_offsets[q])
-      h->pre_part[h->q.job_part[(size_t)j]] = 1;
-  }
-  h->pre_active = true;
-  int rc = cns_run_resident(h, now);
-  h->pre_active = false;
-  if (rc) return rc;
-  if (int rc3 = cns_download(h, out)) return rc3;
-  // ---- the preempted lists: (pending job, reference) pairs in push_back order per job -> CSR by job ------------------
-  u32 cnt = 0;
-  HIPCHK(h, hipMemcpy(&cnt, misc + off_cnt, 4, hipMemcpyDeviceToHost));
-  if (cnt > out_cap) return fail(h, CNS_ERR_UNSUPPORTED, "cns_select_preempt: more preemptions than the result buffer holds");
-  std::vector<u32> pairs((size_t)cnt * 2 + 2);
-  if (cnt) HIPCHK(h, hipMemcpy(pairs.data(), misc + off_out, (size_t)cnt * 8, hipMemcpyDeviceToHost));
-  if (cnt > pout->capacity) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: cns_preempt_out::capacity too small");
-  for (u64 j = 0; j <= J; ++j) pout->offsets[j] = 0;
-  for (u32 i = 0; i < cnt; ++i) pout->offsets[pairs[2 * i] + 1]++;
-  for (u64 j = 0; j < J; ++j) pout->offsets[j + 1] += pout->offsets[j];
-  {
-    std::vector<u64> cur(pout->offsets, pout->offsets + J);
-    for (u32 i = 0; i < cnt; ++i) pout->preempted[cur[pairs[2 * i]]++] = pairs[2 * i + 1];   // append order = push_back order within a job
-  }
-  // m_preempting_set_ / EnqueuePreemptCancel (:6786-6793), in queue order
-  std::set<u32> pset(set_in.begin(), set_in.end());
-  pout->num_cancelled = 0;
-  for (u64 j = 0; j < J; ++j)
-    for (u64 x = pout->offsets[j]; x < pout->offsets[j + 1]; ++x) {
-      const u32 ref = pout->preempted[x];
-      if (ref & CNS_PREEMPT_REF_PENDING) continue;
-      const u32 id = pre->rn_job_id[ref];
-      if (!pset.insert(id).second) continue;
-      if (pout->num_cancelled >= pout->cancel_capacity) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: cancel_capacity too small");
-      pout->cancelled_job_ids[pout->num_cancelled++] = id;
-    }
-  pout->num_preempting = 0;
-  for (u32 id : pset) {
-    if (pout->num_preempting >= pout->preempting_capacity) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: preempting_capacity too small");
-    pout->preempting_job_ids[pout->num_preempting++] = id;
-  }
-  return CNS_OK;
+  return pre_cycle(h, now, jobs, pre, out, pout, R, A, set_in, "cns_select_preempt", [&](PreParams& Q) -> int {
+    DevBuf* B = h->d_pre;
+    if (int rc = upload_some(h, B[B_RNJOB], h->run.ent_job)) return rc;
+    if (int rc = upload_some(h, B[B_ENTSLOT], h->run.ent_slot)) return rc;
+    if (int rc = upload(h, B[B_RJQOS], rj_qos)) return rc;
+    if (int rc = upload(h, B[B_RJQP], rj_qprio)) return rc;
+    if (int rc = upload(h, B[B_RJSTART], rj_start)) return rc;
+    if (int rc = upload(h, B[B_RJEND], rj_end)) return rc;
+    if (int rc = upload(h, B[B_RJPRE], rj_pre)) return rc;
+    if (int rc = upload(h, B[B_RJOFF], rj_off)) return rc;
+    if (int rc = upload(h, B[B_RJENT], rj_ent)) return rc;
+    Q.rn_job = B[B_RNJOB].as<u32>(); Q.ent_slot = B[B_ENTSLOT].as<u32>();
+    Q.rj_qos = B[B_RJQOS].as<u32>(); Q.rj_qprio = B[B_RJQP].as<u32>(); Q.rj_start = B[B_RJSTART].as<i64>(); Q.rj_end = B[B_RJEND].as<i64>();
+    Q.rj_preempting = B[B_RJPRE].as<uint8_t>(); Q.rj_off = B[B_RJOFF].as<u32>(); Q.rj_ent = B[B_RJENT].as<u32>();
+    return 0;
+  });
 }
 
 int cns_get_partition_status(const cns_handle* h, uint8_t* status, uint32_t capacity) {
@@ -1275,6 +1311,7 @@ int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity
 #include "usage_host.inc"
 #include "gate_host.inc"
 #include "running_host.inc"
+#include "running_preempt_host.inc"
 
 }  // extern "C"
 

@@ -97,6 +97,7 @@ static int run_rebuild(cns_handle* h, int first, u32 R, u32 A, u32* pairs, bool*
   HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   *pairs = M; *over_cap = flag != 0;
+  h->rl_sorted_side = kin == B[RL_K0].as<u64>() ? 0 : 1;   // (run_commit keeps that side for cns_running_select_preempt)
   return 0;
 }
 
@@ -107,6 +108,10 @@ static int run_commit(cns_handle* h, u32 R, u32 A, u32 M) {
   DevBuf* B = h->d_rl;
   for (int k = 0; k < 6; ++k) run_swap(B[RL_ID + k], B[RL_WID + k]);
   run_swap(h->d_rn_off, B[RL_RNOFF]); run_swap(h->d_rn_end, B[RL_RNEND]); run_swap(h->d_rn_res, B[RL_RNRES]);
+  // the sorted (slot, allocation) pairs these tables came from stay alive beside them: position d of the pairs is entry d of the tables
+  // (running_preempt_host.inc builds the index of a cycle with preemption from them; a later call that fails writes other buffers)
+  run_swap(h->d_rp[RP_KEYS], B[RL_K0 + h->rl_sorted_side]); run_swap(h->d_rp[RP_VALS], B[RL_V0 + h->rl_sorted_side]);
+  h->rl_M = M; h->rp_index = h->rp_call = false;
   (void)cns_snapshot::build_running(h->lay, h->rlay, nullptr, h->run);   // (no host copy of the entries: cns_select_preempt is refused)
   h->rl_have = h->rl_dev = true;
   h->rl_R = R; h->rl_A = A; h->rl_N = h->lay.N;
@@ -238,11 +243,12 @@ int cns_running_advance(cns_handle* h, const cns_running_step* in, const cns_run
   run_drop_if_stale(h);
   cns_running::Facts F;
   F.have_ledger = h->rl_have && h->have_nodes;
-  F.have_cycle = h->have_run; F.preempt_cycle = h->run_preempt;
+  F.have_cycle = h->have_run; F.preempt_cycle = h->run_preempt && !h->run_preempt_rl;   // (served behind cns_running_select_preempt: the caller's mask decides)
   F.cycle_jobs = h->q.J; F.cycle_now = h->last_now; F.cycle_places = h->q.places;
   F.ledger_jobs = h->rl_R; F.ledger_allocs = h->rl_A;
   std::vector<u32> sorted_ids, order;
   if (const auto v = cns_running::check_step(F, in, out, &sorted_ids, &order)) return fail(h, v.code, v.msg);
+  if (const auto v = cns_running::check_step_after_preempt(h->have_run && h->run_preempt_rl, in)) return fail(h, v.code, v.msg);
   const int rc = advance_impl(h, in, out, sorted_ids, order);
   if (rc != 0) drain(h);   // nothing of the call is left in flight, the message survives
   return rc;

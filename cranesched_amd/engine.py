@@ -57,6 +57,8 @@ USAGE_ABI_SYMBOLS = ("cns_usage_set_tables", "cns_usage_apply", "cns_usage_get_t
 GATE_ABI_SYMBOLS = ("cns_gate_pending", "cns_gate_shape")
 # ... and include/crane_gpu_running/running.h
 RUNNING_ABI_SYMBOLS = ("cns_running_seed", "cns_running_advance", "cns_running_get", "cns_running_get_timing", "cns_running_shape")
+# ... and include/crane_gpu_running/running_preempt.h
+RUNNING_PREEMPT_ABI_SYMBOLS = ("cns_running_select_preempt", "cns_debug_get_preempt_index", "cns_running_preempt_get_timing")
 LIMITS_ABI_SYMBOLS = ("cns_set_run_limits", "cns_apply_run_limits", "cns_upload_limit_jobs", "cns_run_limits_resident",
                       "cns_download_limits", "cns_get_limit_timing", "cns_get_usage", "cns_limits_shape")
 
@@ -648,6 +650,44 @@ class GpuNodeSelector:
         v = [C.c_uint32(0) for _ in range(4)]
         self._check(self._L.cns_running_shape(*[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    # -- a cycle with preemption on that set (include/crane_gpu_running/running_preempt.h) ---------------------------------------
+    def node_select_preempt_resident(self, now: int, jobs: abi.Jobs, preempt: "abi.Preempt"):
+        """node_select_preempt for a handle whose running tables were built by seed_running / advance_running; -> (Placements,
+        PreemptOut).  LEDGER ORDER: running job index r is ledger row r, so preempt.rn_job_id / rn_qos / rn_qos_priority / rn_start_sec
+        are in the ledger's order (seed order, stable erase, admitted jobs appended in queue order; running_ledger() reports it), and a
+        reference without bit 31 in the preempted lists is a ledger row.  rn_job_id is checked against the ledger on the device.
+        advance_running behind it needs its admit mask."""
+        out = abi.Placements(jobs.num_jobs, jobs.total_places())
+        pout = abi.PreemptOut(jobs.num_jobs, len(preempt.rn_job_id))
+        cj, co, cp, cpo = jobs.to_c(), out.to_c(), preempt.to_c(), pout.to_c()
+        self._check(self._L.cns_running_select_preempt(self._h, C.c_int64(now), C.byref(cj), C.byref(cp), C.byref(co), C.byref(cpo)))
+        self._jobs = jobs
+        return out, pout
+
+    def preempt_index(self) -> dict:
+        """The index the last node_select_preempt_resident ran on, as built on the device: ent_job, ent_slot, ent_end (the patched per-slot
+        end times) per entry; rj_off [rows + 1], rj_ent per entry, rj_end and rj_preempting per ledger row."""
+        ne, nr = np.zeros(1, np.uint64), np.zeros(1, np.uint64)
+        o = abi.CnsPreemptIndexOut()
+        o.num_entries, o.num_rows = abi._ptr(ne), abi._ptr(nr)
+        self._check(self._L.cns_debug_get_preempt_index(self._h, C.byref(o)))
+        m, r = int(ne[0]), int(nr[0])
+        a = {"ent_job": np.zeros(max(m, 1), np.uint32), "ent_slot": np.zeros(max(m, 1), np.uint32), "ent_end": np.zeros(max(m, 1), np.int64),
+             "rj_off": np.zeros(r + 1, np.uint32), "rj_ent": np.zeros(max(m, 1), np.uint32), "rj_end": np.zeros(max(r, 1), np.int64),
+             "rj_preempting": np.zeros(max(r, 1), np.uint8)}
+        o.capacity_entries, o.capacity_rows = m, r
+        for f, v in a.items():
+            setattr(o, f, abi._ptr(v))
+        self._check(self._L.cns_debug_get_preempt_index(self._h, C.byref(o)))
+        return {f: v[:(r + 1 if f == "rj_off" else r if f in ("rj_end", "rj_preempting") else m)] for f, v in a.items()}
+
+    def preempt_setup_timing(self) -> dict:
+        """What the last cycle with preemption (either call) spent in front of its cycle: setup_ms on the host clock, index_ms / mark_ms on
+        the device (node_select_preempt_resident only)."""
+        t = abi.CnsRunningPreemptTiming()
+        self._check(self._L.cns_running_preempt_get_timing(self._h, C.byref(t)))
+        return {f: getattr(t, f) for f, _ in abi.CnsRunningPreemptTiming._fields_}
 
     def device_results(self):
         p, n = C.c_void_p(), C.c_uint64()

@@ -25,6 +25,7 @@
 #include "../../include/crane_gpu_gate/pending_gate.h"
 #include "../../include/crane_gpu_usage/usage.h"
 #include "../../include/crane_gpu_running/running.h"
+#include "../../include/crane_gpu_running/running_preempt.h"
 
 namespace crane {
 
@@ -89,6 +90,8 @@ struct GpuNodeSelectionAlgo::Impl {
   // the running set kept on the device (include/crane_gpu_running/running.h): on; the per-slot tables must be rebuilt from the ledger
   // before the next cycle (a snapshot was pushed since); the `now` of the last cycle
   bool resident_running = false, resident_stale = false;
+  std::vector<job_id_t> ledger_ids;                                 // the device ledger's rows, in ledger order (SeedRunning / AdvanceRunning keep it)
+  bool ledger_ids_valid = false;
   int64_t last_now = 0;
   bool resvq_stale = true;   // the engine's per-node tables of the reservation what-ifs are older than the packed running set / the snapshot
   std::vector<const PdJobInScheduler*> last_ord;                      // the jobs of the last cns_select, in its order
@@ -1149,6 +1152,8 @@ bool GpuNodeSelectionAlgo::SeedRunning(const std::vector<std::unique_ptr<RnJobIn
   const int st = cns_running_seed(I.h, rs.num_jobs ? &rs : nullptr, ids.data());
   if (st != 0) return fail(st, cns_last_error(I.h));
   I.resident_stale = false;
+  I.ledger_ids.assign(ids.begin(), ids.end() - 1);   // seed order
+  I.ledger_ids_valid = true;
   status_ = 0; error_.clear();
   return true;
 }
@@ -1184,6 +1189,15 @@ bool GpuNodeSelectionAlgo::AdvanceRunning(const std::vector<job_id_t>& finished_
   const int st = cns_running_advance(I.h, &in, &out);
   if (st != 0) return fail(st, cns_last_error(I.h));
   I.resident_stale = false;
+  if (I.ledger_ids_valid) {   // the ledger's order on this side: a stable erase, then the admitted jobs in queue order
+    std::unordered_set<job_id_t> gone;
+    for (size_t i = 0; i < ret.size(); ++i) if (found[i]) gone.insert(ret[i]);
+    if (!gone.empty()) I.ledger_ids.erase(std::remove_if(I.ledger_ids.begin(), I.ledger_ids.end(), [&](job_id_t id) { return gone.count(id) != 0; }), I.ledger_ids.end());
+    uint64_t appended = 0;
+    for (size_t j = 0; j < mask.size(); ++j)   // (the device's own test: admit[j], reason none, starts now)
+      if (mask[j] && I.last.reason[j] == CNS_REASON_NONE && I.last.start[j] == I.last_now) { I.ledger_ids.push_back(ids[j]); ++appended; }
+    if (appended != nadm) I.ledger_ids_valid = false;   // (a cycle with preemption is refused until the next SeedRunning)
+  }
   if (num_retired) *num_retired = nret;
   if (num_admitted) *num_admitted = nadm;
   status_ = 0; error_.clear();
@@ -1239,7 +1253,6 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
   int st = 0;
   if (I.resident_running) {   // the cycle runs on the device ledger: nothing of the running set is handed in
     if (I.grp) return fail_all(CNS_ERR_UNSUPPORTED, "resident running on an algorithm object over several devices");
-    if (I.preempt_enabled) return fail_all(CNS_ERR_STATE, "preemption needs the running jobs themselves: turn resident running off (UseResidentRunning(false)) for such a snapshot");
     if (I.resident_stale) {   // a snapshot was pushed since the last boundary: the per-slot tables again, from the ledger
       const cns_running_step none{};
       st = cns_running_advance(I.h, &none, nullptr);
@@ -1292,14 +1305,32 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
     return fail_all(CNS_ERR_UNSUPPORTED, "a cycle with preemption runs on ONE device (TryPreempt_ releases resources inside the cycle: csrc/preempt_dev.inc): build the algorithm over one device for it");
   } else {
     // ---- the cycle with preemption (include/crane_gpu/preempt.h): qos ids, the fields TryPreempt_ reads, the set ------
-    if (!I.r_src_valid || I.r_src.size() != I.r_end.size())
-      return fail_all(CNS_ERR_STATE, "preemption needs the running jobs themselves: call NodeSelect(now, running_jobs, pending_jobs)");
-    const uint32_t R = (uint32_t)I.r_src.size();
+    // running job index r: the packed running set's, or — on the device ledger (include/crane_gpu_running/running_preempt.h) — ledger
+    // row r: the caller's running jobs looked up by the ids SeedRunning / AdvanceRunning kept in ledger order
+    std::vector<RnJobInScheduler*> by_row;
+    if (I.resident_running) {
+      if (!I.ledger_ids_valid) return fail_all(CNS_ERR_STATE, "preemption on the device ledger needs its id order: call SeedRunning first");
+      std::unordered_map<job_id_t, RnJobInScheduler*> by_id;
+      by_id.reserve(running_jobs.size());
+      for (const auto& rn : running_jobs) by_id.emplace(rn->job_id, rn.get());
+      by_row.reserve(I.ledger_ids.size());
+      for (job_id_t id : I.ledger_ids) {
+        auto it = by_id.find(id);
+        if (it == by_id.end())
+          return fail_all(CNS_ERR_STATE, "preemption needs the running jobs themselves: job " + std::to_string(id) + " of the device ledger is not in running_jobs (call NodeSelect(now, running_jobs, pending_jobs))");
+        by_row.push_back(it->second);
+      }
+    } else {
+      if (!I.r_src_valid || I.r_src.size() != I.r_end.size())
+        return fail_all(CNS_ERR_STATE, "preemption needs the running jobs themselves: call NodeSelect(now, running_jobs, pending_jobs)");
+    }
+    const std::vector<RnJobInScheduler*>& rsrc = I.resident_running ? by_row : I.r_src;
+    const uint32_t R = (uint32_t)rsrc.size();
     std::vector<uint32_t> pj_id(J + 1), pj_qos(J + 1), pj_qp(J + 1), rj_id(R + 1), rj_qos(R + 1), rj_qp(R + 1), pset;
     std::vector<double> pj_prio(J + 1);
     std::vector<int64_t> rj_start(R + 1);
     for (size_t j = 0; j < J; ++j) { pj_id[j] = ord[j]->job_id; pj_qos[j] = I.qos_of(ord[j]->qos); pj_qp[j] = ord[j]->qos_priority; pj_prio[j] = ord[j]->priority; }
-    for (uint32_t r = 0; r < R; ++r) { rj_id[r] = I.r_src[r]->job_id; rj_qos[r] = I.qos_of(I.r_src[r]->qos); rj_qp[r] = I.r_src[r]->qos_priority; rj_start[r] = I.r_src[r]->start_time; }
+    for (uint32_t r = 0; r < R; ++r) { rj_id[r] = rsrc[r]->job_id; rj_qos[r] = I.qos_of(rsrc[r]->qos); rj_qp[r] = rsrc[r]->qos_priority; rj_start[r] = rsrc[r]->start_time; }
     for (job_id_t id : I.preempting) pset.push_back(id);
     std::vector<uint32_t> qoff(I.qos_preempt.size() + 1, 0), qflat;
     for (size_t q = 0; q < I.qos_preempt.size(); ++q) { for (uint32_t x : I.qos_preempt[q]) qflat.push_back(x); qoff[q + 1] = (uint32_t)qflat.size(); }
@@ -1317,13 +1348,13 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
     po.capacity = po_refs.size(); po.offsets = po_off.data(); po.preempted = po_refs.data();
     po.cancel_capacity = (uint32_t)po_cancel.size(); po.cancelled_job_ids = po_cancel.data();
     po.preempting_capacity = (uint32_t)po_set.size(); po.preempting_job_ids = po_set.data();
-    st = cns_select_preempt(I.h, now, &js, &ps, &out, &po);
+    st = I.resident_running ? cns_running_select_preempt(I.h, now, &js, &ps, &out, &po) : cns_select_preempt(I.h, now, &js, &ps, &out, &po);
     if (st != 0) return fail_all(st, cns_last_error(I.h));
     for (size_t j = 0; j < J; ++j)
       for (uint64_t x = po_off[j]; x < po_off[j + 1]; ++x) {
         const uint32_t ref = po_refs[x];
         if (ref & CNS_PREEMPT_REF_PENDING) ord[j]->preempted_jobs.emplace_back(ord[ref & 0x7FFFFFFFu]);
-        else ord[j]->preempted_jobs.emplace_back(I.r_src[ref]);
+        else ord[j]->preempted_jobs.emplace_back(rsrc[ref]);
       }
     I.cancelled.assign(po_cancel.begin(), po_cancel.begin() + po.num_cancelled);
     I.cc_pre_off = po_off;

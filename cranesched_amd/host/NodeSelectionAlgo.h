@@ -612,8 +612,12 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   //                                                      1575-1628): their placements are read on the device.  `admitted` names them
   //                                                      by pointer, in any order; a job the cycle did not start now never enters.
   // A new snapshot (SetClusterSnapshot, a craned state flip) keeps the ledger while the node count stays; the next NodeSelect rebuilds
-  // the per-slot tables from it first.  Default: off — NodeSelect hands the running set in as before.  One device only; a cycle with
-  // preemption needs the running jobs themselves and is refused while this is on.
+  // the per-slot tables from it first.  Default: off — NodeSelect hands the running set in as before.  One device only.
+  // A cycle with preemption (a snapshot with preempt_enabled) runs on the ledger too (include/crane_gpu_running/running_preempt.h): the
+  // adapter keeps the ledger's id order from SeedRunning / AdvanceRunning, looks every row's RnJobInScheduler up by id in running_jobs
+  // (a row that is not there fails the cycle) and hands qos, qos_priority and start_time in in ledger order; the preempted lists point
+  // at the caller's own objects.  AdvanceRunning behind such a cycle takes `admitted` as the jobs the commit loop really started: a job
+  // that preempted a running job is held back by it ("Waiting for Preemption", JobScheduler.cpp:1542-1555) and must not be named.
   void UseResidentRunning(bool on);
   bool ResidentRunning() const;
   bool SeedRunning(const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs);

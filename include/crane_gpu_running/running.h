@@ -38,6 +38,11 @@
  *           array the cycle's cns_job_soa carried — the caller's contract, as in cns_commit_check), and one allocation per placement
  *           record whose node_idx != CNS_NODE_NONE, in record order.  out->num_admitted: rows appended.
  *           The ids of the admitted rows must be distinct and absent from the ledger: the caller's contract, NOT checked.
+ *           After a successful cns_running_select_preempt (running_preempt.h) with preemption enabled the admit step IS served, and
+ *           in->admit is required (NULL: CNS_ERR_INVALID_ARG): a job that preempted a running job has reason none and start == now,
+ *           and the reference's commit loop holds it back ("Waiting for Preemption", JobScheduler.cpp:1542-1555, cns_commit_check's
+ *           code) — only the caller's mask says whether it started.  A pending job preempted inside the cycle carries
+ *           CNS_REASON_PREEMPTED and is never admitted.
  *   REBUILD the per-slot running tables from the new ledger against the handle's CURRENT layout: an allocation outside a reservation
  *           counts on every slot of its node (none for an unschedulable node, JobScheduler.cpp:6685-6686), one inside a reservation on
  *           that reservation's virtual node (none for an unknown reservation or one that does not list the node, :6693-6700).
@@ -51,7 +56,8 @@
  *
  * cns_running_get downloads the ledger (every pointer optional).  A later cns_set_running replaces the per-slot tables as ever and
  * drops the ledger.  cns_select_preempt after the tables were built here returns CNS_ERR_STATE (call cns_set_running first): its
- * setup reads the host copy of the running set, which this path does not fill.  Never a device fault: every index a kernel follows is
+ * setup reads the host copy of the running set, which this path does not fill; cns_running_select_preempt (running_preempt.h) is that
+ * cycle on the ledger.  Never a device fault: every index a kernel follows is
  * validated on the host or bounded in the kernel.  No kernel of these calls waits for another workgroup.  Single device only (not
  * served through cns_group_*).  cns_probe, cns_commit_check, cns_usage_apply before or after behave exactly as without these calls.
  * Ownership, errors, threading: as in node_select.h.  There is no CPU fallback.
