@@ -855,6 +855,41 @@ class CnsRunningPreemptTiming(C.Structure):
                 ("index_built", C.c_uint32), ("reserved0", C.c_uint32)]
 
 
+# include/crane_gpu_running/running_attrs.h
+class CnsRunningAttrs(C.Structure):
+    _fields_ = [(f, _P) for f in ("start_sec", "qos", "qos_priority", "partition_priority", "account")]
+
+
+class CnsRunningAttrsOut(C.Structure):
+    _fields_ = [("capacity_jobs", C.c_uint64), ("num_jobs", _P)] + \
+               [(f, _P) for f in ("start_sec", "qos", "qos_priority", "partition_priority", "account", "node_num", "alloc_cpu_raw", "alloc_mem")]
+
+
+@dataclass
+class RunningAttrs:
+    """cns_running_attrs: the per-job attributes beside the device ledger, one value per row (a seed) or per queue job (an advance,
+    where start_sec is not read and may be left out)."""
+    qos: np.ndarray
+    qos_priority: np.ndarray
+    partition_priority: np.ndarray
+    account: np.ndarray
+    start_sec: np.ndarray = None
+
+    def __post_init__(self):
+        self.qos = _arr(self.qos, np.uint32); n = len(self.qos)
+        self.qos_priority = _arr(self.qos_priority, np.uint32, n)
+        self.partition_priority = _arr(self.partition_priority, np.uint32, n)
+        self.account = _arr(self.account, np.uint32, n)
+        if self.start_sec is not None:
+            self.start_sec = _arr(self.start_sec, np.int64, n)
+
+    def __len__(self):
+        return len(self.qos)
+
+    def to_c(self) -> CnsRunningAttrs:
+        return CnsRunningAttrs(*[_ptr(getattr(self, f)) for f, _ in CnsRunningAttrs._fields_])
+
+
 def _csr(lists):
     off = np.zeros(len(lists) + 1, np.uint64)
     off[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64) if len(lists) else []

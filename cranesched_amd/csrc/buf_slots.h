@@ -74,6 +74,14 @@ enum { RL_ID = 0, RL_END, RL_RESV, RL_OFF, RL_NODE, RL_RES,                     
 enum { RP_KEYS = 0, RP_VALS, RP_ENTJOB, RP_ENTSLOT, RP_K0, RP_K1, RP_V0, RP_V1, RP_HIST, RP_RJOFF, RP_RJENT,   // per rebuild
        RP_GIVEN, RP_SET, RP_FOUND, RP_FLAG, RP_RJPRE, RP_RJEND, RP_ENTEND, RP_COUNT };                         // per call
 
+// cns_engine::d_ra (running_host.inc, running_attrs_host.inc): the attribute columns beside the ledger, the call's copy of them, what a
+// cycle boundary needs to carry them, the per-row sums, the running side of cns_priority_order_resident
+enum { RA_START = 0, RA_QOS, RA_QPRIO, RA_PART, RA_ACCT,                                                    // the columns
+       RA_WSTART, RA_WQOS, RA_WQPRIO, RA_WPART, RA_WACCT,                                                   // the call's copy of them
+       RA_ORIGIN, RA_QQOS, RA_QQPRIO, RA_QPART, RA_QACCT,                                                   // a cycle boundary: where a row came from, the queue's attributes
+       RA_NODENUM, RA_CPU, RA_MEM, RA_SUMFLAG,                                                              // per ledger state: the sums, their flag words
+       RA_FLAG, RA_K0, RA_K1, RA_V0, RA_V1, RA_HIST, RA_PICK, RA_PICKED, RA_COUNT };                        // per call
+
 // cns_engine::d_pre (engine.hip: a cycle with preemption)
 enum { B_QPOFF, B_QP, B_PJQOS, B_PJQP, B_PJPRIO, B_PJREC0, B_PJK, B_PJEND, B_RNJOB, B_ENTSLOT, B_ENTGONE, B_RJQOS, B_RJQP,
        B_RJSTART, B_RJEND, B_RJPRE, B_RJOFF, B_RJENT, B_HEAD, B_RECNEXT, B_RECORIG, B_RECSLOT, B_RECGONE, B_MISC, B_COUNT };

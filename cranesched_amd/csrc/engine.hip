@@ -32,6 +32,7 @@
 #include "../../include/crane_gpu_usage/usage.h"
 #include "../../include/crane_gpu_running/running.h"
 #include "../../include/crane_gpu_running/running_preempt.h"
+#include "../../include/crane_gpu_running/running_attrs.h"
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
 #include <limits>
@@ -51,6 +52,7 @@
 #include "gate_kernels.inc"   // the dependency-event drain and Phase 1 in front of a cycle (include/crane_gpu_gate/pending_gate.h)
 #include "running_kernels.inc" // the running set kept on the device between two cycles: retire, admit, rebuild (include/crane_gpu_running/running.h)
 #include "running_preempt_kernels.inc" // a cycle with preemption on that set: the entry index, the job -> entries CSR, the marks and the end patch (include/crane_gpu_running/running_preempt.h)
+#include "running_attrs_kernels.inc" // the attribute columns beside that set, the per-row sums and the running side of the sorter taken from them (include/crane_gpu_running/running_attrs.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 #include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
 #include "csr_host.inc"        // the CSR rules of the callers' lists: offsets, sorted lists without a repeat (no HIP in there either)
@@ -59,6 +61,7 @@
 #include "usage_check_host.inc" // the input rules of cns_usage_set_tables / cns_usage_apply (no HIP in there either)
 #include "running_check_host.inc" // the input rules of cns_running_seed / cns_running_advance (no HIP in there either)
 #include "running_preempt_check_host.inc" // the input rules of cns_running_select_preempt (no HIP in there either)
+#include "running_attrs_check_host.inc" // the input rules of the calls of running_attrs.h (no HIP in there either)
 #include "sort_host.inc"       // the arithmetic of the pair sort: passes, tiles, histogram bytes (no HIP in there either)
 #include "resvq_passes.inc"    // the radix passes over the segment numbers of cns_resvq_run's sort (no HIP in there either)
 #include "buf_slots.h"         // the slots of cns_engine's per-feature buffer sets
@@ -260,6 +263,11 @@ struct cns_engine {
   std::chrono::steady_clock::time_point pre_t0{};   // entry of the last cns_select_preempt / cns_running_select_preempt with preemption enabled
   cns_running_preempt_timing rp_timing{};       // ... what it spent in front of its cycle
   const i64* rn_end_bound = nullptr;            // the per-slot end times of the next run when they are not d_rn_end (the patched copy of such a call)
+  // the attribute columns beside the ledger (running_attrs_host.inc): two copies, what a cycle boundary needs to carry them, the
+  // per-row sums and the running side of cns_priority_order_resident
+  DevBuf d_ra[RA_COUNT];
+  bool ra_have = false;                         // the ledger carries columns (a plain seed / advance and whatever drops the ledger drop them)
+  bool ra_sums = false;                         // RA_NODENUM, RA_CPU, RA_MEM, RA_SUMFLAG describe the current ledger
 };
 
 namespace {
@@ -737,6 +745,7 @@ int cns_set_running(cns_handle* h, const cns_running_soa* rn) {
   if (const cns_snapshot::Status st = cns_snapshot::build_running(h->lay, h->rlay, rn, run)) return fail(h, st.code, st.msg);
   h->run = std::move(run);
   h->rl_have = h->rl_dev = false; h->rp_index = h->rp_call = false;   // (the ledger of cns_running_seed describes another set now)
+  h->ra_have = h->ra_sums = false;
   if (int rc = upload_running(h)) return rc;
   h->have_run = false;
   return CNS_OK;
@@ -991,8 +1000,11 @@ int cns_select(cns_handle* h, int64_t now, const cns_job_soa* jobs, cns_placemen
 // The cycle of cns_select_preempt / cns_running_select_preempt behind their setup of the running side: the queue is uploaded, the
 // end times of the preempting rows are bound.  R running jobs, A entries of the per-slot tables, set_in: the ids of the preempting set
 // that still run.  bind_running puts the running side's tables on the device and names them in the parameter block.
+// row_ids: the job ids of the preempted running jobs when the caller handed no rn_job_id in (cns_running_select_preempt_attrs).
+using PreRowIds = std::function<int(const std::vector<u32>& rows, std::vector<u32>& ids)>;
 static int pre_cycle(cns_handle* h, int64_t now, const cns_job_soa* jobs, const cns_preempt_soa* pre, cns_placement_soa* out, cns_preempt_out* pout,
-                     const u32 R, const u32 A, const std::vector<u32>& set_in, const std::string& who, const std::function<int(PreParams&)>& bind_running) {
+                     const u32 R, const u32 A, const std::vector<u32>& set_in, const std::string& who, const std::function<int(PreParams&)>& bind_running,
+                     const PreRowIds* row_ids = nullptr) {
   const u64 J = jobs->num_jobs;
   // No pending job's qos may preempt anything: TryPreempt_ returns at :6385 for every job, so the cycle is the plain one
   // (with the preempting jobs ending at now + 1) and runs on the pipelined kernels.
@@ -1095,11 +1107,19 @@ static int pre_cycle(cns_handle* h, int64_t now, const cns_job_soa* jobs, const 
   // m_preempting_set_ / EnqueuePreemptCancel (:6786-6793), in queue order
   std::set<u32> pset(set_in.begin(), set_in.end());
   pout->num_cancelled = 0;
+  std::vector<u32> picked_ids;   // with row_ids: the ids of the running references, in the order the loop below meets them
+  if (row_ids) {
+    std::vector<u32> rows;
+    for (u64 x = 0; x < pout->offsets[J]; ++x)
+      if (!(pout->preempted[x] & CNS_PREEMPT_REF_PENDING)) rows.push_back(pout->preempted[x]);
+    if (int rc4 = (*row_ids)(rows, picked_ids)) return rc4;
+  }
+  size_t met = 0;
   for (u64 j = 0; j < J; ++j)
     for (u64 x = pout->offsets[j]; x < pout->offsets[j + 1]; ++x) {
       const u32 ref = pout->preempted[x];
       if (ref & CNS_PREEMPT_REF_PENDING) continue;
-      const u32 id = pre->rn_job_id[ref];
+      const u32 id = row_ids ? picked_ids[met++] : pre->rn_job_id[ref];
       if (!pset.insert(id).second) continue;
       if (pout->num_cancelled >= pout->cancel_capacity) return fail(h, CNS_ERR_INVALID_ARG, who + ": cancel_capacity too small");
       pout->cancelled_job_ids[pout->num_cancelled++] = id;
@@ -1312,6 +1332,7 @@ int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity
 #include "gate_host.inc"
 #include "running_host.inc"
 #include "running_preempt_host.inc"
+#include "running_attrs_host.inc"
 
 }  // extern "C"
 

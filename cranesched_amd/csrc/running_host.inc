@@ -10,12 +10,30 @@ static void run_swap(DevBuf& a, DevBuf& b) { std::swap(a.p, b.p); std::swap(a.ca
 
 // a changed num_nodes drops the ledger: its node indices name another cluster
 static void run_drop_if_stale(cns_handle* h) {
-  if (h->rl_have && h->rl_N != h->lay.N) h->rl_have = false;
+  if (h->rl_have && h->rl_N != h->lay.N) h->rl_have = h->ra_have = h->ra_sums = false;
 }
 
 static RunLedger run_ledger(cns_handle* h, int first) {
   DevBuf* B = h->d_rl + first;
   return RunLedger{B[0].as<u32>(), B[1].as<i64>(), B[2].as<u32>(), B[3].as<u32>(), B[4].as<u32>(), B[5].as<Res>()};
+}
+
+// The attribute columns beside the ledger (include/crane_gpu_running/running_attrs.h; the calls: running_attrs_host.inc).  A seed or an
+// advance that carries them writes the copy at d_ra[RA_WSTART..] and swaps it in behind run_commit, which by itself leaves a ledger
+// without columns: that is what a plain call does.
+static RaCols ra_cols(cns_handle* h, int first) {
+  DevBuf* B = h->d_ra + first;
+  return RaCols{B[0].as<i64>(), B[1].as<u32>(), B[2].as<u32>(), B[3].as<u32>(), B[4].as<u32>()};
+}
+static int ra_ensure_copy(cns_handle* h, u32 rows) {
+  DevBuf* B = h->d_ra;
+  HIPCHK(h, B[RA_WSTART].ensure((size_t)rows * 8));
+  for (int k = RA_WQOS; k <= RA_WACCT; ++k) HIPCHK(h, B[k].ensure((size_t)rows * 4));
+  return 0;
+}
+static void ra_commit(cns_handle* h) {
+  for (int k = 0; k < 5; ++k) run_swap(h->d_ra[RA_START + k], h->d_ra[RA_WSTART + k]);
+  h->ra_have = true;
 }
 
 // Layout::node_slots as a CSR on the device: derived again only when a snapshot was uploaded since
@@ -112,6 +130,7 @@ static int run_commit(cns_handle* h, u32 R, u32 A, u32 M) {
   // (running_preempt_host.inc builds the index of a cycle with preemption from them; a later call that fails writes other buffers)
   run_swap(h->d_rp[RP_KEYS], B[RL_K0 + h->rl_sorted_side]); run_swap(h->d_rp[RP_VALS], B[RL_V0 + h->rl_sorted_side]);
   h->rl_M = M; h->rp_index = h->rp_call = false;
+  h->ra_have = h->ra_sums = false;   // (the caller that carried the columns swaps them in behind this)
   (void)cns_snapshot::build_running(h->lay, h->rlay, nullptr, h->run);   // (no host copy of the entries: cns_select_preempt is refused)
   h->rl_have = h->rl_dev = true;
   h->rl_R = R; h->rl_A = A; h->rl_N = h->lay.N;
@@ -124,7 +143,7 @@ static int run_commit(cns_handle* h, u32 R, u32 A, u32 M) {
   return CNS_OK;
 }
 
-static int seed_impl(cns_handle* h, const cns_running_soa* rn, const uint32_t* job_ids, u32 R, u32 A) {
+static int seed_impl(cns_handle* h, const cns_running_soa* rn, const uint32_t* job_ids, u32 R, u32 A, const cns_running_attrs* attrs = nullptr, bool with_attrs = false) {
   HIPCHK(h, hipSetDevice(h->device));
   DevBuf* B = h->d_rl;
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
@@ -139,12 +158,22 @@ static int seed_impl(cns_handle* h, const cns_running_soa* rn, const uint32_t* j
   if (int rc = stage(h, B[RL_WOFF], R ? rn->alloc_offsets : &zero, ((size_t)R + 1) * 4)) return rc;
   if (int rc = stage(h, B[RL_WNODE], R ? rn->alloc_node : nullptr, (size_t)A * 4)) return rc;
   if (int rc = stage(h, B[RL_WRES], res.data(), (size_t)A * sizeof(Res))) return rc;
+  if (with_attrs) {
+    DevBuf* C = h->d_ra;
+    if (int rc = stage(h, C[RA_WSTART], R ? attrs->start_sec : nullptr, (size_t)R * 8)) return rc;
+    if (int rc = stage(h, C[RA_WQOS], R ? attrs->qos : nullptr, (size_t)R * 4)) return rc;
+    if (int rc = stage(h, C[RA_WQPRIO], R ? attrs->qos_priority : nullptr, (size_t)R * 4)) return rc;
+    if (int rc = stage(h, C[RA_WPART], R ? attrs->partition_priority : nullptr, (size_t)R * 4)) return rc;
+    if (int rc = stage(h, C[RA_WACCT], R ? attrs->account : nullptr, (size_t)R * 4)) return rc;
+  }
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
   u32 M = 0;
   bool over = false;
-  if (int rc = run_rebuild(h, RL_WID, R, A, &M, &over)) return rc;   // (its synchronize: the local vectors)
+  if (int rc = run_rebuild(h, RL_WID, R, A, &M, &over)) return rc;   // (its synchronize: the local vectors, the caller's arrays)
   if (over) return fail(h, CNS_ERR_UNSUPPORTED, kRunOverCap);
-  return run_commit(h, R, A, M);
+  if (int rc = run_commit(h, R, A, M)) return rc;
+  if (with_attrs) ra_commit(h);
+  return CNS_OK;
 }
 
 int cns_running_seed(cns_handle* h, const cns_running_soa* rn, const uint32_t* job_ids) {
@@ -157,8 +186,9 @@ int cns_running_seed(cns_handle* h, const cns_running_soa* rn, const uint32_t* j
   return rc;
 }
 
+// queue_attrs / with_attrs: cns_running_advance_attrs (the columns follow the rows); a plain call launches what it always did
 static int advance_impl(cns_handle* h, const cns_running_step* in, const cns_running_step_out* out, const std::vector<u32>& sorted_ids,
-                        const std::vector<u32>& order) {
+                        const std::vector<u32>& order, const cns_running_attrs* queue_attrs = nullptr, bool with_attrs = false) {
   const u32 K = (u32)in->num_retire, R = h->rl_R, A = h->rl_A;
   const u64 J = in->num_jobs, places = J ? h->q.places : 0;
   HIPCHK(h, hipSetDevice(h->device));
@@ -177,6 +207,17 @@ static int advance_impl(cns_handle* h, const cns_running_step* in, const cns_run
   HIPCHK(h, B[RL_WOFF].ensure(((size_t)cap_rows + 1) * 4)); HIPCHK(h, B[RL_WNODE].ensure((size_t)cap_ents * 4)); HIPCHK(h, B[RL_WRES].ensure((size_t)cap_ents * sizeof(Res)));
   HIPCHK(h, B[RL_TOT].ensure(8 * sizeof(u32)));
   HIPCHK(h, hipMemsetAsync(B[RL_TOT].p, 0, 8 * sizeof(u32), h->stream));
+  DevBuf* C = h->d_ra;
+  if (with_attrs) {
+    if (int rc = ra_ensure_copy(h, cap_rows)) return rc;
+    HIPCHK(h, C[RA_ORIGIN].ensure((size_t)cap_rows * 4));
+    if (J) {
+      if (int rc = stage(h, C[RA_QQOS], queue_attrs->qos, (size_t)J * 4)) return rc;
+      if (int rc = stage(h, C[RA_QQPRIO], queue_attrs->qos_priority, (size_t)J * 4)) return rc;
+      if (int rc = stage(h, C[RA_QPART], queue_attrs->partition_priority, (size_t)J * 4)) return rc;
+      if (int rc = stage(h, C[RA_QACCT], queue_attrs->account, (size_t)J * 4)) return rc;
+    }
+  }
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
   u32* tot = B[RL_TOT].as<u32>();   // kept rows, kept entries, admitted rows, admitted entries
   RunSrc S;
@@ -193,6 +234,7 @@ static int advance_impl(cns_handle* h, const cns_running_step* in, const cns_run
     scan_counts(h->stream, S.wave_rows, waves, tot + 0);
     scan_counts(h->stream, S.wave_ents, waves, tot + 1);
     hipLaunchKernelGGL(k_run_compact<false>, dim3(grid), dim3(kRunBlock), 0, h->stream, S);
+    if (with_attrs) hipLaunchKernelGGL(k_ra_origin<false>, dim3(grid), dim3(kRunBlock), 0, h->stream, S, C[RA_ORIGIN].as<u32>());
     HIPCHK(h, hipGetLastError());
   }
   if (J) {   // ---- admit: the jobs of the last cycle that the commit loop started, behind the kept rows ----
@@ -216,9 +258,18 @@ static int advance_impl(cns_handle* h, const cns_running_step* in, const cns_run
     scan_counts(h->stream, S.wave_rows, waves, tot + 2);
     scan_counts(h->stream, S.wave_ents, waves, tot + 3);
     hipLaunchKernelGGL(k_run_compact<true>, dim3(grid), dim3(kRunBlock), 0, h->stream, S);
+    if (with_attrs) hipLaunchKernelGGL(k_ra_origin<true>, dim3(grid), dim3(kRunBlock), 0, h->stream, S, C[RA_ORIGIN].as<u32>());
     HIPCHK(h, hipGetLastError());
   }
   hipLaunchKernelGGL(k_run_seal, dim3(1), dim3(64), 0, h->stream, S.D.off, (const u32*)tot, cap_rows);
+  if (with_attrs && cap_rows) {
+    RaGather G;
+    memset(&G, 0, sizeof G);
+    G.cap_rows = cap_rows; G.old_rows = R; G.queue_jobs = J; G.now = in->now_sec;
+    G.tot = tot; G.origin = C[RA_ORIGIN].as<u32>(); G.L = ra_cols(h, RA_START); G.D = ra_cols(h, RA_WSTART);
+    G.q_qos = C[RA_QQOS].as<u32>(); G.q_qprio = C[RA_QQPRIO].as<u32>(); G.q_part = C[RA_QPART].as<u32>(); G.q_account = C[RA_QACCT].as<u32>();
+    hipLaunchKernelGGL(k_ra_gather, dim3((cap_rows + kRunBlock - 1) / kRunBlock), dim3(kRunBlock), 0, h->stream, G);
+  }
   HIPCHK(h, hipGetLastError());
   u32 ht[4] = {0, 0, 0, 0};
   std::vector<uint8_t> found(K);
@@ -232,6 +283,7 @@ static int advance_impl(cns_handle* h, const cns_running_step* in, const cns_run
   if (int rc = run_rebuild(h, RL_WID, (u32)R2, (u32)A2, &M, &over)) return rc;
   if (over) return fail(h, CNS_ERR_UNSUPPORTED, kRunOverCap);
   if (int rc = run_commit(h, (u32)R2, (u32)A2, M)) return rc;
+  if (with_attrs) ra_commit(h);
   for (u32 i = 0; i < K; ++i) out->found[order[i]] = found[i];
   if (out && out->num_retired) *out->num_retired = R - ht[0];
   if (out && out->num_admitted) *out->num_admitted = ht[2];

@@ -34,8 +34,10 @@ static int rp_build_index(cns_handle* h) {
   return 0;
 }
 
+// from_attrs: cns_running_select_preempt_attrs (running_attrs_host.inc) — the running jobs' fields come from the ledger's columns, the
+// rows are the ledger's by construction (no rn_job_id to upload or to check), the ids of the preempted rows are picked on the device
 static int running_select_preempt_impl(cns_handle* h, int64_t now, const cns_job_soa* jobs, const cns_preempt_soa* pre, cns_placement_soa* out,
-                                       cns_preempt_out* pout) {
+                                       cns_preempt_out* pout, bool from_attrs = false) {
   DevBuf* P = h->d_rp;
   const u32 R = h->rl_R, M = h->rl_M;
   HIPCHK(h, hipSetDevice(h->device));
@@ -48,7 +50,7 @@ static int running_select_preempt_impl(cns_handle* h, int64_t now, const cns_job
   h->rp_call = false;
   if (build) { if (int rc = rp_build_index(h)) return rc; }
   HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-  if (int rc = stage(h, P[RP_GIVEN], R ? pre->rn_job_id : nullptr, (size_t)R * 4)) return rc;
+  if (!from_attrs) { if (int rc = stage(h, P[RP_GIVEN], R ? pre->rn_job_id : nullptr, (size_t)R * 4)) return rc; }
   if (int rc = stage(h, P[RP_SET], set.data(), (size_t)ns * 4)) return rc;
   HIPCHK(h, P[RP_FOUND].ensure(ns));
   if (ns) HIPCHK(h, hipMemsetAsync(P[RP_FOUND].p, 0, ns, h->stream));
@@ -60,7 +62,7 @@ static int running_select_preempt_impl(cns_handle* h, int64_t now, const cns_job
     RpMark K;
     memset(&K, 0, sizeof K);
     K.R = R; K.nset = ns; K.now = now;
-    K.ledger_id = h->d_rl[RL_ID].as<u32>(); K.ledger_end = h->d_rl[RL_END].as<i64>(); K.given_id = P[RP_GIVEN].as<u32>();
+    K.ledger_id = h->d_rl[RL_ID].as<u32>(); K.ledger_end = h->d_rl[RL_END].as<i64>(); K.given_id = from_attrs ? K.ledger_id : P[RP_GIVEN].as<u32>();
     K.set = P[RP_SET].as<u32>(); K.rj_off = P[RP_RJOFF].as<u32>(); K.found = P[RP_FOUND].as<uint8_t>();
     K.rj_preempting = P[RP_RJPRE].as<uint8_t>(); K.rj_end = P[RP_RJEND].as<i64>(); K.flag = P[RP_FLAG].as<u32>();
     hipLaunchKernelGGL(k_rp_mark, dim3((R + kRunChunk - 1) / kRunChunk), dim3(kRunBlock), 0, h->stream, K);
@@ -97,16 +99,41 @@ static int running_select_preempt_impl(cns_handle* h, int64_t now, const cns_job
   if (int rc = cns_upload_jobs(h, jobs)) return rc;
   h->rp_call = true;
   h->rn_end_bound = P[RP_ENTEND].as<i64>();   // this call's cycle runs on the patched copy; the resident end times are not written
-  const int rc = pre_cycle(h, now, jobs, pre, out, pout, R, M, set_in, "cns_running_select_preempt", [&](PreParams& Q) -> int {
+  // the job ids behind the few ledger rows the cycle preempted, without the caller's rn_job_id
+  const PreRowIds pick_ids = [&](const std::vector<u32>& rows, std::vector<u32>& ids) -> int {
+    const u32 n = (u32)rows.size();
+    ids.assign(n, 0u);
+    if (!n) return 0;
+    DevBuf* C = h->d_ra;
+    if (int rc2 = stage(h, C[RA_PICK], rows.data(), (size_t)n * 4)) return rc2;
+    HIPCHK(h, C[RA_PICKED].ensure((size_t)n * 4));
+    hipLaunchKernelGGL(k_ra_pick, dim3((n + kRunBlock - 1) / kRunBlock), dim3(kRunBlock), 0, h->stream, (const u32*)C[RA_PICK].as<u32>(), n, (const u32*)h->d_rl[RL_ID].as<u32>(), R,
+                       C[RA_PICKED].as<u32>());
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(ids.data(), C[RA_PICKED].p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+  };
+  const int rc = pre_cycle(h, now, jobs, pre, out, pout, R, M, set_in, from_attrs ? "cns_running_select_preempt_attrs" : "cns_running_select_preempt", [&](PreParams& Q) -> int {
     DevBuf* B = h->d_pre;
-    if (int rc2 = stage(h, B[B_RJQOS], pre->rn_qos, (size_t)R * 4)) return rc2;          // (as they are: ledger order is the caller's contract)
-    if (int rc2 = stage(h, B[B_RJQP], pre->rn_qos_priority, (size_t)R * 4)) return rc2;
-    if (int rc2 = stage(h, B[B_RJSTART], pre->rn_start_sec, (size_t)R * 8)) return rc2;
+    if (from_attrs) {   // three device-to-device copies into the buffers the cycle reads
+      DevBuf* C = h->d_ra;
+      HIPCHK(h, B[B_RJQOS].ensure((size_t)R * 4)); HIPCHK(h, B[B_RJQP].ensure((size_t)R * 4)); HIPCHK(h, B[B_RJSTART].ensure((size_t)R * 8));
+      if (R) {
+        HIPCHK(h, hipMemcpyAsync(B[B_RJQOS].p, C[RA_QOS].p, (size_t)R * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(B[B_RJQP].p, C[RA_QPRIO].p, (size_t)R * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(B[B_RJSTART].p, C[RA_START].p, (size_t)R * 8, hipMemcpyDeviceToDevice, h->stream));
+      }
+    } else {
+      if (int rc2 = stage(h, B[B_RJQOS], pre->rn_qos, (size_t)R * 4)) return rc2;          // (as they are: ledger order is the caller's contract)
+      if (int rc2 = stage(h, B[B_RJQP], pre->rn_qos_priority, (size_t)R * 4)) return rc2;
+      if (int rc2 = stage(h, B[B_RJSTART], pre->rn_start_sec, (size_t)R * 8)) return rc2;
+    }
     Q.rn_job = P[RP_ENTJOB].as<u32>(); Q.ent_slot = P[RP_ENTSLOT].as<u32>();
     Q.rj_qos = B[B_RJQOS].as<u32>(); Q.rj_qprio = B[B_RJQP].as<u32>(); Q.rj_start = B[B_RJSTART].as<i64>(); Q.rj_end = P[RP_RJEND].as<i64>();
     Q.rj_preempting = P[RP_RJPRE].as<uint8_t>(); Q.rj_off = P[RP_RJOFF].as<u32>(); Q.rj_ent = P[RP_RJENT].as<u32>();
     return 0;
-  });
+  }, from_attrs ? &pick_ids : nullptr);
   if (rc == CNS_OK) h->run_preempt_rl = true;
   return rc;
 }

@@ -59,6 +59,9 @@ GATE_ABI_SYMBOLS = ("cns_gate_pending", "cns_gate_shape")
 RUNNING_ABI_SYMBOLS = ("cns_running_seed", "cns_running_advance", "cns_running_get", "cns_running_get_timing", "cns_running_shape")
 # ... and include/crane_gpu_running/running_preempt.h
 RUNNING_PREEMPT_ABI_SYMBOLS = ("cns_running_select_preempt", "cns_debug_get_preempt_index", "cns_running_preempt_get_timing")
+# ... and include/crane_gpu_running/running_attrs.h
+RUNNING_ATTRS_ABI_SYMBOLS = ("cns_running_seed_attrs", "cns_running_advance_attrs", "cns_running_get_attrs", "cns_priority_order_resident",
+                             "cns_running_select_preempt_attrs")
 LIMITS_ABI_SYMBOLS = ("cns_set_run_limits", "cns_apply_run_limits", "cns_upload_limit_jobs", "cns_run_limits_resident",
                       "cns_download_limits", "cns_get_limit_timing", "cns_get_usage", "cns_limits_shape")
 
@@ -581,22 +584,39 @@ class GpuNodeSelector:
         return a.value, b.value, c.value
 
     # -- the running set kept on the device between two cycles (include/crane_gpu_running/running.h) -----------------------------
-    def seed_running(self, running: "abi.Running | None", job_ids=None):
+    def seed_running(self, running: "abi.Running | None", job_ids=None, attrs: "abi.RunningAttrs | None" = None):
         """The running set into the device ledger, job_ids[R] naming its rows; the per-slot running tables are derived from it on the
-        device and end up exactly as set_running(running) would leave them.  After set_nodes / set_reservations."""
-        if running is None or len(running.end_sec) == 0:
-            self._check(self._L.cns_running_seed(self._h, None, None))
+        device and end up exactly as set_running(running) would leave them.  After set_nodes / set_reservations.
+        attrs (abi.RunningAttrs, one value per row): the ledger also carries the attribute columns (running_attrs.h); without it
+        this is the plain call, which leaves a ledger without columns."""
+        empty = running is None or len(running.end_sec) == 0
+        if attrs is None:
+            if empty:
+                self._check(self._L.cns_running_seed(self._h, None, None))
+                return
+            ids = abi._arr(job_ids, np.uint32, len(running.end_sec))
+            r = running.to_c()
+            self._check(self._L.cns_running_seed(self._h, C.byref(r), abi._ptr(ids)))
             return
+        if empty:
+            self._check(self._L.cns_running_seed_attrs(self._h, None, None, None))
+            return
+        if len(attrs) != len(running.end_sec):
+            raise ValueError("attrs: one value per running job")
         ids = abi._arr(job_ids, np.uint32, len(running.end_sec))
-        r = running.to_c()
-        self._check(self._L.cns_running_seed(self._h, C.byref(r), abi._ptr(ids)))
+        r, a = running.to_c(), attrs.to_c()
+        self._check(self._L.cns_running_seed_attrs(self._h, C.byref(r), abi._ptr(ids), C.byref(a)))
 
-    def advance_running(self, retire_ids=(), now: "int | None" = None, job_ids=None, admit=None, reservation=None):
+    def advance_running(self, retire_ids=(), now: "int | None" = None, job_ids=None, admit=None, reservation=None,
+                        attrs: "abi.RunningAttrs | bool | None" = None):
         """One cycle boundary on the device ledger: the rows that carry one of retire_ids are erased (stably), then — when job_ids is
         given, one id per job of the last node_select's queue — every job with admit[j] != 0 (None: every job) that the cycle started at
         `now` is appended with its placements, then the per-slot running tables are rebuilt against the current layout.
         -> (found[K] uint8, num_retired, num_admitted).  Nothing to retire and nothing to admit: the rebuild alone (what follows
-        set_nodes / set_reservations)."""
+        set_nodes / set_reservations).
+        attrs: the columns follow the rows (cns_running_advance_attrs) — an abi.RunningAttrs with one value per job of the queue when
+        job_ids is given (an admitted row starts at `now`), True when there is nothing to admit.  Without it this is the plain call,
+        which drops the columns."""
         ret = abi._arr(np.asarray(retire_ids, np.uint32).reshape(-1), np.uint32)
         k = len(ret)
         found, nret, nadm = np.zeros(max(k, 1), np.uint8), np.zeros(1, np.uint64), np.zeros(1, np.uint64)
@@ -616,8 +636,41 @@ class GpuNodeSelector:
                 s.reservation = abi._ptr(rv)
                 keep.append(rv)
         o = abi.CnsRunningStepOut(abi._ptr(found), abi._ptr(nret), abi._ptr(nadm))
-        self._check(self._L.cns_running_advance(self._h, C.byref(s), C.byref(o)))
+        if attrs is None or attrs is False:
+            self._check(self._L.cns_running_advance(self._h, C.byref(s), C.byref(o)))
+        else:
+            qa = attrs.to_c() if isinstance(attrs, abi.RunningAttrs) else None
+            self._check(self._L.cns_running_advance_attrs(self._h, C.byref(s), C.byref(qa) if qa is not None else None, C.byref(o)))
         return found[:k], int(nret[0]), int(nadm[0])
+
+    def running_attrs(self) -> dict:
+        """The attribute columns of the device ledger and the three values derived per row (node_num, alloc_cpu_raw, alloc_mem: what
+        the sorter reads of a running job), in ledger order."""
+        nj = np.zeros(1, np.uint64)
+        o = abi.CnsRunningAttrsOut()
+        o.num_jobs = abi._ptr(nj)
+        self._check(self._L.cns_running_get_attrs(self._h, C.byref(o)))
+        r = int(nj[0])
+        dt = {"start_sec": np.int64, "alloc_cpu_raw": np.int64, "alloc_mem": np.uint64}
+        a = {f: np.zeros(max(r, 1), dt.get(f, np.uint32)) for f, _ in abi.CnsRunningAttrsOut._fields_[2:]}
+        o.capacity_jobs = r
+        for f, v in a.items():
+            setattr(o, f, abi._ptr(v))
+        self._check(self._L.cns_running_get_attrs(self._h, C.byref(o)))
+        return {f: v[:r] for f, v in a.items()}
+
+    def priority_order_resident(self, now: int, cfg, num_accounts: int, pending, limit: "int | None" = None):
+        """priority_order with the running side taken from the device ledger and its attribute columns: running job i is ledger row i.
+        -> (order, priority, num_ordered), bit for bit what priority_order gives for the same rows handed in from the host."""
+        J = pending.num_jobs
+        order = np.empty(max(J, 1), np.uint32)
+        prio = np.empty(max(J, 1), np.float64)
+        nord = C.c_uint64(0)
+        c_cfg, c_pd = cfg.to_c(), pending.to_c()
+        self._check(self._L.cns_priority_order_resident(
+            self._h, C.c_int64(now), C.byref(c_cfg), C.c_uint32(num_accounts), C.byref(c_pd), C.c_uint64(J if limit is None else limit),
+            order.ctypes.data_as(C.c_void_p), prio.ctypes.data_as(C.c_void_p), C.byref(nord)))
+        return order[:J], prio[:J], int(nord.value)
 
     def running_ledger(self):
         """The device ledger -> (abi.Running, job_ids): its rows in ledger order, every plane."""
@@ -652,15 +705,30 @@ class GpuNodeSelector:
         return tuple(x.value for x in v)
 
     # -- a cycle with preemption on that set (include/crane_gpu_running/running_preempt.h) ---------------------------------------
-    def node_select_preempt_resident(self, now: int, jobs: abi.Jobs, preempt: "abi.Preempt"):
+    def node_select_preempt_resident(self, now: int, jobs: abi.Jobs, preempt: "abi.Preempt", from_attrs: bool = False):
         """node_select_preempt for a handle whose running tables were built by seed_running / advance_running; -> (Placements,
         PreemptOut).  LEDGER ORDER: running job index r is ledger row r, so preempt.rn_job_id / rn_qos / rn_qos_priority / rn_start_sec
         are in the ledger's order (seed order, stable erase, admitted jobs appended in queue order; running_ledger() reports it), and a
         reference without bit 31 in the preempted lists is a ledger row.  rn_job_id is checked against the ledger on the device.
-        advance_running behind it needs its admit mask."""
+        advance_running behind it needs its admit mask.
+        from_attrs: cns_running_select_preempt_attrs — the running jobs' qos, qos_priority and start_sec come from the ledger's columns
+        and preempt's rn_* arrays are not handed in at all (leave them empty)."""
         out = abi.Placements(jobs.num_jobs, jobs.total_places())
+        cj, co, cp = jobs.to_c(), out.to_c(), preempt.to_c()
+        if from_attrs:
+            nj = np.zeros(1, np.uint64)
+            led = abi.CnsRunningLedger()
+            led.num_jobs = abi._ptr(nj)
+            self._check(self._L.cns_running_get(self._h, C.byref(led)))
+            pout = abi.PreemptOut(jobs.num_jobs, int(nj[0]))
+            cpo = pout.to_c()
+            if preempt.enabled:
+                cp.rn_job_id = cp.rn_qos = cp.rn_qos_priority = cp.rn_start_sec = None
+            self._check(self._L.cns_running_select_preempt_attrs(self._h, C.c_int64(now), C.byref(cj), C.byref(cp), C.byref(co), C.byref(cpo)))
+            self._jobs = jobs
+            return out, pout
         pout = abi.PreemptOut(jobs.num_jobs, len(preempt.rn_job_id))
-        cj, co, cp, cpo = jobs.to_c(), out.to_c(), preempt.to_c(), pout.to_c()
+        cpo = pout.to_c()
         self._check(self._L.cns_running_select_preempt(self._h, C.c_int64(now), C.byref(cj), C.byref(cp), C.byref(co), C.byref(cpo)))
         self._jobs = jobs
         return out, pout

@@ -26,6 +26,7 @@
 #include "../../include/crane_gpu_usage/usage.h"
 #include "../../include/crane_gpu_running/running.h"
 #include "../../include/crane_gpu_running/running_preempt.h"
+#include "../../include/crane_gpu_running/running_attrs.h"
 
 namespace crane {
 
@@ -92,6 +93,8 @@ struct GpuNodeSelectionAlgo::Impl {
   bool resident_running = false, resident_stale = false;
   std::vector<job_id_t> ledger_ids;                                 // the device ledger's rows, in ledger order (SeedRunning / AdvanceRunning keep it)
   bool ledger_ids_valid = false;
+  bool want_attrs = false, ra_cols = false;                         // UseResidentAttrs; ... and the ledger carries the attribute columns (running_attrs.h)
+  std::unordered_map<std::string, uint32_t> account_ids;            // account name -> dense id, grow-only across cycles
   int64_t last_now = 0;
   bool resvq_stale = true;   // the engine's per-node tables of the reservation what-ifs are older than the packed running set / the snapshot
   std::vector<const PdJobInScheduler*> last_ord;                      // the jobs of the last cns_select, in its order
@@ -1137,6 +1140,11 @@ void GpuNodeSelectionAlgo::NodeSelect(const TimeSec& now,
 // ---------------------------------------------------------------------------------------------------------
 void GpuNodeSelectionAlgo::UseResidentRunning(bool on) { impl_->resident_running = on; }
 bool GpuNodeSelectionAlgo::ResidentRunning() const { return impl_->resident_running; }
+void GpuNodeSelectionAlgo::UseResidentAttrs(bool on) { impl_->want_attrs = on; }
+bool GpuNodeSelectionAlgo::ResidentAttrs() const { return impl_->h && !impl_->grp && impl_->resident_running && impl_->ra_cols; }
+uint32_t GpuNodeSelectionAlgo::AccountId(const std::string& account) { return impl_->account_ids.emplace(account, (uint32_t)impl_->account_ids.size()).first->second; }
+uint32_t GpuNodeSelectionAlgo::NumAccounts() const { return (uint32_t)impl_->account_ids.size(); }
+cns_engine* GpuNodeSelectionAlgo::EngineHandle() const { return impl_->grp ? nullptr : impl_->h; }
 
 bool GpuNodeSelectionAlgo::SeedRunning(const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs) {
   Impl& I = *impl_;
@@ -1149,8 +1157,18 @@ bool GpuNodeSelectionAlgo::SeedRunning(const std::vector<std::unique_ptr<RnJobIn
   std::vector<uint32_t> ids(I.r_src.size() + 1);
   for (size_t r = 0; r < I.r_src.size(); ++r) ids[r] = I.r_src[r]->job_id;
   const cns_running_soa rs = I.running_soa();
-  const int st = cns_running_seed(I.h, rs.num_jobs ? &rs : nullptr, ids.data());
+  const size_t R = I.r_src.size();
+  std::vector<int64_t> a_start(R + 1);
+  std::vector<uint32_t> a_qos(R + 1), a_qp(R + 1), a_pp(R + 1), a_acc(R + 1);
+  for (size_t r = 0; I.want_attrs && r < R; ++r) {
+    const RnJobInScheduler& j = *I.r_src[r];
+    a_start[r] = j.start_time; a_qos[r] = I.qos_of(j.qos); a_qp[r] = j.qos_priority; a_pp[r] = j.partition_priority; a_acc[r] = AccountId(j.account);
+  }
+  const cns_running_attrs at{a_start.data(), a_qos.data(), a_qp.data(), a_pp.data(), a_acc.data()};
+  I.ra_cols = false;
+  const int st = I.want_attrs ? cns_running_seed_attrs(I.h, rs.num_jobs ? &rs : nullptr, ids.data(), &at) : cns_running_seed(I.h, rs.num_jobs ? &rs : nullptr, ids.data());
   if (st != 0) return fail(st, cns_last_error(I.h));
+  I.ra_cols = I.want_attrs;
   I.resident_stale = false;
   I.ledger_ids.assign(ids.begin(), ids.end() - 1);   // seed order
   I.ledger_ids_valid = true;
@@ -1186,7 +1204,19 @@ bool GpuNodeSelectionAlgo::AdvanceRunning(const std::vector<job_id_t>& finished_
   }
   uint64_t nret = 0, nadm = 0;
   const cns_running_step_out out{found.data(), &nret, &nadm};
-  const int st = cns_running_advance(I.h, &in, &out);
+  int st = 0;
+  if (I.ra_cols) {   // the columns follow the rows: the queue's attributes, in its order
+    const size_t J = in.num_jobs;
+    std::vector<uint32_t> q_qos(J + 1), q_qp(J + 1), q_pp(J + 1), q_acc(J + 1);
+    for (size_t j = 0; j < J; ++j) {
+      const PdJobInScheduler& p = *I.last_ord[j];
+      q_qos[j] = I.qos_of(p.qos); q_qp[j] = p.qos_priority; q_pp[j] = p.partition_priority; q_acc[j] = AccountId(p.account);
+    }
+    const cns_running_attrs qa{nullptr, q_qos.data(), q_qp.data(), q_pp.data(), q_acc.data()};
+    st = cns_running_advance_attrs(I.h, &in, &qa, &out);
+  } else {
+    st = cns_running_advance(I.h, &in, &out);
+  }
   if (st != 0) return fail(st, cns_last_error(I.h));
   I.resident_stale = false;
   if (I.ledger_ids_valid) {   // the ledger's order on this side: a stable erase, then the admitted jobs in queue order
@@ -1255,7 +1285,7 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
     if (I.grp) return fail_all(CNS_ERR_UNSUPPORTED, "resident running on an algorithm object over several devices");
     if (I.resident_stale) {   // a snapshot was pushed since the last boundary: the per-slot tables again, from the ledger
       const cns_running_step none{};
-      st = cns_running_advance(I.h, &none, nullptr);
+      st = I.ra_cols ? cns_running_advance_attrs(I.h, &none, nullptr, nullptr) : cns_running_advance(I.h, &none, nullptr);   // (the plain call would drop the columns)
       if (st != 0) return fail_all(st, cns_last_error(I.h));
       I.resident_stale = false;
     }
@@ -1330,7 +1360,8 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
     std::vector<double> pj_prio(J + 1);
     std::vector<int64_t> rj_start(R + 1);
     for (size_t j = 0; j < J; ++j) { pj_id[j] = ord[j]->job_id; pj_qos[j] = I.qos_of(ord[j]->qos); pj_qp[j] = ord[j]->qos_priority; pj_prio[j] = ord[j]->priority; }
-    for (uint32_t r = 0; r < R; ++r) { rj_id[r] = rsrc[r]->job_id; rj_qos[r] = I.qos_of(rsrc[r]->qos); rj_qp[r] = rsrc[r]->qos_priority; rj_start[r] = rsrc[r]->start_time; }
+    if (I.resident_running && I.ra_cols) { for (uint32_t r = 0; r < R; ++r) rj_id[r] = rsrc[r]->job_id; }   // (for CommitCheck's running ids only)
+    else for (uint32_t r = 0; r < R; ++r) { rj_id[r] = rsrc[r]->job_id; rj_qos[r] = I.qos_of(rsrc[r]->qos); rj_qp[r] = rsrc[r]->qos_priority; rj_start[r] = rsrc[r]->start_time; }
     for (job_id_t id : I.preempting) pset.push_back(id);
     std::vector<uint32_t> qoff(I.qos_preempt.size() + 1, 0), qflat;
     for (size_t q = 0; q < I.qos_preempt.size(); ++q) { for (uint32_t x : I.qos_preempt[q]) qflat.push_back(x); qoff[q + 1] = (uint32_t)qflat.size(); }
@@ -1340,7 +1371,8 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
     ps.enabled = 1; ps.num_qos = (uint32_t)I.qos_preempt.size();
     ps.qos_preempt_offsets = qoff.data(); ps.qos_preempt = qflat.data();
     ps.pd_job_id = pj_id.data(); ps.pd_qos = pj_qos.data(); ps.pd_qos_priority = pj_qp.data(); ps.pd_priority = pj_prio.data();
-    ps.rn_job_id = rj_id.data(); ps.rn_qos = rj_qos.data(); ps.rn_qos_priority = rj_qp.data(); ps.rn_start_sec = rj_start.data();
+    const bool from_cols = I.resident_running && I.ra_cols;   // qos, qos_priority and start_sec of the rows are on the ledger: nothing per row goes up
+    if (!from_cols) { ps.rn_job_id = rj_id.data(); ps.rn_qos = rj_qos.data(); ps.rn_qos_priority = rj_qp.data(); ps.rn_start_sec = rj_start.data(); }
     ps.num_preempting = (uint32_t)I.preempting.size(); ps.preempting_job_ids = pset.data();
     std::vector<uint64_t> po_off(J + 1, 0);
     std::vector<uint32_t> po_refs(4 * (J + R) + 64), po_cancel(R + 1), po_set(R + I.preempting.size() + 1);
@@ -1348,7 +1380,8 @@ void GpuNodeSelectionAlgo::SelectPacked_(const TimeSec& now, const std::vector<s
     po.capacity = po_refs.size(); po.offsets = po_off.data(); po.preempted = po_refs.data();
     po.cancel_capacity = (uint32_t)po_cancel.size(); po.cancelled_job_ids = po_cancel.data();
     po.preempting_capacity = (uint32_t)po_set.size(); po.preempting_job_ids = po_set.data();
-    st = I.resident_running ? cns_running_select_preempt(I.h, now, &js, &ps, &out, &po) : cns_select_preempt(I.h, now, &js, &ps, &out, &po);
+    st = from_cols ? cns_running_select_preempt_attrs(I.h, now, &js, &ps, &out, &po)
+         : I.resident_running ? cns_running_select_preempt(I.h, now, &js, &ps, &out, &po) : cns_select_preempt(I.h, now, &js, &ps, &out, &po);
     if (st != 0) return fail_all(st, cns_last_error(I.h));
     for (size_t j = 0; j < J; ++j)
       for (uint64_t x = po_off[j]; x < po_off[j + 1]; ++x) {
@@ -2621,15 +2654,20 @@ GpuMultiFactorPriority::GpuMultiFactorPriority(const PriorityConfig& cfg, int de
   status_ = cns_create(&c, &h_);
   if (status_ != 0) error_ = cns_last_error(nullptr);
 }
+GpuMultiFactorPriority::GpuMultiFactorPriority(const PriorityConfig& cfg, GpuNodeSelectionAlgo* algo) : cfg_(cfg), algo_(algo) {
+  h_ = algo ? algo->EngineHandle() : nullptr;
+  if (!h_) { status_ = CNS_ERR_NO_DEVICE; error_ = "GpuMultiFactorPriority: the algorithm object has no engine on one device to borrow"; }
+}
 GpuMultiFactorPriority::~GpuMultiFactorPriority() {
-  if (h_) cns_destroy(h_);
+  if (h_ && !algo_) cns_destroy(h_);
 }
 
 void GpuMultiFactorPriority::GetOrderedJobPtrVec(const TimeSec& now,
                                                  const std::vector<std::unique_ptr<PdJobInScheduler>>& pending_jobs,
                                                  const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs,
                                                  size_t limit, std::vector<PdJobInScheduler*>& job_ptr_vec) {
-  const size_t J = pending_jobs.size(), R = running_jobs.size();
+  const bool resident = algo_ && algo_->ResidentAttrs();   // the running side is the ledger's: running_jobs is not touched
+  const size_t J = pending_jobs.size(), R = resident ? 0 : running_jobs.size();
   job_ptr_vec.clear();
   job_ptr_vec.reserve(J);
   auto keep_input_order = [&](int st, const std::string& msg) {
@@ -2639,7 +2677,7 @@ void GpuMultiFactorPriority::GetOrderedJobPtrVec(const TimeSec& now,
   if (!h_) return keep_input_order(status_ ? status_ : CNS_ERR_NO_DEVICE, error_);
   // dense account ids (the reference keys its service-value map by account name, cpp:7667,7744)
   std::unordered_map<std::string, uint32_t> acc_id;
-  auto id_of = [&](const std::string& a) { return acc_id.emplace(a, (uint32_t)acc_id.size()).first->second; };
+  auto id_of = [&](const std::string& a) { return resident ? algo_->AccountId(a) : acc_id.emplace(a, (uint32_t)acc_id.size()).first->second; };
   std::vector<int64_t> submit(J), cpu(J), r_start(R), r_cpu(R);
   std::vector<uint32_t> qos(J), part(J), nn(J), acc(J), r_qos(R), r_part(R), r_nn(R), r_acc(R);
   std::vector<uint64_t> mem(J), r_mem(R);
@@ -2671,8 +2709,8 @@ void GpuMultiFactorPriority::GetOrderedJobPtrVec(const TimeSec& now,
   std::vector<uint32_t> order(J + 1);
   std::vector<double> prio(J + 1);
   uint64_t nord = 0;
-  const int st = cns_priority_order(h_, now, &c, (uint32_t)acc_id.size(), &pd, R ? &rn : nullptr, limit, order.data(),
-                                    prio.data(), &nord);
+  const int st = resident ? cns_priority_order_resident(h_, now, &c, algo_->NumAccounts(), &pd, limit, order.data(), prio.data(), &nord)
+                           : cns_priority_order(h_, now, &c, (uint32_t)acc_id.size(), &pd, R ? &rn : nullptr, limit, order.data(), prio.data(), &nord);
   if (st != 0) return keep_input_order(st, cns_last_error(h_));
   status_ = 0;
   error_.clear();

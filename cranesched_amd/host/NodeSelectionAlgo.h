@@ -267,9 +267,15 @@ class IPrioritySorter {
 // values, priorities and the ordering run on the device (include/crane_gpu/priority.h).  Writes job->priority,
 // fills job_ptr_vec with the first `limit` jobs by descending priority (ties: input order) and marks the rest
 // "Priority" (cpp:7625-7630).  On an engine error the vector keeps input order and LastError() says why.
+// A sorter built over a GpuNodeSelectionAlgo BORROWS that object's engine (the algorithm object must outlive it): when the algorithm
+// runs with resident running and its device ledger carries the attribute columns (include/crane_gpu_running/running_attrs.h:
+// SeedRunning / AdvanceRunning hand them in), the running side is read from the ledger — ledger row i is running job i — and the
+// CONTENTS of `running_jobs` are not touched (the vector may be empty).  Otherwise it behaves as the sorter with a handle of its own.
+class GpuNodeSelectionAlgo;
 class GpuMultiFactorPriority final : public IPrioritySorter {
  public:
   explicit GpuMultiFactorPriority(const PriorityConfig& cfg, int device = 0);
+  GpuMultiFactorPriority(const PriorityConfig& cfg, GpuNodeSelectionAlgo* algo);
   ~GpuMultiFactorPriority() override;
   GpuMultiFactorPriority(const GpuMultiFactorPriority&) = delete;
   GpuMultiFactorPriority& operator=(const GpuMultiFactorPriority&) = delete;
@@ -282,6 +288,7 @@ class GpuMultiFactorPriority final : public IPrioritySorter {
  private:
   PriorityConfig cfg_;
   cns_engine* h_{nullptr};
+  GpuNodeSelectionAlgo* algo_{nullptr};   // the owner of h_ when it is borrowed
   int status_{0};
   std::string error_;
 };
@@ -602,7 +609,7 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
 
   // ---- the running set kept on the device between two cycles (include/crane_gpu_running/running.h) -------------------------
   // With resident running ON, NodeSelect(now, running_jobs, pending_jobs) does not hand the running set to the engine and ignores the
-  // CONTENTS of running_jobs (a multifactor sorter still reads them): the cycle runs on the device ledger.  The caller seeds the ledger
+  // CONTENTS of running_jobs (a multifactor sorter still reads them, unless it borrows this object's engine and UseResidentAttrs is on): the cycle runs on the device ledger.  The caller seeds the ledger
   // once and, behind every cycle, tells it what the commit loop did:
   //   SeedRunning(running_jobs)                          the whole set, once (and again after a restart); the vector's order is the
   //                                                      ledger's order (a job whose reservation is unknown is left out, as in a cycle)
@@ -620,6 +627,20 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   // that preempted a running job is held back by it ("Waiting for Preemption", JobScheduler.cpp:1542-1555) and must not be named.
   void UseResidentRunning(bool on);
   bool ResidentRunning() const;
+  // The attribute columns beside the ledger (include/crane_gpu_running/running_attrs.h).  SeedRunning hands start_time, qos, qos_priority,
+  // partition_priority and account of every RnJobInScheduler in, AdvanceRunning those of the admitted PdJobInScheduler (its start is the
+  // cycle's now).  Account names map to dense ids through a grow-only table kept across cycles: an id, once given, never moves;
+  // NumAccounts() is its size.  ResidentAttrs(): resident running is on and the ledger carries the columns — then a
+  // GpuMultiFactorPriority built over this object ranks from the ledger, and NodeSelect with preempt_enabled packs no per-row arrays
+  // (cns_running_select_preempt_attrs; it still needs the caller's objects to resolve the preempted lists by ledger id).
+  // Opt-in (UseResidentAttrs(true) before SeedRunning), because a row admitted with the columns starts at the cycle's now whatever
+  // start_time the caller later writes into its own RnJobInScheduler: a caller that keeps another start there and wants TryPreempt_ to
+  // see it stays on the plain calls.
+  void UseResidentAttrs(bool on);
+  bool ResidentAttrs() const;
+  uint32_t AccountId(const std::string& account);
+  uint32_t NumAccounts() const;
+  cns_engine* EngineHandle() const;
   bool SeedRunning(const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs);
   bool AdvanceRunning(const std::vector<job_id_t>& finished_job_ids, const std::vector<const PdJobInScheduler*>& admitted,
                       uint64_t* num_retired = nullptr, uint64_t* num_admitted = nullptr);
