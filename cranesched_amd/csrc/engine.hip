@@ -58,6 +58,9 @@
 #include "csr_host.inc"        // the CSR rules of the callers' lists: offsets, sorted lists without a repeat (no HIP in there either)
 #include "snapshot_host.inc"   // the layout of a snapshot: groups, refusals, slots, reservations, node types, running entries (no HIP in there either)
 #include "gate_check_host.inc" // the input rules of cns_gate_pending (no HIP in there either)
+#include "acct_space_host.inc" // the record space the run limits, the submit limits and the usage tables address, its account chains and key ranges (no HIP in there either)
+#include "limits_check_host.inc" // the input rules of cns_set_run_limits / cns_upload_limit_jobs (no HIP in there either)
+#include "submit_check_host.inc" // the input rules of cns_set_submit_limits / cns_check_submissions (no HIP in there either)
 #include "usage_check_host.inc" // the input rules of cns_usage_set_tables / cns_usage_apply (no HIP in there either)
 #include "running_check_host.inc" // the input rules of cns_running_seed / cns_running_advance (no HIP in there either)
 #include "running_preempt_check_host.inc" // the input rules of cns_running_select_preempt (no HIP in there either)
@@ -226,22 +229,19 @@ struct cns_engine {
   DevBuf d_pre[B_COUNT];
   bool lim_have_tables = false, lim_have_jobs = false, lim_have_run = false;
   bool lim_has_upl = false, lim_has_apl = false, lim_has_sel = false, lim_has_skip = false;
-  u32 lim_U = 0, lim_UA = 0, lim_A = 0, lim_Q = 0, lim_Pn = 0, lim_base[5] = {0, 0, 0, 0, 0};
-  u64 lim_NR = 0, lim_J = 0, lim_sel_J = 0;
+  cns_acct::Space lim_sp{}, sub_sp{}, use_sp{};  // the record space of each feature's tables as last set (acct_space_host.inc)
+  u64 lim_J = 0, lim_sel_J = 0;
   std::vector<u32> lim_level;
   cns_limit_timing lim_timing{};
   // the submit limits over a batch of submissions (submit_host.inc): tables, the call's job arrays, items and results in buffers of their own
   DevBuf d_sub[SB_COUNT];
   bool sub_have = false, sub_has_upl = false, sub_has_apl = false, sub_has_uq = false, sub_has_aq = false, sub_has_g = false;
-  u32 sub_U = 0, sub_UA = 0, sub_A = 0, sub_Q = 0, sub_Pn = 0, sub_NR = 0, sub_NE = 0, sub_base[5] = {0, 0, 0, 0, 0}, sub_ent[3] = {0, 0, 0};
   u32 sub_max_set = 0, sub_max_cur = 0;         // the largest submit count of the tables as set / as the last call left them
   cns_gres_layout sub_lay{};
   cns_submit_timing sub_timing{};
   // releases and charges on the usage tables (usage_host.inc): three copies of the table, the call's rows, items and masks
   DevBuf d_use[US_COUNT];
   bool use_have = false, use_have_cur = false;  // tables set / a cns_usage_apply succeeded since
-  cns_usage_host::Dims use_dims{};
-  u32 use_base[5] = {0, 0, 0, 0, 0}, use_ent[3] = {0, 0, 0};
   cns_usage_timing use_timing{};
   // the running set kept on the device (running_host.inc): two copies of the ledger, the call's lists, counts and pairs, the per-slot
   // tables of the call (swapped with d_rn_off / d_rn_end / d_rn_res when it succeeded)

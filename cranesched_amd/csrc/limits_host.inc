@@ -58,31 +58,12 @@ int cns_set_run_limits(cns_handle* h, const cns_limit_tables* t) {
   if (!h || !t) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_run_limits: null argument");
   if (!h->have_nodes) return fail(h, CNS_ERR_STATE, "cns_set_run_limits before cns_set_nodes (the GRES layout comes with the nodes)");
   h->lim_have_tables = h->lim_have_jobs = h->lim_have_run = false;
-  const u64 U = t->num_users, UA = t->num_user_accts, A = t->num_accounts, Q = t->num_qos, Pn = t->num_partitions;
-  if (!Q || !t->qos) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_run_limits: no QoS");
-  if (A && !t->acct_parent) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_run_limits: acct_parent missing");
-  if (t->num_part_limits && !t->part_limits) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_run_limits: part_limits missing");
-  const u64 NR = U * Q + UA * Pn + A * Q + A * Pn + Q;
-  if (NR >= 0xFFFFFFF0ull || 3 * Q + t->num_part_limits >= 0xFFFFFFF0ull)
-    return fail(h, CNS_ERR_UNSUPPORTED, "cns_set_run_limits: more than 2^32 usage records");
+  cns_acct::Space S;
+  std::vector<u32> level;   // account tree levels (root = 0); the chain of a job is its account and the ancestors
+  if (const auto v = cns_limits_host::check_tables(t, &S, &level)) return fail(h, v.code, v.msg);
   HIPCHK(h, hipSetDevice(h->device));
   const LimCompMap m = lim_comp_map(h);
-  // account tree levels (root = 0); the chain of a job is its account and the ancestors
-  std::vector<u32> level(A, kNone);
-  for (u64 a = 0; a < A; ++a) {
-    u32 chain[CNS_LIM_MAX_CHAIN + 1];
-    u32 n = 0, x = (u32)a;
-    while (x != CNS_LIM_NONE) {
-      if (x >= A) return fail(h, CNS_ERR_INVALID_ARG, "acct_parent out of range");
-      if (level[x] != kNone) break;
-      if (n == CNS_LIM_MAX_CHAIN) return fail(h, CNS_ERR_UNSUPPORTED, "account chain longer than CNS_LIM_MAX_CHAIN (or a cycle)");
-      chain[n++] = x;
-      x = t->acct_parent[x];
-    }
-    u32 lv = x == CNS_LIM_NONE ? 0 : level[x] + 1;
-    while (n) { level[chain[--n]] = lv++; }
-    if (level[a] >= CNS_LIM_MAX_CHAIN) return fail(h, CNS_ERR_UNSUPPORTED, "account chain longer than CNS_LIM_MAX_CHAIN");
-  }
+  const u64 Q = S.Q;
   // limit records: [Qos per-user | Qos per-account | Qos global | partition limits]
   std::vector<LimRec> lim(3 * Q + t->num_part_limits);
   std::vector<u32> qflags(Q, 0);
@@ -90,7 +71,6 @@ int cns_set_run_limits(cns_handle* h, const cns_limit_tables* t) {
   auto zero_gres = [](LimRec& r) { for (u32 c = 4; c < 16; ++c) r.lim[c] = 0; };
   for (u64 q = 0; q < Q; ++q) {
     const cns_qos_limits& s = t->qos[q];
-    if (s.max_wall_sec < 0) return fail(h, CNS_ERR_INVALID_ARG, "negative Qos max_wall");
     const i64 wall = s.max_wall_sec > 0 ? s.max_wall_sec : kInf;
     LimRec& ru = lim[q]; LimRec& ra = lim[Q + q]; LimRec& rg = lim[2 * Q + q];
     zero_gres(ru); zero_gres(ra); zero_gres(rg);
@@ -104,53 +84,39 @@ int cns_set_run_limits(cns_handle* h, const cns_limit_tables* t) {
   }
   for (u32 i = 0; i < t->num_part_limits; ++i) {
     const cns_part_limit& s = t->part_limits[i];
-    if (s.max_wall_sec < 0) return fail(h, CNS_ERR_INVALID_ARG, "negative partition max_wall");
     LimRec& r = lim[3 * Q + i];
     zero_gres(r);
     r.lim[1] = s.max_jobs; r.lim[2] = s.max_wall_sec > 0 ? s.max_wall_sec : kInf;
     lim_pack_tres(m, s.max_tres, r);
   }
-  for (const u32* tab : {t->user_part_limit, t->acct_part_limit}) {
-    if (!tab) continue;
-    const u64 n = (tab == t->user_part_limit ? UA : A) * Pn;
-    for (u64 i = 0; i < n; ++i)
-      if (tab[i] != CNS_LIM_NONE && tab[i] >= t->num_part_limits) return fail(h, CNS_ERR_INVALID_ARG, "partition limit index out of range");
-  }
   // usage records, one array: [user_qos | user_part | acct_qos | acct_part | qos]; entries that do not exist are zero
-  std::vector<i64> usage(std::max<u64>(NR, 1) * 16, 0);
-  std::vector<uint8_t> exists(std::max<u64>(NR, 1), 1);
-  u64 base = 0;
-  auto put = [&](const cns_usage* u, const uint8_t* e, u64 n) {
-    for (u64 i = 0; i < n; ++i) {
-      const bool ex = !e || e[i];
-      exists[base + i] = ex;
-      lim_pack_usage(m, (u && ex) ? u + i : nullptr, usage.data() + (base + i) * 16);
+  std::vector<i64> usage(std::max<u64>(S.NR, 1) * 16, 0);
+  std::vector<uint8_t> exists(std::max<u64>(S.NR, 1), 1);
+  const cns_usage* use[5] = {t->user_qos, t->user_part, t->acct_qos, t->acct_part, t->qos_usage};
+  const uint8_t* nex[5] = {t->user_qos_exists, t->user_part_exists, t->acct_qos_exists, t->acct_part_exists, nullptr};
+  for (int w = 0; w < 5; ++w)
+    for (u64 i = 0, r = S.base[w]; i < S.len[w]; ++i, ++r) {
+      exists[r] = !nex[w] || nex[w][i];
+      lim_pack_usage(m, (use[w] && exists[r]) ? use[w] + i : nullptr, usage.data() + r * 16);
     }
-    base += n;
-  };
-  h->lim_base[0] = 0;            put(t->user_qos, t->user_qos_exists, U * Q);
-  h->lim_base[1] = (u32)base;    put(t->user_part, t->user_part_exists, UA * Pn);
-  h->lim_base[2] = (u32)base;    put(t->acct_qos, t->acct_qos_exists, A * Q);
-  h->lim_base[3] = (u32)base;    put(t->acct_part, t->acct_part_exists, A * Pn);
-  h->lim_base[4] = (u32)base;    put(t->qos_usage, nullptr, Q);
-  std::vector<u32> parent(t->acct_parent, t->acct_parent + A);
+  std::vector<u32> parent(t->acct_parent, t->acct_parent + S.A);
   if (parent.empty()) { parent.push_back(kNone); level.push_back(0); }
   DevBuf* b = h->d_lim;  // (buf_slots.h)
   if (int rc = upload(h, b[LM_LIM], lim)) return rc;
   if (int rc = upload(h, b[LM_QFLAGS], qflags)) return rc;
   if (int rc = upload(h, b[LM_PARENT], parent)) return rc;
   if (int rc = upload(h, b[LM_LEVEL], level)) return rc;
-  h->lim_has_upl = t->user_part_limit != nullptr && UA * Pn > 0;
-  h->lim_has_apl = t->acct_part_limit != nullptr && A * Pn > 0;
+  h->lim_has_upl = t->user_part_limit != nullptr && S.len[1] > 0;
+  h->lim_has_apl = t->acct_part_limit != nullptr && S.len[3] > 0;
   std::vector<u32> upl, apl;  // kept alive until the stream is drained below
-  if (h->lim_has_upl) { upl.assign(t->user_part_limit, t->user_part_limit + UA * Pn); if (int rc = upload(h, b[LM_UPL], upl)) return rc; }
-  if (h->lim_has_apl) { apl.assign(t->acct_part_limit, t->acct_part_limit + A * Pn); if (int rc = upload(h, b[LM_APL], apl)) return rc; }
+  if (h->lim_has_upl) { upl.assign(t->user_part_limit, t->user_part_limit + S.len[1]); if (int rc = upload(h, b[LM_UPL], upl)) return rc; }
+  if (h->lim_has_apl) { apl.assign(t->acct_part_limit, t->acct_part_limit + S.len[3]); if (int rc = upload(h, b[LM_APL], apl)) return rc; }
   if (int rc = upload(h, b[LM_USAGE0], usage)) return rc;
   if (int rc = upload(h, b[LM_EXISTS0], exists)) return rc;
   HIPCHK(h, b[LM_USAGE].ensure(usage.size() * 8));
   HIPCHK(h, b[LM_EXISTS].ensure(exists.size()));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->lim_U = (u32)U; h->lim_UA = (u32)UA; h->lim_A = (u32)A; h->lim_Q = (u32)Q; h->lim_Pn = (u32)Pn; h->lim_NR = NR;
+  h->lim_sp = S;
   h->lim_level = level;
   h->lim_have_tables = true;
   return CNS_OK;
@@ -162,17 +128,7 @@ int cns_upload_limit_jobs(cns_handle* h, const cns_limit_job_soa* jb) {
   if (!h->have_jobs) return fail(h, CNS_ERR_STATE, "cns_upload_limit_jobs before cns_upload_jobs / cns_select");
   h->lim_have_jobs = h->lim_have_run = false;
   const u64 J = jb->num_jobs;
-  if (J && (!jb->user || !jb->user_acct || !jb->account || !jb->qos || !jb->partition || !jb->time_limit_sec))
-    return fail(h, CNS_ERR_INVALID_ARG, "cns_upload_limit_jobs: missing array");
-  if (J > 0xFFFFFFF0ull) return fail(h, CNS_ERR_UNSUPPORTED, "more than 2^32-16 jobs");
-  for (u64 i = 0; i < J; ++i) {
-    if (jb->skip && jb->skip[i]) continue;
-    if (jb->user[i] >= h->lim_U || jb->user_acct[i] >= h->lim_UA || jb->account[i] >= h->lim_A || jb->qos[i] >= h->lim_Q ||
-        jb->partition[i] >= h->lim_Pn)
-      return fail(h, CNS_ERR_INVALID_ARG, "limit job " + std::to_string(i) + ": user / user_acct / account / qos / partition out of range");
-    if ((jb->select_index ? jb->select_index[i] : i) >= h->q.J)
-      return fail(h, CNS_ERR_INVALID_ARG, "limit job " + std::to_string(i) + ": select_index outside the last cns_select");
-  }
+  if (const auto v = cns_limits_host::check_jobs(h->lim_sp, jb, h->q.J)) return fail(h, v.code, v.msg);
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
   DevBuf* b = h->d_lim;
@@ -220,8 +176,9 @@ int cns_run_limits_resident(cns_handle* h) {
   DevBuf* b = h->d_lim;
   LimParams P;
   memset(&P, 0, sizeof P);
-  P.J = h->lim_J; P.Q = h->lim_Q; P.Pn = h->lim_Pn;
-  P.base_uq = h->lim_base[0]; P.base_up = h->lim_base[1]; P.base_aq = h->lim_base[2]; P.base_ap = h->lim_base[3]; P.base_g = h->lim_base[4];
+  const cns_acct::Space& S = h->lim_sp;
+  P.J = h->lim_J; P.Q = (u32)S.Q; P.Pn = (u32)S.Pn;
+  P.base_uq = (u32)S.base[0]; P.base_up = (u32)S.base[1]; P.base_aq = (u32)S.base[2]; P.base_ap = (u32)S.base[3]; P.base_g = (u32)S.base[4];
   P.sel = h->lim_has_sel ? b[LM_SEL].as<u64>() : nullptr;
   P.user = b[LM_USER].as<u32>(); P.ua = b[LM_UA].as<u32>(); P.account = b[LM_ACCT].as<u32>(); P.qos = b[LM_QOS].as<u32>(); P.part = b[LM_PART].as<u32>();
   P.tl = b[LM_TL].as<i64>(); P.skip = h->lim_has_skip ? b[LM_SKIP].as<uint8_t>() : nullptr;
@@ -246,10 +203,10 @@ int cns_run_limits_resident(cns_handle* h) {
   const u32 nb = (u32)((h->lim_J + 255) / 256);
   const char* mode_env = getenv("CNS_LIMITS_MODE");   // "seq": force the ordered single-wave kernel (tests cover both)
   const bool force_seq = mode_env && std::string(mode_env) == "seq";
-  P.NR = (u32)h->lim_NR;
+  P.NR = (u32)S.NR;
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  HIPCHK(h, hipMemcpyAsync(b[LM_USAGE].p, b[LM_USAGE0].p, std::max<u64>(h->lim_NR, 1) * 128, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(b[LM_EXISTS].p, b[LM_EXISTS0].p, std::max<u64>(h->lim_NR, 1), hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(b[LM_USAGE].p, b[LM_USAGE0].p, std::max<u64>(S.NR, 1) * 128, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(b[LM_EXISTS].p, b[LM_EXISTS0].p, std::max<u64>(S.NR, 1), hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipMemsetAsync(b[LM_CTR].p, 0, 32, h->stream));   // total, admitted, n_items, undecided
   u64 res[2] = {0, 0};
   u32 rounds = 0;
@@ -263,7 +220,7 @@ int cns_run_limits_resident(cns_handle* h) {
   const u64 M = res[0];
   const u64 n = M * 16;
   DevBuf* pb = h->d_limpar;
-  const bool par = M > 0 && !force_seq && n < 0xFFFFFFF0ull;
+  const bool par = M > 0 && !force_seq && n < cns_acct::kMaxRecords;
   if (par) {
     HIPCHK(h, pb[LP_K0].ensure(n * 8));
     P.item_key = pb[LP_K0].as<u64>();
@@ -282,7 +239,7 @@ int cns_run_limits_resident(cns_handle* h) {
     // (candidate, slot) items sorted by usage record, stable: inside a record the candidates stay in commit-loop order
     u64* kin = pb[LP_K0].as<u64>(); u64* kout = pb[LP_K1].as<u64>();
     u32* vin = pb[LP_V0].as<u32>(); u32* vout = pb[LP_V1].as<u32>();
-    sort_index_pairs(h->stream, n32, cns_sort::key_passes(h->lim_NR), kin, vin, kout, vout, pb[LP_HIST].as<u32>());
+    sort_index_pairs(h->stream, n32, cns_sort::key_passes(h->lim_sp.NR), kin, vin, kout, vout, pb[LP_HIST].as<u32>());
     ParParams R;
     memset(&R, 0, sizeof R);
     u64* ctr = b[LM_CTR].as<u64>();
@@ -382,18 +339,18 @@ int cns_get_usage(cns_handle* h, cns_usage* uq, uint8_t* uqe, cns_usage* up, uin
   if (!h) return fail(h, CNS_ERR_INVALID_ARG, "cns_get_usage: null handle");
   if (!h->lim_have_run) return fail(h, CNS_ERR_STATE, "cns_get_usage before a successful admission run");
   HIPCHK(h, hipSetDevice(h->device));
-  const u64 NR = std::max<u64>(h->lim_NR, 1);
+  const cns_acct::Space& S = h->lim_sp;
+  const u64 NR = std::max<u64>(S.NR, 1);
   std::vector<i64> usage(NR * 16);
   std::vector<uint8_t> exists(NR);
   HIPCHK(h, hipMemcpy(usage.data(), h->d_lim[LM_USAGE].p, NR * 128, hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpy(exists.data(), h->d_lim[LM_EXISTS].p, NR, hipMemcpyDeviceToHost));
   const LimCompMap m = lim_comp_map(h);
-  const u64 cnt[5] = {(u64)h->lim_U * h->lim_Q, (u64)h->lim_UA * h->lim_Pn, (u64)h->lim_A * h->lim_Q, (u64)h->lim_A * h->lim_Pn, h->lim_Q};
   cns_usage* outs[5] = {uq, up, aq, ap, qu};
   uint8_t* exs[5] = {uqe, upe, aqe, ape, nullptr};
   for (u32 tb = 0; tb < 5; ++tb)
-    for (u64 i = 0; i < cnt[tb]; ++i) {
-      const u64 r = h->lim_base[tb] + i;
+    for (u64 i = 0; i < S.len[tb]; ++i) {
+      const u64 r = S.base[tb] + i;
       if (outs[tb]) lim_unpack_usage(m, usage.data() + r * 16, outs[tb] + i);
       if (exs[tb]) exs[tb][i] = exists[r];
     }

@@ -7,76 +7,32 @@
 int cns_set_submit_limits(cns_handle* h, const cns_submit_tables* t) {
   if (!h || !t) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: null argument");
   h->sub_have = false;
-  const u64 U = t->num_users, UA = t->num_user_accts, A = t->num_accounts, Q = t->num_qos, Pn = t->num_partitions, L = t->num_part_limits;
-  if ((Q && !t->qos) || (A && !t->acct_parent) || (L && !t->part_limits)) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: missing table");
-  if (t->gres.num_classes > CNS_MAX_GRES_CLASSES) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: gres.num_classes > 8");
-  for (u32 g = 0; g < t->gres.num_classes; ++g)
-    if (t->gres.class_name[g] >= CNS_MAX_GRES_NAMES) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: gres class name id >= 4");
-  const u64 n_uq = U * Q, n_up = UA * Pn, n_aq = A * Q, n_ap = A * Pn;
-  const u64 NR = n_uq + n_up + n_aq + n_ap + Q, NE = U + A + Q;
-  if (n_uq > 0xFFFFFFF0ull || n_up > 0xFFFFFFF0ull || n_aq > 0xFFFFFFF0ull || n_ap > 0xFFFFFFF0ull || NR + NE >= 0xFFFFFFF0ull)
-    return fail(h, CNS_ERR_UNSUPPORTED, "cns_set_submit_limits: more than 2^32 - 16 records");
-  for (u64 a = 0; a < A; ++a) {
-    const u32 p = t->acct_parent[a];
-    if (p != CNS_LIM_NONE && p >= A) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: acct_parent out of range");
-  }
-  for (u64 a = 0; a < A; ++a) {
-    u64 depth = 0;
-    for (u32 x = (u32)a; x != CNS_LIM_NONE && depth <= A; x = t->acct_parent[x]) ++depth;
-    if (depth > A) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: the chain of account " + std::to_string(a) + " does not end");
-    if (depth > CNS_LIM_MAX_CHAIN) return fail(h, CNS_ERR_UNSUPPORTED, "cns_set_submit_limits: account " + std::to_string(a) + ": a chain of more than 6 accounts");
-  }
-  for (int w = 0; w < 2; ++w) {
-    const u32* m = w ? t->acct_part_limit : t->user_part_limit;
-    const u64 n = w ? n_ap : n_up;
-    if (m)
-      for (u64 i = 0; i < n; ++i)
-        if (m[i] != CNS_LIM_NONE && m[i] >= L) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: partition limit index out of range");
-  }
-  {
-    const cns_usage* tabs[5] = {t->user_qos, t->user_part, t->acct_qos, t->acct_part, t->qos_usage};
-    const u64 lens[5] = {n_uq, n_up, n_aq, n_ap, Q};
-    for (int w = 0; w < 5; ++w)
-      if (tabs[w])
-        for (u64 i = 0; i < lens[w]; ++i)
-          if (tabs[w][i].jobs_count == 0xFFFFFFFFu) return fail(h, CNS_ERR_INVALID_ARG, "cns_set_submit_limits: a jobs_count of UINT32_MAX");
-  }
+  cns_acct::Space S;
+  if (const auto v = cns_submit_host::check_tables(t, &S)) return fail(h, v.code, v.msg);
   // the table: five count tables back to back, then one exists value per user, account, QoS
-  std::vector<u32> st((size_t)(NR + NE), 0u);
+  std::vector<u32> st((size_t)(S.NR + S.NE), 0u);
   u32 mx = 0;
-  {
-    const u32* cnt[5] = {t->user_qos_submit, t->user_part_submit, t->acct_qos_submit, t->acct_part_submit, t->qos_submit};
-    const u64 lens[5] = {n_uq, n_up, n_aq, n_ap, Q};
-    u64 off = 0;
-    for (int w = 0; w < 5; ++w) {
-      h->sub_base[w] = (u32)off;
-      if (cnt[w])
-        for (u64 i = 0; i < lens[w]; ++i) { st[(size_t)(off + i)] = cnt[w][i]; mx = std::max(mx, cnt[w][i]); }
-      off += lens[w];
-    }
-    const uint8_t* ex[3] = {t->user_exists, t->acct_exists, t->qos_exists};
-    const u64 elen[3] = {U, A, Q};
-    for (int w = 0; w < 3; ++w) {
-      h->sub_ent[w] = (u32)off;
-      if (ex[w])
-        for (u64 i = 0; i < elen[w]; ++i) st[(size_t)(off + i)] = ex[w][i] ? 1u : 0u;
-      off += elen[w];
-    }
-  }
+  const u32* cnt[5] = {t->user_qos_submit, t->user_part_submit, t->acct_qos_submit, t->acct_part_submit, t->qos_submit};
+  for (int w = 0; w < 5; ++w)
+    if (cnt[w])
+      for (u64 i = 0; i < S.len[w]; ++i) { st[(size_t)(S.base[w] + i)] = cnt[w][i]; mx = std::max(mx, cnt[w][i]); }
+  const uint8_t* ex[3] = {t->user_exists, t->acct_exists, t->qos_exists};
+  for (int w = 0; w < 3; ++w)
+    if (ex[w])
+      for (u64 i = 0; i < S.ent_len[w]; ++i) st[(size_t)(S.ent[w] + i)] = ex[w][i] ? 1u : 0u;
   HIPCHK(h, hipSetDevice(h->device));
   DevBuf* B = h->d_sub;
   int rc = 0;
-  if ((rc = stage(h, B[SB_QOS], t->qos, (size_t)Q * sizeof(cns_submit_qos))) || (rc = stage(h, B[SB_PL], t->part_limits, (size_t)L * sizeof(cns_submit_part_limit))) ||
-      (rc = stage(h, B[SB_PARENT], t->acct_parent, (size_t)A * 4)) || (rc = stage(h, B[SB_UPL], t->user_part_limit, (size_t)n_up * 4)) ||
-      (rc = stage(h, B[SB_APL], t->acct_part_limit, (size_t)n_ap * 4)) || (rc = stage(h, B[SB_UQ], t->user_qos, (size_t)n_uq * sizeof(cns_usage))) ||
-      (rc = stage(h, B[SB_AQ], t->acct_qos, (size_t)n_aq * sizeof(cns_usage))) || (rc = stage(h, B[SB_G], t->qos_usage, (size_t)Q * sizeof(cns_usage))) ||
+  if ((rc = stage(h, B[SB_QOS], t->qos, (size_t)S.Q * sizeof(cns_submit_qos))) || (rc = stage(h, B[SB_PL], t->part_limits, (size_t)t->num_part_limits * sizeof(cns_submit_part_limit))) ||
+      (rc = stage(h, B[SB_PARENT], t->acct_parent, (size_t)S.A * 4)) || (rc = stage(h, B[SB_UPL], t->user_part_limit, (size_t)S.len[1] * 4)) ||
+      (rc = stage(h, B[SB_APL], t->acct_part_limit, (size_t)S.len[3] * 4)) || (rc = stage(h, B[SB_UQ], t->user_qos, (size_t)S.len[0] * sizeof(cns_usage))) ||
+      (rc = stage(h, B[SB_AQ], t->acct_qos, (size_t)S.len[2] * sizeof(cns_usage))) || (rc = stage(h, B[SB_G], t->qos_usage, (size_t)S.len[4] * sizeof(cns_usage))) ||
       (rc = stage(h, B[SB_ST_SET], st.data(), st.size() * 4)) || (rc = stage(h, B[SB_ST], st.data(), st.size() * 4))) {
     drain(h);
     return rc;
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->sub_U = (u32)U; h->sub_UA = (u32)UA; h->sub_A = (u32)A; h->sub_Q = (u32)Q; h->sub_Pn = (u32)Pn;
-  h->sub_NR = (u32)NR; h->sub_NE = (u32)NE;
+  h->sub_sp = S;
   h->sub_has_upl = t->user_part_limit != nullptr; h->sub_has_apl = t->acct_part_limit != nullptr;
   h->sub_has_uq = t->user_qos != nullptr; h->sub_has_aq = t->acct_qos != nullptr; h->sub_has_g = t->qos_usage != nullptr;
   h->sub_lay = t->gres;
@@ -88,23 +44,9 @@ int cns_set_submit_limits(cns_handle* h, const cns_submit_tables* t) {
 
 static int submit_impl(cns_handle* h, const cns_job_soa* jb, const cns_submit_keys* ky, u32 flags, const cns_submit_out* out) {
   const u32 J = (u32)jb->num_jobs;
-  if (!jb->partition || !jb->time_limit_sec || !jb->node_mem || !jb->task_cpu_raw || !jb->task_mem || !jb->node_num || !jb->ntasks)
-    return fail(h, CNS_ERR_INVALID_ARG, "cns_check_submissions: missing job array");
-  if (!ky->user || !ky->user_acct || !ky->account || !ky->qos || !ky->count) return fail(h, CNS_ERR_INVALID_ARG, "cns_check_submissions: missing key array");
-  if (!out->code || !out->time_limit_out) return fail(h, CNS_ERR_INVALID_ARG, "cns_check_submissions: missing result array");
+  const cns_acct::Space& S = h->sub_sp;
+  if (const auto v = cns_submit_host::check_jobs(S, jb, ky, out, flags, h->sub_max_set, h->sub_max_cur)) return fail(h, v.code, v.msg);
   const bool carry = (flags & CNS_SUBMIT_CARRY) != 0;
-  // ---- the validating pass: indices of the jobs that are not skipped, and the input rule on the 32-bit counts ----
-  u64 total = 0;
-  for (u32 j = 0; j < J; ++j) {
-    if (ky->skip && ky->skip[j]) continue;
-    if (ky->user[j] >= h->sub_U || ky->account[j] >= h->sub_A || ky->qos[j] >= h->sub_Q || jb->partition[j] >= h->sub_Pn ||
-        (ky->user_acct[j] != CNS_LIM_NONE && ky->user_acct[j] >= h->sub_UA))
-      return fail(h, CNS_ERR_INVALID_ARG, "cns_check_submissions: job " + std::to_string(j) + ": a key index out of range");
-    total += ky->count[j];
-  }
-  if ((u64)(carry ? h->sub_max_cur : h->sub_max_set) + total > 0xFFFFFFFFull)
-    return fail(h, CNS_ERR_UNSUPPORTED, "cns_check_submissions: the largest submit count + the sum of count over the call exceeds UINT32_MAX");
-
   HIPCHK(h, hipSetDevice(h->device));
   DevBuf* B = h->d_sub;
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
@@ -117,7 +59,7 @@ static int submit_impl(cns_handle* h, const cns_job_soa* jb, const cns_submit_ke
     for (const auto& u : ups)
       if (int rc = stage(h, B[u.b], u.p, (size_t)J * u.sz)) return rc;
   }
-  const u32 NK = h->sub_NR + h->sub_NE;
+  const u32 NR = (u32)S.NR, NK = (u32)(S.NR + S.NE);
   const size_t n = (size_t)J * kSubItems;
   HIPCHK(h, B[SB_PRE].ensure(J)); HIPCHK(h, B[SB_STATE].ensure(J)); HIPCHK(h, B[SB_STAT].ensure((size_t)J * 8)); HIPCHK(h, B[SB_COND].ensure((size_t)J * 8));
   HIPCHK(h, B[SB_IKEY].ensure(n * 4)); HIPCHK(h, B[SB_ITHR].ensure(n * 4)); HIPCHK(h, B[SB_CODE].ensure(J)); HIPCHK(h, B[SB_TLO].ensure((size_t)J * 8));
@@ -130,9 +72,9 @@ static int submit_impl(cns_handle* h, const cns_job_soa* jb, const cns_submit_ke
 
   SubParams P;
   memset(&P, 0, sizeof P);
-  P.J = J; P.Q = h->sub_Q; P.Pn = h->sub_Pn; P.NK = NK;
-  P.base_uq = h->sub_base[0]; P.base_up = h->sub_base[1]; P.base_aq = h->sub_base[2]; P.base_ap = h->sub_base[3]; P.base_g = h->sub_base[4];
-  P.ent_user = h->sub_ent[0]; P.ent_acct = h->sub_ent[1]; P.ent_qos = h->sub_ent[2];
+  P.J = J; P.Q = (u32)S.Q; P.Pn = (u32)S.Pn; P.NK = NK;
+  P.base_uq = (u32)S.base[0]; P.base_up = (u32)S.base[1]; P.base_aq = (u32)S.base[2]; P.base_ap = (u32)S.base[3]; P.base_g = (u32)S.base[4];
+  P.ent_user = (u32)S.ent[0]; P.ent_acct = (u32)S.ent[1]; P.ent_qos = (u32)S.ent[2];
   P.part = B[SB_JPART].as<u32>(); P.tl = B[SB_JTL].as<i64>(); P.ncpu = jb->node_cpu_raw ? B[SB_JNCPU].as<i64>() : nullptr; P.nmem = B[SB_JNMEM].as<u64>();
   P.tcpu = B[SB_JTCPU].as<i64>(); P.tmem = B[SB_JTMEM].as<u64>(); P.k = B[SB_JK].as<u32>(); P.nt = B[SB_JNT].as<u32>();
   P.gt = jb->gres_total ? B[SB_JGT].as<u32>() : nullptr; P.gs = jb->gres_spec ? B[SB_JGS].as<u64>() : nullptr;
@@ -200,7 +142,7 @@ static int submit_impl(cns_handle* h, const cns_job_soa* jb, const cns_submit_ke
     }
   }
   if (!decided) hipLaunchKernelGGL(k_sub_admit, dim3(1), dim3(64), 0, h->stream, P);   // CNS_SUBMIT_MODE=seq, or a chain the rounds did not finish
-  if (h->sub_NR) hipLaunchKernelGGL(k_sub_max, dim3((h->sub_NR + 255) / 256), dim3(256), 0, h->stream, (const u32*)P.st, h->sub_NR, P.ctr);
+  if (NR) hipLaunchKernelGGL(k_sub_max, dim3((NR + 255) / 256), dim3(256), 0, h->stream, (const u32*)P.st, NR, P.ctr);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -240,20 +182,17 @@ int cns_get_submit_usage(cns_handle* h, uint32_t* user_qos_submit, uint32_t* use
   if (!h) return fail(h, CNS_ERR_INVALID_ARG, "cns_get_submit_usage: null handle");
   if (!h->sub_have) return fail(h, CNS_ERR_STATE, "cns_get_submit_usage before cns_set_submit_limits");
   HIPCHK(h, hipSetDevice(h->device));
-  std::vector<u32> st((size_t)h->sub_NR + h->sub_NE);
+  const cns_acct::Space& S = h->sub_sp;
+  std::vector<u32> st((size_t)(S.NR + S.NE));
   if (!st.empty()) HIPCHK(h, hipMemcpyAsync(st.data(), h->d_sub[SB_ST].p, st.size() * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   uint32_t* cnt[5] = {user_qos_submit, user_part_submit, acct_qos_submit, acct_part_submit, qos_submit};
-  for (int w = 0; w < 5; ++w) {
-    const size_t beg = h->sub_base[w], end = w < 4 ? h->sub_base[w + 1] : h->sub_NR;
-    if (cnt[w] && end > beg) memcpy(cnt[w], st.data() + beg, (end - beg) * 4);
-  }
+  for (int w = 0; w < 5; ++w)
+    if (cnt[w] && S.len[w]) memcpy(cnt[w], st.data() + S.base[w], S.len[w] * 4);
   uint8_t* ex[3] = {user_exists, acct_exists, qos_exists};
-  for (int w = 0; w < 3; ++w) {
-    const size_t beg = h->sub_ent[w], end = w < 2 ? h->sub_ent[w + 1] : st.size();
+  for (int w = 0; w < 3; ++w)
     if (ex[w])
-      for (size_t i = beg; i < end; ++i) ex[w][i - beg] = st[i] ? 1 : 0;
-  }
+      for (u64 i = 0; i < S.ent_len[w]; ++i) ex[w][i] = st[S.ent[w] + i] ? 1 : 0;
   return CNS_OK;
 }
 

@@ -7,52 +7,32 @@
 #include <string>
 
 #include "../../include/crane_gpu_usage/usage.h"
+#include "acct_space_host.inc"
 
 namespace cns_usage_host {
 
-constexpr uint64_t kMaxRecords = 0xFFFFFFF0ull;   // record ids and the "no record" key stay a uint32
-
-struct Verdict {
-  int code = 0;   // CNS_OK, CNS_ERR_INVALID_ARG or CNS_ERR_UNSUPPORTED
-  std::string msg;
-  explicit operator bool() const { return code != 0; }
-};
-struct Dims {
-  uint64_t U = 0, UA = 0, A = 0, Q = 0, Pn = 0;
-  uint64_t len[5] = {0, 0, 0, 0, 0};   // records of user_qos, user_part, acct_qos, acct_part, qos_usage
-  uint64_t NR = 0, NE = 0;             // records, entities
-};
+using cns_acct::kMaxRecords;
+using cns_acct::Verdict;
+using Dims = cns_acct::Space;   // the record space of the tables (acct_space_host.inc)
 
 inline Verdict refuse(const char* call, int code, std::string msg) {
-  Verdict v;
-  v.code = code; v.msg = std::string(call) + ": " + std::move(msg);
-  return v;
+  return cns_acct::refuse(code, std::string(call) + ": " + std::move(msg));
 }
 
 inline Verdict check_tables(const cns_usage_tables* t, Dims* dims) {
   const char* C = "cns_usage_set_tables";
-  Dims D;
-  D.U = t->num_users; D.UA = t->num_user_accts; D.A = t->num_accounts; D.Q = t->num_qos; D.Pn = t->num_partitions;
-  if (D.A && !t->acct_parent) return refuse(C, CNS_ERR_INVALID_ARG, "missing array: acct_parent");
+  if (t->num_accounts && !t->acct_parent) return refuse(C, CNS_ERR_INVALID_ARG, "missing array: acct_parent");
   if (t->gres.num_classes > CNS_MAX_GRES_CLASSES) return refuse(C, CNS_ERR_INVALID_ARG, "gres.num_classes > 8");
   for (uint32_t g = 0; g < t->gres.num_classes; ++g)
     if (t->gres.class_name[g] >= CNS_MAX_GRES_NAMES) return refuse(C, CNS_ERR_INVALID_ARG, "gres class name id >= 4");
-  D.len[0] = D.U * D.Q; D.len[1] = D.UA * D.Pn; D.len[2] = D.A * D.Q; D.len[3] = D.A * D.Pn; D.len[4] = D.Q;
-  for (int w = 0; w < 5; ++w) {
-    if (D.len[w] > kMaxRecords) return refuse(C, CNS_ERR_UNSUPPORTED, "more than 2^32 - 16 records");
-    D.NR += D.len[w];
-  }
-  D.NE = D.U + D.A + D.Q;
-  if (D.NR + D.NE >= kMaxRecords) return refuse(C, CNS_ERR_UNSUPPORTED, "more than 2^32 - 16 records");
-  for (uint64_t a = 0; a < D.A; ++a) {
-    const uint32_t p = t->acct_parent[a];
-    if (p != CNS_LIM_NONE && p >= D.A) return refuse(C, CNS_ERR_INVALID_ARG, "acct_parent[" + std::to_string(a) + "] out of range");
-  }
-  for (uint64_t a = 0; a < D.A; ++a) {
-    uint64_t depth = 0;
-    for (uint32_t x = (uint32_t)a; x != CNS_LIM_NONE && depth <= D.A; x = t->acct_parent[x]) ++depth;
-    if (depth > D.A) return refuse(C, CNS_ERR_INVALID_ARG, "the chain of account " + std::to_string(a) + " does not end");
-    if (depth > CNS_LIM_MAX_CHAIN) return refuse(C, CNS_ERR_UNSUPPORTED, "account " + std::to_string(a) + ": a chain of more than 6 accounts");
+  Dims D;
+  if (!cns_acct::make_space(t->num_users, t->num_user_accts, t->num_accounts, t->num_qos, t->num_partitions, &D) || D.NR + D.NE >= kMaxRecords)
+    return refuse(C, CNS_ERR_UNSUPPORTED, "more than 2^32 - 16 records");
+  if (const auto f = cns_acct::walk_chains(t->acct_parent, D.A, true, nullptr)) {
+    const std::string a = std::to_string(f.account);
+    if (f.what == cns_acct::ChainFinding::kParentRange) return refuse(C, CNS_ERR_INVALID_ARG, "acct_parent[" + a + "] out of range");
+    if (f.what == cns_acct::ChainFinding::kNoEnd) return refuse(C, CNS_ERR_INVALID_ARG, "the chain of account " + a + " does not end");
+    return refuse(C, CNS_ERR_UNSUPPORTED, "account " + a + ": a chain of more than 6 accounts");
   }
   const cns_usage* tabs[5] = {t->user_qos, t->user_part, t->acct_qos, t->acct_part, t->qos_usage};
   for (int w = 0; w < 5; ++w)
@@ -75,8 +55,7 @@ inline Verdict check_jobs(const Dims& D, const cns_usage_jobs* jb, const cns_usa
   for (uint64_t j = 0; j < J; ++j) {
     if (jb->skip && jb->skip[j]) continue;
     const std::string row = "job " + std::to_string(j) + ": ";
-    if (jb->user[j] >= D.U || jb->account[j] >= D.A || jb->qos[j] >= D.Q || jb->partition[j] >= D.Pn ||
-        (jb->user_acct[j] != CNS_LIM_NONE && jb->user_acct[j] >= D.UA))
+    if (!cns_acct::keys_in_range(D, jb->user[j], jb->user_acct[j], jb->account[j], jb->qos[j], jb->partition[j], true))
       return refuse(C, CNS_ERR_INVALID_ARG, row + "a key index out of range");
     if (op == CNS_USAGE_CHARGE && jb->user_acct[j] == CNS_LIM_NONE) return refuse(C, CNS_ERR_INVALID_ARG, row + "a charge without a user_acct");
     if ((jb->cpu_raw && jb->cpu_raw[j] < 0) || (jb->wall_sec && jb->wall_sec[j] < 0)) return refuse(C, CNS_ERR_INVALID_ARG, row + "a negative cpu_raw or wall_sec");

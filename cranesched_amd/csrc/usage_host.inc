@@ -6,12 +6,12 @@
 // Three copies of the table: US_TAB_SET (as set), US_TAB_CUR (after the last call that succeeded), US_TAB_WORK (the call's output:
 // a copy of its source that the kernels write into; swapped with CUR when the call succeeded, so a refused charge leaves CUR alone).
 
-static size_t use_tab_bytes(const cns_engine* h) { return (size_t)h->use_dims.NR * kUseComp * 8 + (size_t)(h->use_dims.NR + h->use_dims.NE); }
+static size_t use_tab_bytes(const cns_engine* h) { return (size_t)h->use_sp.NR * kUseComp * 8 + (size_t)(h->use_sp.NR + h->use_sp.NE); }
 
 int cns_usage_set_tables(cns_handle* h, const cns_usage_tables* t) {
   if (!h || !t) return fail(h, CNS_ERR_INVALID_ARG, "cns_usage_set_tables: null argument");
   h->use_have = h->use_have_cur = false;
-  cns_usage_host::Dims D;
+  cns_acct::Space D;
   if (const auto v = cns_usage_host::check_tables(t, &D)) return fail(h, v.code, v.msg);
   // records [NR][17], then the exists bytes [NR] (1 for the qos records), then the entity bytes [NE]
   std::vector<u64> tab(((size_t)D.NR * kUseComp * 8 + (size_t)(D.NR + D.NE) + 7) / 8, 0ull);
@@ -20,9 +20,8 @@ int cns_usage_set_tables(cns_handle* h, const cns_usage_tables* t) {
     const cns_usage* use[5] = {t->user_qos, t->user_part, t->acct_qos, t->acct_part, t->qos_usage};
     const u32* sub[5] = {t->user_qos_submit, t->user_part_submit, t->acct_qos_submit, t->acct_part_submit, t->qos_submit};
     const uint8_t* nex[5] = {t->user_qos_exists, t->user_part_exists, t->acct_qos_exists, t->acct_part_exists, nullptr};
-    u64 off = 0;
     for (int w = 0; w < 5; ++w) {
-      h->use_base[w] = (u32)off;
+      const u64 off = D.base[w];
       for (u64 i = 0; i < D.len[w]; ++i) {
         const bool exists = w == 4 || (nex[w] ? nex[w][i] != 0 : (use[w] || sub[w]));
         ex[off + i] = exists ? 1 : 0;
@@ -36,16 +35,11 @@ int cns_usage_set_tables(cns_handle* h, const cns_usage_tables* t) {
         }
         if (sub[w]) r[4] = sub[w][i];
       }
-      off += D.len[w];
     }
     const uint8_t* ent[3] = {t->user_exists, t->acct_exists, t->qos_exists};
-    const u64 elen[3] = {D.U, D.A, D.Q};
-    for (int w = 0; w < 3; ++w) {
-      h->use_ent[w] = (u32)off;
+    for (int w = 0; w < 3; ++w)
       if (ent[w])
-        for (u64 i = 0; i < elen[w]; ++i) ex[off + i] = ent[w][i] ? 1 : 0;
-      off += elen[w];
-    }
+        for (u64 i = 0; i < D.ent_len[w]; ++i) ex[D.ent[w] + i] = ent[w][i] ? 1 : 0;
   }
   HIPCHK(h, hipSetDevice(h->device));
   DevBuf* B = h->d_use;
@@ -57,14 +51,14 @@ int cns_usage_set_tables(cns_handle* h, const cns_usage_tables* t) {
     return rc;
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->use_dims = D;
+  h->use_sp = D;
   h->use_timing = cns_usage_timing{};
   h->use_have = true;
   return CNS_OK;
 }
 
 static int usage_impl(cns_handle* h, u32 op, const cns_usage_jobs* jb, u32 flags, const cns_usage_out* out) {
-  const cns_usage_host::Dims& D = h->use_dims;
+  const cns_acct::Space& D = h->use_sp;
   const u32 J = (u32)jb->num_jobs;
   const bool carry = (flags & CNS_USAGE_CARRY) != 0;
   HIPCHK(h, hipSetDevice(h->device));
@@ -92,8 +86,8 @@ static int usage_impl(cns_handle* h, u32 op, const cns_usage_jobs* jb, u32 flags
   UseParams P;
   memset(&P, 0, sizeof P);
   P.J = J; P.op = op; P.Q = (u32)D.Q; P.Pn = (u32)D.Pn; P.NK = NK;
-  P.base_uq = h->use_base[0]; P.base_up = h->use_base[1]; P.base_aq = h->use_base[2]; P.base_ap = h->use_base[3]; P.base_g = h->use_base[4];
-  P.ent_user = h->use_ent[0]; P.ent_acct = h->use_ent[1]; P.ent_qos = h->use_ent[2];
+  P.base_uq = (u32)D.base[0]; P.base_up = (u32)D.base[1]; P.base_aq = (u32)D.base[2]; P.base_ap = (u32)D.base[3]; P.base_g = (u32)D.base[4];
+  P.ent_user = (u32)D.ent[0]; P.ent_acct = (u32)D.ent[1]; P.ent_qos = (u32)D.ent[2];
   P.user = B[US_JUSER].as<u32>(); P.ua = B[US_JUA].as<u32>(); P.account = B[US_JACCT].as<u32>(); P.qos = B[US_JQOS].as<u32>(); P.part = B[US_JPART].as<u32>();
   P.cpu = jb->cpu_raw ? B[US_JCPU].as<i64>() : nullptr; P.mem = jb->mem ? B[US_JMEM].as<u64>() : nullptr; P.wall = jb->wall_sec ? B[US_JWALL].as<i64>() : nullptr;
   P.jobs = jb->jobs_count ? B[US_JJOBS].as<u32>() : nullptr; P.submit = jb->submit_count ? B[US_JSUB].as<u32>() : nullptr;
@@ -117,7 +111,7 @@ static int usage_impl(cns_handle* h, u32 op, const cns_usage_jobs* jb, u32 flags
   HIPCHK(h, hipStreamSynchronize(h->stream));   // the number of items that carry a record sizes the scan's grids
   UsePar R;
   memset(&R, 0, sizeof R);
-  R.n = (u32)hc[0]; R.nchunks = (R.n + kUseItemChunk - 1) / kUseItemChunk; R.op = op; R.base_g = h->use_base[4];
+  R.n = (u32)hc[0]; R.nchunks = (R.n + kUseItemChunk - 1) / kUseItemChunk; R.op = op; R.base_g = (u32)D.base[4];
   if (R.n) {
     HIPCHK(h, B[US_TAILS].ensure((size_t)R.nchunks * kUseComp * 8)); HIPCHK(h, B[US_TFLAGS].ensure((size_t)R.nchunks * 4));
     HIPCHK(h, B[US_CARRY].ensure((size_t)R.nchunks * kUseComp * 8)); HIPCHK(h, B[US_CFLAGS].ensure((size_t)R.nchunks * 4));
@@ -161,7 +155,7 @@ int cns_usage_apply(cns_handle* h, uint32_t op, const cns_usage_jobs* jobs, uint
   if (!h->use_have) return fail(h, CNS_ERR_STATE, "cns_usage_apply before cns_usage_set_tables");
   if ((flags & CNS_USAGE_CARRY) && !h->use_have_cur) return fail(h, CNS_ERR_STATE, "cns_usage_apply: CNS_USAGE_CARRY before a first cns_usage_apply");
   if (jobs->num_jobs == 0) return CNS_OK;   // nothing asked, nothing written
-  if (const auto v = cns_usage_host::check_jobs(h->use_dims, jobs, out, op, nullptr)) return fail(h, v.code, v.msg);
+  if (const auto v = cns_usage_host::check_jobs(h->use_sp, jobs, out, op, nullptr)) return fail(h, v.code, v.msg);
   const int rc = usage_impl(h, op, jobs, flags, out);
   if (rc != 0) drain(h);   // nothing of the call is left in flight, the message survives
   return rc;
@@ -170,7 +164,7 @@ int cns_usage_apply(cns_handle* h, uint32_t op, const cns_usage_jobs* jobs, uint
 int cns_usage_get_tables(cns_handle* h, const cns_usage_tables_out* o) {
   if (!h || !o) return fail(h, CNS_ERR_INVALID_ARG, "cns_usage_get_tables: null argument");
   if (!h->use_have) return fail(h, CNS_ERR_STATE, "cns_usage_get_tables before cns_usage_set_tables");
-  const cns_usage_host::Dims& D = h->use_dims;
+  const cns_acct::Space& D = h->use_sp;
   HIPCHK(h, hipSetDevice(h->device));
   const size_t bytes = use_tab_bytes(h);
   std::vector<u64> tab((bytes + 7) / 8, 0ull);
@@ -181,7 +175,7 @@ int cns_usage_get_tables(cns_handle* h, const cns_usage_tables_out* o) {
   u32* sub[5] = {o->user_qos_submit, o->user_part_submit, o->acct_qos_submit, o->acct_part_submit, o->qos_submit};
   uint8_t* nex[5] = {o->user_qos_exists, o->user_part_exists, o->acct_qos_exists, o->acct_part_exists, nullptr};
   for (int w = 0; w < 5; ++w) {
-    const u64 off = h->use_base[w];
+    const u64 off = D.base[w];
     for (u64 i = 0; i < D.len[w]; ++i) {
       const u64* r = tab.data() + (size_t)(off + i) * kUseComp;
       if (use[w]) {
@@ -195,10 +189,9 @@ int cns_usage_get_tables(cns_handle* h, const cns_usage_tables_out* o) {
     }
   }
   uint8_t* ent[3] = {o->user_exists, o->acct_exists, o->qos_exists};
-  const u64 elen[3] = {D.U, D.A, D.Q};
   for (int w = 0; w < 3; ++w)
     if (ent[w])
-      for (u64 i = 0; i < elen[w]; ++i) ent[w][i] = ex[h->use_ent[w] + i];
+      for (u64 i = 0; i < D.ent_len[w]; ++i) ent[w][i] = ex[D.ent[w] + i];
   return CNS_OK;
 }
 

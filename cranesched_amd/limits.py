@@ -47,6 +47,38 @@ assert TRES_DT.itemsize == 120 and QOS_DT.itemsize == 392 and PART_LIMIT_DT.item
 
 _P = C.c_void_p
 
+# The record space the run limits, the submit limits and the usage tables share (csrc/acct_space_host.inc): five tables, a submit count
+# and an exists byte per record of each, an exists byte per user / account / QoS, and the two maps into part_limits.
+TABLES = ("user_qos", "user_part", "acct_qos", "acct_part", "qos_usage")
+SUBMITS = ("user_qos_submit", "user_part_submit", "acct_qos_submit", "acct_part_submit", "qos_submit")
+NESTED = ("user_qos_exists", "user_part_exists", "acct_qos_exists", "acct_part_exists")
+ENTITIES = ("user_exists", "acct_exists", "qos_exists")
+
+
+def table_shapes(t) -> dict:
+    """field -> (dtype, records) of every per-record array a tables class may carry."""
+    Q, A, U, UA, Pn = t.num_qos, t.num_accounts, t.num_users, t.num_user_accts, t.num_partitions
+    n = dict(zip(TABLES, (U * Q, UA * Pn, A * Q, A * Pn, Q)))
+    sh = {f: (USAGE_DT, n[f]) for f in TABLES}
+    sh.update({s: (np.uint32, n[f]) for s, f in zip(SUBMITS, TABLES)})
+    sh.update({e: (np.uint8, n[f]) for e, f in zip(NESTED, TABLES)})
+    sh.update(zip(ENTITIES, ((np.uint8, U), (np.uint8, A), (np.uint8, Q))))
+    sh.update({"user_part_limit": (np.uint32, n["user_part"]), "acct_part_limit": (np.uint32, n["acct_part"])})
+    return sh
+
+
+def coerce_tables(t) -> None:
+    """The per-record arrays of t that are given, in the order of its fields: contiguous, of their dtype, flat, as long as their table."""
+    sh = table_shapes(t)
+    for f in t.__dataclass_fields__:
+        v = getattr(t, f)
+        if f in sh and v is not None:
+            dt, n = sh[f]
+            v = np.ascontiguousarray(v, dt).reshape(-1)
+            if len(v) != n:
+                raise ValueError(f"{f}: expected {n} records, got {len(v)}")
+            setattr(t, f, v)
+
 
 class CnsLimitTables(C.Structure):
     _fields_ = [("num_users", C.c_uint32), ("num_user_accts", C.c_uint32), ("num_accounts", C.c_uint32),
@@ -135,19 +167,7 @@ class LimitTables:
         self.qos = np.ascontiguousarray(self.qos, QOS_DT).reshape(-1)
         self.acct_parent = np.ascontiguousarray(self.acct_parent, np.uint32)
         self.part_limits = np.ascontiguousarray(self.part_limits, PART_LIMIT_DT).reshape(-1)
-        Q, A, U, UA, Pn = len(self.qos), len(self.acct_parent), self.num_users, self.num_user_accts, self.num_partitions
-        shapes = {"user_part_limit": (np.uint32, UA * Pn), "acct_part_limit": (np.uint32, A * Pn),
-                  "user_qos": (USAGE_DT, U * Q), "user_qos_exists": (np.uint8, U * Q),
-                  "user_part": (USAGE_DT, UA * Pn), "user_part_exists": (np.uint8, UA * Pn),
-                  "acct_qos": (USAGE_DT, A * Q), "acct_qos_exists": (np.uint8, A * Q),
-                  "acct_part": (USAGE_DT, A * Pn), "acct_part_exists": (np.uint8, A * Pn), "qos_usage": (USAGE_DT, Q)}
-        for f, (dt, n) in shapes.items():
-            v = getattr(self, f)
-            if v is not None:
-                v = np.ascontiguousarray(v, dt).reshape(-1)
-                if len(v) != n:
-                    raise ValueError(f"{f}: expected {n} records, got {len(v)}")
-                setattr(self, f, v)
+        coerce_tables(self)
 
     @property
     def num_qos(self):
@@ -166,10 +186,8 @@ class LimitTables:
                               p(self.acct_part), p(self.acct_part_exists), p(self.qos_usage))
 
     def empty_usage(self) -> "Usage":
-        Q, A, U, UA, Pn = self.num_qos, self.num_accounts, self.num_users, self.num_user_accts, self.num_partitions
-        return Usage(np.zeros(U * Q, USAGE_DT), np.zeros(U * Q, np.uint8), np.zeros(UA * Pn, USAGE_DT),
-                     np.zeros(UA * Pn, np.uint8), np.zeros(A * Q, USAGE_DT), np.zeros(A * Q, np.uint8),
-                     np.zeros(A * Pn, USAGE_DT), np.zeros(A * Pn, np.uint8), np.zeros(Q, USAGE_DT))
+        sh = table_shapes(self)
+        return Usage(*[np.zeros(sh[f][1], sh[f][0]) for f in Usage.__dataclass_fields__])
 
 
 @dataclass

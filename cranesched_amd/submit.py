@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import abi
-from .limits import LIM_NONE, TRES_DT, UNLIMITED_CPU_RAW, UNLIMITED_JOBS, USAGE_DT, unlimited_tres
+from .limits import LIM_NONE, TRES_DT, UNLIMITED_CPU_RAW, UNLIMITED_JOBS, coerce_tables, table_shapes, unlimited_tres
 
 SUBMIT_QOS_DT = np.dtype([("max_submit_jobs_per_user", "<u4"), ("max_submit_jobs_per_account", "<u4"), ("max_submit_jobs", "<u4"),
                           ("max_jobs_per_user", "<u4"), ("max_jobs_per_account", "<u4"), ("max_jobs", "<u4"), ("deny_on_limit", "<u4"),
@@ -100,21 +100,7 @@ class SubmitTables:
         self.qos = np.ascontiguousarray(self.qos, SUBMIT_QOS_DT).reshape(-1)
         self.acct_parent = np.ascontiguousarray(self.acct_parent, np.uint32)
         self.part_limits = np.ascontiguousarray(self.part_limits, SUBMIT_PART_LIMIT_DT).reshape(-1)
-        for f, (dt, n) in self._shapes().items():
-            v = getattr(self, f)
-            if v is not None:
-                v = np.ascontiguousarray(v, dt).reshape(-1)
-                if len(v) != n:
-                    raise ValueError(f"{f}: expected {n} records, got {len(v)}")
-                setattr(self, f, v)
-
-    def _shapes(self):
-        Q, A, U, UA, Pn = len(self.qos), len(self.acct_parent), self.num_users, self.num_user_accts, self.num_partitions
-        return {"user_part_limit": (np.uint32, UA * Pn), "acct_part_limit": (np.uint32, A * Pn),
-                "user_qos": (USAGE_DT, U * Q), "user_part": (USAGE_DT, UA * Pn), "acct_qos": (USAGE_DT, A * Q), "acct_part": (USAGE_DT, A * Pn),
-                "qos_usage": (USAGE_DT, Q), "user_qos_submit": (np.uint32, U * Q), "user_part_submit": (np.uint32, UA * Pn),
-                "acct_qos_submit": (np.uint32, A * Q), "acct_part_submit": (np.uint32, A * Pn), "qos_submit": (np.uint32, Q),
-                "user_exists": (np.uint8, U), "acct_exists": (np.uint8, A), "qos_exists": (np.uint8, Q)}
+        coerce_tables(self)
 
     @property
     def num_qos(self):
@@ -134,7 +120,7 @@ class SubmitTables:
 
     def state(self) -> SubmitState:
         """The counters and exists bits as set (a copy; None = zeros)."""
-        sh = self._shapes()
+        sh = table_shapes(self)
         return SubmitState(*[np.zeros(sh[f][1], sh[f][0]) if getattr(self, f) is None else getattr(self, f).copy()
                              for f in SubmitState.__dataclass_fields__])
 

@@ -13,12 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import abi
-from .limits import LIM_NONE, USAGE_DT
-
-TABLES = ("user_qos", "user_part", "acct_qos", "acct_part", "qos_usage")
-SUBMITS = ("user_qos_submit", "user_part_submit", "acct_qos_submit", "acct_part_submit", "qos_submit")
-NESTED = ("user_qos_exists", "user_part_exists", "acct_qos_exists", "acct_part_exists")
-ENTITIES = ("user_exists", "acct_exists", "qos_exists")
+from .limits import ENTITIES, LIM_NONE, NESTED, SUBMITS, TABLES, USAGE_DT, coerce_tables, table_shapes
 
 
 @dataclass
@@ -90,26 +85,11 @@ class UsageTables:
 
     def __post_init__(self):
         self.acct_parent = np.ascontiguousarray(self.acct_parent, np.uint32)
-        for f, (dt, n) in self._shapes().items():
-            v = getattr(self, f)
-            if v is not None:
-                v = np.ascontiguousarray(v, dt).reshape(-1)
-                if len(v) != n:
-                    raise ValueError(f"{f}: expected {n} records, got {len(v)}")
-                setattr(self, f, v)
+        coerce_tables(self)
 
     @property
     def num_accounts(self):
         return len(self.acct_parent)
-
-    def _shapes(self):
-        Q, A, U, UA, Pn = self.num_qos, self.num_accounts, self.num_users, self.num_user_accts, self.num_partitions
-        n = {"user_qos": U * Q, "user_part": UA * Pn, "acct_qos": A * Q, "acct_part": A * Pn, "qos_usage": Q}
-        sh = {f: (USAGE_DT, n[f]) for f in TABLES}
-        sh.update({s: (np.uint32, n[f]) for s, f in zip(SUBMITS, TABLES)})
-        sh.update({e: (np.uint8, n[f]) for e, f in zip(NESTED, TABLES)})
-        sh.update({"user_exists": (np.uint8, U), "acct_exists": (np.uint8, A), "qos_exists": (np.uint8, Q)})
-        return sh
 
     def to_c(self) -> abi.CnsUsageTables:
         p = lambda a: None if a is None or len(a) == 0 else a.ctypes.data
@@ -121,7 +101,7 @@ class UsageTables:
     def state(self) -> UsageState:
         """The tables as the engine holds them after cns_usage_set_tables (a copy): None = zeros; a nested exists array that is not given
         = every entry exists if the table or its submit counts are given, none otherwise; a record that does not exist is zero."""
-        sh = self._shapes()
+        sh = table_shapes(self)
         v = {f: np.zeros(sh[f][1], sh[f][0]) if getattr(self, f) is None else getattr(self, f).copy() for f in TABLES + SUBMITS + ENTITIES}
         for e, f, s in zip(NESTED, TABLES, SUBMITS):
             given = getattr(self, f) is not None or getattr(self, s) is not None

@@ -17,7 +17,7 @@ SRC = os.path.join(ROOT, "tests", "cpp", "sort_host_test.cpp")
 # caller -> the routine it sorts with, and the pass count it hands over
 CALLERS = {
     "priority_host.inc": ("sort_index_pairs(", "J, 8,"),
-    "limits_host.inc": ("sort_index_pairs(", "cns_sort::key_passes(h->lim_NR)"),
+    "limits_host.inc": ("sort_index_pairs(", "cns_sort::key_passes(h->lim_sp.NR)"),
     "submit_host.inc": ("sort_index_pairs(", "cns_sort::key_passes(NK)"),
     "usage_host.inc": ("sort_index_pairs(", "cns_sort::key_passes(NK)"),
     "running_host.inc": ("sort_pairs(", "cns_sort::key_passes(S)"),
