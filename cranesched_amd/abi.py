@@ -509,6 +509,8 @@ RESVQ_OK, RESVQ_NOT_ENOUGH, RESVQ_IN_THE_PAST = 0, 1, 2
 RESVQ_FREE, RESVQ_RUNNING, RESVQ_RESERVED, RESVQ_NOT_FOUND = 0, 1, 2, 3
 # cns_resvq_shape's arguments, in the header's order
 ResvqShape = namedtuple("ResvqShape", ("pick_block", "pick_grid", "sort_tile", "scan_span"))
+# cns_preempt_shape's arguments (include/crane_gpu/preempt.h), in the header's order
+PreemptShape = namedtuple("PreemptShape", ("sort_lanes", "rank_sort_max", "compact_records", "cache_nodes", "pool_nodes"))
 
 
 class CnsResvqSoa(C.Structure):

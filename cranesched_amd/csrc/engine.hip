@@ -907,7 +907,7 @@ static int run_resident_once(cns_handle* h, int64_t now, const RunKnobs& kn, boo
     *fault_code = fault[0];
     return fail(h, CNS_ERR_UNSUPPORTED, std::string("cns_select_preempt: job ") + std::to_string(fault[1]) + (fault[0] == 31
                     ? " has more preemption candidates on its nodes than the candidate buffer holds"
-                    : " needs more segment-tree nodes than the per-partition pool (65536) holds") +
+                    : " needs more segment-tree nodes than the per-partition pool (" + std::to_string(kPrePoolNodes) + ") holds") +
                     "; keep the CPU SchedulerAlgo for this cycle (include/crane_gpu/preempt.h, limits)");
   }
   if (fault[0]) {
@@ -1043,7 +1043,7 @@ static int pre_cycle(cns_handle* h, int64_t now, const cns_job_soa* jobs, const 
   // work buffers per partition (documented in include/crane_gpu/preempt.h): candidate / chosen lists sized for every running
   // job plus every pending job of the cycle (at most all of them hold resources on one job's nodes), bounded by 64 Mi entries
   // over all partitions; segment-tree pools of 65 536 nodes.  Exceeding either is CNS_ERR_UNSUPPORTED, not a device fault.
-  const u32 pool_nodes = 1u << 16;
+  const u32 pool_nodes = kPrePoolNodes;
   const u32 cand_cap = (u32)std::max<u64>(4096, std::min<u64>((u64)R + J + 1, (64ull << 20) / std::max<u32>(h->rlay.P, 1)));
   const u32 out_cap = (u32)std::min<u64>(4 * (J + R) + 64, 1u << 28);
   DevBuf* B = h->d_pre;
@@ -1224,6 +1224,15 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
     Q.rj_preempting = B[B_RJPRE].as<uint8_t>(); Q.rj_off = B[B_RJOFF].as<u32>(); Q.rj_ent = B[B_RJENT].as<u32>();
     return 0;
   });
+}
+
+int cns_preempt_shape(uint32_t* sort_lanes, uint32_t* rank_sort_max, uint32_t* compact_records, uint32_t* cache_nodes, uint32_t* pool_nodes) {
+  if (sort_lanes) *sort_lanes = kPreSortLanes;
+  if (rank_sort_max) *rank_sort_max = kPreSortLanes * kPreSortChunks;
+  if (compact_records) *compact_records = kPcCap;
+  if (cache_nodes) *cache_nodes = kPreCacheN;
+  if (pool_nodes) *pool_nodes = kPrePoolNodes;
+  return CNS_OK;
 }
 
 int cns_get_partition_status(const cns_handle* h, uint8_t* status, uint32_t capacity) {

@@ -24,6 +24,10 @@
 #endif
 constexpr i64 kPreTicks = 4000000000ll;
 constexpr u32 kPrePending = 0x80000000u;
+// The sizes TryPreempt_ is compiled with (cns_preempt_shape returns them; tests/preempt_seams.py puts a case on each):
+constexpr u32 kPreSortLanes = 64;                        // candidates per step: of the collection, of a chunk of the rank sort, of apply()'s registers
+constexpr u32 kPreSortChunks = 4;                        // chunks the register rank sort holds: more candidates are ordered block by block
+constexpr u32 kPrePoolNodes = 1u << 16;                  // nodes of a partition's segment-tree pool: a call that needs more is CNS_ERR_UNSUPPORTED
 
 #ifndef CNS_PRE_HOST   // (CNS_PRE_HOST: the two tree forms alone, compiled for the HOST by tests/host_seg — the device source itself under the CPU suite)
 __device__ __forceinline__ i64 pre_ticks(i64 t, i64 now) {
@@ -536,8 +540,7 @@ __device__ __noinline__ int pre_try(const KParams& P, const JobCtx& J, const Hea
   PPROF_ADD(0, 1); PPROF_ADD(1, p1 - p0); PPROF_ADD(6, nc);
   if (nc == 0) return -1;
   // ---- order (:6399-6432) --------------------------------------------------------------------------------------------
-  constexpr u32 kPreSortChunks = 4;
-  if (nc <= 64u * kPreSortChunks && Q.literal_tree == 0u) {   // (the debug settings CNS_PREEMPT_TREE=literal | tiny also send every call through the block-by-block form below: the tests of those settings cover it on small cases)
+  if (nc <= kPreSortLanes * kPreSortChunks && Q.literal_tree == 0u) {   // (the debug settings CNS_PREEMPT_TREE=literal | tiny also send every call through the block-by-block form below: the tests of those settings cover it on small cases)
     // up to 256 candidates: lane l holds candidates l, l + 64, ... and counts the candidates that come before each of them (the
     // comparator is a strict total order, so the counts are the positions) — one gather of the views instead of ~nc^2 / 4
     // dependent trips to HBM

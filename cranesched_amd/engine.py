@@ -40,7 +40,7 @@ PRIORITY_ABI_SYMBOLS = ("cns_priority_order", "cns_priority_timing")
 # ... and include/crane_gpu/steps.h
 STEPS_ABI_SYMBOLS = ("cns_schedule_steps",)
 # ... and include/crane_gpu/preempt.h
-PREEMPT_ABI_SYMBOLS = ("cns_select_preempt",)
+PREEMPT_ABI_SYMBOLS = ("cns_select_preempt", "cns_preempt_shape")
 # ... and include/crane_gpu_probe/probe.h
 PROBE_ABI_SYMBOLS = ("cns_probe", "cns_probe_upload", "cns_probe_run_resident", "cns_probe_download")
 # ... and include/crane_gpu_resv/resv_probe.h
@@ -111,6 +111,15 @@ def resvq_shape() -> "abi.ResvqShape":
     if status != 0:
         raise EngineError(status, "cns_resvq_shape")
     return abi.ResvqShape(*[x.value for x in v])
+
+
+def preempt_shape() -> "abi.PreemptShape":
+    """cns_preempt_shape: the sizes the device form of TryPreempt_ is compiled with.  Needs no handle and no GPU."""
+    v = [C.c_uint32(0) for _ in abi.PreemptShape._fields]
+    status = lib().cns_preempt_shape(*[C.byref(x) for x in v])
+    if status != 0:
+        raise EngineError(status, "cns_preempt_shape")
+    return abi.PreemptShape(*[x.value for x in v])
 
 
 class GpuNodeSelector:
@@ -417,6 +426,10 @@ class GpuNodeSelector:
     def resvq_shape(self) -> "abi.ResvqShape":
         """(pick_block, pick_grid, sort_tile, scan_span) of the reservation what-ifs' kernels: where their paths change."""
         return resvq_shape()
+
+    def preempt_shape(self) -> "abi.PreemptShape":
+        """(sort_lanes, rank_sort_max, compact_records, cache_nodes, pool_nodes) of TryPreempt_ on the device: where its paths change."""
+        return preempt_shape()
 
     def resv_query_timing(self) -> dict:
         """HIP-event time of the kernels of the last query_reservations of this object."""

@@ -24,6 +24,16 @@
  * CPU SchedulerAlgo for the cycle): per partition, candidate / chosen lists of max(4096, running + pending jobs)
  * entries (capped so that all partitions together stay below 64 Mi entries) and a segment-tree pool of 65 536 nodes
  * (one job's trees: about node_num x (entries of the nodes' time maps inside its window) x log2 of that).
+ * The capacities behind that, as cns_preempt_shape returns them:
+ *   - compact_records (251): the records of the compressed trees one call may use (workgroup memory).  Not a limit of
+ *     the interface: a call that needs more starts over on the node-for-node trees and gives the same answers
+ *     (tests/test_gpu_preempt_seams.py: compact_full stays just below it, compact_over runs past it);
+ *   - cache_nodes (512): the node-for-node trees' nodes kept in workgroup memory, the rest is written back to the pool
+ *     and fetched again (compact_over, pool_deep);
+ *   - pool_nodes (65 536): the limit above (pool_deep uses more than half of it, pool_over needs more and gets
+ *     CNS_ERR_UNSUPPORTED; the next call on the handle is served);
+ *   - sort_lanes (64) and rank_sort_max (256): candidates are collected, ranked and applied 64 at a time, and up to 256
+ *     are ranked in registers (the cases nc_*, ties_*, list_* and multi_k* of tests/preempt_seams.py sit on these).
  */
 #ifndef CRANE_GPU_PREEMPT_H
 #define CRANE_GPU_PREEMPT_H
@@ -73,6 +83,11 @@ typedef struct cns_preempt_out {
 /* cns_select with preemption; preempt == NULL or preempt->enabled == 0: exactly cns_select (pout may be NULL). */
 int cns_select_preempt(cns_handle* h, int64_t now_sec, const cns_job_soa* jobs, const cns_preempt_soa* preempt,
                        cns_placement_soa* out, cns_preempt_out* pout);
+
+/* The sizes the device form of TryPreempt_ is compiled with (see "Limits" above); any pointer may be NULL.  Needs no
+ * handle and no device. */
+int cns_preempt_shape(uint32_t* sort_lanes, uint32_t* rank_sort_max, uint32_t* compact_records, uint32_t* cache_nodes,
+                      uint32_t* pool_nodes);
 
 #ifdef __cplusplus
 }

@@ -2,6 +2,7 @@
 // host (CNS_PRE_HOST: "LDS" is a static array, a wave is one thread, lane 0) — run on the same random operation sequences:
 // the reference's recursion written out here (RTree), the device's node-for-node tree (LDS write-back cache over a pool in
 // memory) and its compressed form must report the same `satisfied` after every operation.  Test infrastructure (tests/test_seg_host.py builds and runs it); nothing here ships.
+// A second mode, --replay <file>..., runs the recorded operations of one TryPreempt_ call per file through the same three (tests/test_preempt_seams.py).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -129,7 +130,79 @@ static int run_case(uint64_t seed, i64 L, i64 unit, int n_ends, int n_ops, u32 c
   return 0;
 }
 
+// ---- --replay <file>...: the tree operations of ONE TryPreempt_ call each, as tests/select_pyref.py's recorder noted them -----------
+//   call <k> <seg_end>                                              k trees over [0, seg_end)
+//   target <cpu> <mem> <clo> <chi> <gres> <c2> <c3>                 k lines, tree 0 first
+//   op <tree> <st> <ed> <1 add | 0 sub> <cpu> ... <c3>              in the order the trees saw them
+// They go through the compressed form and the node-for-node form as pre_try sets them up — ONE record space of kPcCap records and ONE
+// pool of kPrePoolNodes nodes for the k trees of the call, the roots first — and through the reference's recursion.  Per file one line:
+//   C.used C.overflow T.used T.overflow R.nodes satisfied...
+// C.used / T.used: what the call took (up to where the form ran out: the device gives up there too), R.nodes: the nodes the reference's
+// trees hold in the end (what a pool without a limit would need), satisfied: per tree, after the last operation, from the reference's
+// recursion.  A form that has not run out and disagrees with the recursion after any operation ends the program with status 1.
+static bool read_res(FILE* f, Res& r) {
+  long long cpu; unsigned long long w[6];
+  if (fscanf(f, "%lld %llu %llu %llu %llu %llu %llu", &cpu, &w[0], &w[1], &w[2], &w[3], &w[4], &w[5]) != 7) return false;
+  r = res_zero();
+  r.cpu = (i64)cpu; r.mem = w[0]; r.clo = w[1]; r.chi = w[2]; r.gres = w[3]; r.c2 = w[4]; r.c3 = w[5];
+  return true;
+}
+static int replay(const char* path) {
+  FILE* f = fopen(path, "r");
+  if (!f) { fprintf(stderr, "%s: cannot open\n", path); return 2; }
+  char word[16];
+  unsigned k = 0; long long seg_end = 0;
+  if (fscanf(f, "%15s %u %lld", word, &k, &seg_end) != 3 || strcmp(word, "call") || k == 0 || k > kPcCap || seg_end <= 0) { fprintf(stderr, "%s: no call line\n", path); fclose(f); return 2; }
+  std::vector<Res> target(k);
+  for (unsigned i = 0; i < k; ++i)
+    if (fscanf(f, "%15s", word) != 1 || strcmp(word, "target") || !read_res(f, target[i])) { fprintf(stderr, "%s: target %u\n", path, i); fclose(f); return 2; }
+  static std::vector<PreNode> pool(kPrePoolNodes);
+  static u32 lit_lds[kPreCacheDw], cmp_lds[kPreCacheDw];
+  PreTree T;
+  T.pool = pool.data(); T.cap = kPrePoolNodes; T.used = 0; T.overflow = false;
+  T.cdat = lit_lds; T.ctag = T.cdat + kPreCacheN * kPreNodeDw;
+  for (u32 x = 0; x < kPreCacheN; ++x) T.ctag[x] = 0;
+  PreC C;
+  C.base = cmp_lds; C.stack = C.base + kPcCap * kPcDw; C.used = 0; C.overflow = false; C.cap = kPcCap;
+  std::vector<RTree*> RT;
+  for (unsigned i = 0; i < k; ++i) {
+    pre_new(T, 0, (i64)seg_end, 0u, res_zero(), 0);
+    pc_leaf(C, 0, (i64)seg_end, res_zero(), 0u, 0);
+    RT.push_back(new RTree(0, (i64)seg_end, target[i]));
+  }
+  int rc = 0;
+  long n = 0;
+  while (rc == 0 && fscanf(f, "%15s", word) == 1) {
+    unsigned ti = 0, plus = 0; long long st = 0, ed = 0; Res r;
+    if (strcmp(word, "op") || fscanf(f, "%u %lld %lld %u", &ti, &st, &ed, &plus) != 4 || !read_res(f, r) || ti >= k || st >= ed) { fprintf(stderr, "%s: operation %ld\n", path, n); rc = 2; break; }
+    RT[ti]->walk(RT[ti]->root, (i64)st, (i64)ed, r, plus != 0);
+    if (!T.overflow) pre_range(T, ti, target[ti], (i64)st, (i64)ed, r, plus != 0, 0);
+    if (!C.overflow) C = pre_crange_v(C, ti, target[ti], (i64)st, (i64)ed, r, plus != 0);
+    for (unsigned i = 0; i < k && rc == 0; ++i) {   // what pre_try reads between two operations: every root's flag
+      if (!T.overflow && (pre_sat(T, i, 0) != 0) != RT[i]->root->sat) { fprintf(stderr, "%s: operation %ld, tree %u: node for node %u, the recursion %d\n", path, n, i, pre_sat(T, i, 0), (int)RT[i]->root->sat); rc = 1; }
+      if (!C.overflow && (pre_r32(pc_at(C, i) + kPcSat) != 0) != RT[i]->root->sat) { fprintf(stderr, "%s: operation %ld, tree %u: compressed %u, the recursion %d\n", path, n, i, pre_r32(pc_at(C, i) + kPcSat), (int)RT[i]->root->sat); rc = 1; }
+    }
+    ++n;
+  }
+  fclose(f);
+  size_t rnodes = 0;
+  for (RTree* t : RT) rnodes += t->all.size();
+  if (rc == 0) {
+    printf("C.used %u C.overflow %d T.used %u T.overflow %d R.nodes %zu satisfied", C.used, C.overflow ? 1 : 0, T.used, T.overflow ? 1 : 0, rnodes);
+    for (RTree* t : RT) printf(" %d", t->root->sat ? 1 : 0);
+    printf("\n");
+  }
+  for (RTree* t : RT) delete t;
+  return rc;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "--replay")) {
+    if (argc < 3) { fprintf(stderr, "usage: seg_host --replay <file>...\n"); return 2; }
+    for (int a = 2; a < argc; ++a)
+      if (int rc = replay(argv[a])) return rc;
+    return 0;
+  }
   const int cases = argc > 1 ? atoi(argv[1]) : 2000;
   static const i64 Ls[] = {1, 2, 3, 5, 8, 16, 37, 64, 100, 255, 256, 257, 1000, 3600, 86400, 1 << 20};
   static const i64 units[] = {1, 1, 2, 3, 4000000000ll, 4000000000ll, 1ll << 32, 1000003};

@@ -498,9 +498,10 @@ def res_is_zero(r: Res) -> bool:   # ResourceInNodeV3::IsZero, PublicHeader.cpp:
 class SegTree:
     """A lazily split segment tree over [st, ed): every node carries a resource, a `satisfied` flag and two pending tags."""
 
-    def __init__(self, st, ed, target: Res):
+    def __init__(self, st, ed, target: Res, log=None):
         self.target = target
         self.root = self._node(st, ed, False, Res())
+        self.log = log              # a recorder's hook: called with (st, ed, resource, is_add) in front of every operation
 
     @staticmethod
     def _node(st, ed, sat, res):
@@ -543,9 +544,13 @@ class SegTree:
         n["sat"] = n["ls"]["sat"] and n["rs"]["sat"]      # push_up_
 
     def add(self, st, ed, r):
+        if self.log is not None:
+            self.log(st, ed, r, True)
         self._walk(self.root, st, ed, r, True)
 
     def sub(self, st, ed, r):
+        if self.log is not None:
+            self.log(st, ed, r, False)
         self._walk(self.root, st, ed, r, False)
 
     @property
@@ -567,6 +572,7 @@ class PreemptCycle(ResvCycle):
         self.pd = {}                            # index -> dict: qos, qprio, prio, start, end, allocs, reason, nodes
         self.node_jobs = {}                     # node -> {qos: set(ref)}     (NodeState::qos_job_map)
         self.resv_node_jobs = {}                # reservation -> the same for its own NodeStates
+        self.recorder = None                    # a list: try_preempt appends what each call did (tests/preempt_seams.py); off by default
 
     def add_running_job(self, job_id, qos, qprio, start, end, allocs, resv=None):
         end = max(end, self.now + 1)                                             # :6513-6514
@@ -596,8 +602,11 @@ class PreemptCycle(ResvCycle):
             r["allocs"] = merged
         super().start()
 
-    def try_preempt(self, job, jinfo, picks):
-        """picks: the (node, ntasks, alloc) list of the res_total branch, in nodes_to_sched order.  -> list of refs or None."""
+    def try_preempt(self, job, jinfo, picks, idx=None):
+        """picks: the (node, ntasks, alloc) list of the res_total branch, in nodes_to_sched order.  -> list of refs or None.
+        With self.recorder a list, every call that has candidates appends a dict: job (idx), nodes, seg_end, targets (one per tree),
+        candidates, order (the sorted refs), applied (candidates added before every tree was satisfied), chosen (push_back order,
+        None: no preemption) and ops: (tree index, target, st, ed, resource, is_add) in the order the trees saw them."""
         plist = self.qos_preempt[jinfo["qos"]] if jinfo["qos"] < len(self.qos_preempt) else []
         if not plist:
             return None
@@ -618,9 +627,15 @@ class PreemptCycle(ResvCycle):
         order = sorted(cand, key=key)
         tk = lambda t: (t - self.now) * TICKS
         seg_end = tk(self.now + job["L"])
+        rec = None
+        if self.recorder is not None:
+            rec = dict(job=idx, nodes=[i for i, _, _ in picks], seg_end=seg_end, targets=[a for _, _, a in picks], candidates=len(order),
+                       order=list(order), applied=0, chosen=None, ops=[])
+            self.recorder.append(rec)
         trees = {}
-        for i, _, alloc in picks:
-            tr = SegTree(0, seg_end, alloc)
+        for ti, (i, _, alloc) in enumerate(picks):
+            log = None if rec is None else (lambda st, ed, r, plus, ti=ti, alloc=alloc: rec["ops"].append((ti, alloc, st, ed, r.copy(), plus)))
+            tr = SegTree(0, seg_end, alloc, log)
             tm = self.nodes[i].tmap
             for x, (t, r) in enumerate(tm):
                 ed = tk(tm[x + 1][0]) if x + 1 < len(tm) else seg_end
@@ -645,6 +660,8 @@ class PreemptCycle(ResvCycle):
                 break
             apply(ref, True)
             last = x
+        if rec is not None:
+            rec["applied"] = last + 1
         if not ok():
             return None
         chosen = [order[last]] if last >= 0 else []
@@ -653,6 +670,8 @@ class PreemptCycle(ResvCycle):
             if not ok():
                 apply(order[x], True)
                 chosen.append(order[x])
+        if rec is not None:
+            rec["chosen"] = list(chosen)
         return chosen
 
     def run_job_p(self, idx, job, jinfo):
@@ -687,7 +706,7 @@ class PreemptCycle(ResvCycle):
         if kind == "now":
             start = self.now
         else:
-            chosen = self.try_preempt(job, jinfo, picks)                          # :6140-6143
+            chosen = self.try_preempt(job, jinfo, picks, idx)                     # :6140-6143
             if chosen is not None:
                 start, pre = self.now, chosen
             else:

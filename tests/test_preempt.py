@@ -56,7 +56,7 @@ def test_disabled_preemption_is_the_plain_cycle(built):
 # ---------------------------------------------------------------------------------------------------------------------
 # The C++ oracle against the independent Python restatement (tests/select_pyref.py: PreemptCycle, SegTree)
 # ---------------------------------------------------------------------------------------------------------------------
-def run_pyref_preempt(c, j, now, run, pre, max_job_num_per_node=0, max_time_window_sec=0, rv=None):
+def run_pyref_preempt(c, j, now, run, pre, max_job_num_per_node=0, max_time_window_sec=0, rv=None, recorder=None):
     from tests import select_pyref as pr
     from tests.test_select_pyref import _res
     lay = c.gres
@@ -77,6 +77,7 @@ def run_pyref_preempt(c, j, now, run, pre, max_job_num_per_node=0, max_time_wind
                           max_jobs_per_node=max_job_num_per_node or pr.MAX_JOBS_PER_NODE, max_window=max_time_window_sec or pr.MAX_WINDOW,
                           qos_preempt=pre.qos_preempt if pre.enabled else [], preempting=[int(x) for x in pre.preempting],
                           reservations=resvs, pending_resv=pend)
+    cyc.recorder = recorder   # a list: what every TryPreempt_ call did (tests/preempt_seams.py)
     if run is not None:
         ahi = run.alloc_core_hi if run.alloc_core_hi is not None else np.zeros(len(run.alloc_node), np.uint64)
         ag = run.alloc_gres if run.alloc_gres is not None else np.zeros(len(run.alloc_node), np.uint64)
