@@ -63,6 +63,7 @@
 #include "submit_check_host.inc" // the input rules of cns_set_submit_limits / cns_check_submissions (no HIP in there either)
 #include "usage_check_host.inc" // the input rules of cns_usage_set_tables / cns_usage_apply (no HIP in there either)
 #include "running_check_host.inc" // the input rules of cns_running_seed / cns_running_advance (no HIP in there either)
+#include "preempt_host.inc"    // the host side of a cycle with preemption: who may preempt, the buffer plan, the running side, the fold of the results (no HIP in there either)
 #include "running_preempt_check_host.inc" // the input rules of cns_running_select_preempt (no HIP in there either)
 #include "running_attrs_check_host.inc" // the input rules of the calls of running_attrs.h (no HIP in there either)
 #include "sort_host.inc"       // the arithmetic of the pair sort: passes, tiles, histogram bytes (no HIP in there either)
@@ -226,6 +227,7 @@ struct cns_engine {
   std::set<void*> host_bufs;                    // page-locked host buffers handed out by cns_host_alloc
   bool pre_active = false;                      // the next run is a cycle with preemption (general path of k_select only)
   PreParams pre_params{};
+  cns_preempt::Plan pre_plan{};                 // the sizes of d_pre for the cycle pre_params was bound for (preempt_host.inc)
   DevBuf d_pre[B_COUNT];
   bool lim_have_tables = false, lim_have_jobs = false, lim_have_run = false;
   bool lim_has_upl = false, lim_has_apl = false, lim_has_sel = false, lim_has_skip = false;
@@ -809,10 +811,11 @@ static int run_resident_once(cns_handle* h, int64_t now, const RunKnobs& kn, boo
     // k_select partitions too, and a second pass over a first pass's per-slot job lists (slot_head / rec_next), hidden
     // candidates (ent_gone / rec_gone) and preempted pairs (out_cnt) would loop on a self-linked list or report pairs twice.
     DevBuf* B = h->d_pre;
-    HIPCHK(h, hipMemsetAsync(B[B_ENTGONE].p, 0, std::max<size_t>(h->rl_dev ? (size_t)h->rl_M : h->run.ent_job.size(), 1), h->stream));
-    HIPCHK(h, hipMemsetAsync(B[B_HEAD].p, 0xFF, (size_t)std::max<u32>(h->rlay.S, 1) * 4, h->stream));
-    HIPCHK(h, hipMemsetAsync(B[B_RECGONE].p, 0, std::max<u64>(h->q.places, 1), h->stream));
-    HIPCHK(h, hipMemsetAsync(h->pre_params.out_cnt, 0, 16, h->stream));
+    const cns_preempt::Plan& L = h->pre_plan;
+    HIPCHK(h, hipMemsetAsync(B[B_ENTGONE].p, 0, L.ent_gone, h->stream));
+    HIPCHK(h, hipMemsetAsync(B[B_HEAD].p, 0xFF, L.slot_head, h->stream));
+    HIPCHK(h, hipMemsetAsync(B[B_RECGONE].p, 0, L.rec_gone, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->pre_params.out_cnt, 0, L.cnt_bytes, h->stream));
   }
   HIPCHK(h, hipMemsetAsync(h->d_prof.p, 0, ((size_t)h->rlay.P * (32 + 16) + 2048) * sizeof(u64), h->stream));   // cycle counters + the always-on protocol counters
   HIPCHK(h, h->d_params.ensure(sizeof(KParams)));
@@ -1006,61 +1009,33 @@ static int pre_cycle(cns_handle* h, int64_t now, const cns_job_soa* jobs, const 
                      const u32 R, const u32 A, const std::vector<u32>& set_in, const std::string& who, const std::function<int(PreParams&)>& bind_running,
                      const PreRowIds* row_ids = nullptr) {
   const u64 J = jobs->num_jobs;
-  // No pending job's qos may preempt anything: TryPreempt_ returns at :6385 for every job, so the cycle is the plain one
-  // (with the preempting jobs ending at now + 1) and runs on the pipelined kernels.
-  bool any_list = false;
-  for (u64 j = 0; j < J && !any_list; ++j) {
-    const u32 q = pre->pd_qos[j];
-    any_list = q < pre->num_qos && pre->qos_preempt_offsets[q + 1] > pre->qos_preempt_offsets[q];
-  }
   const auto setup_done = [h] { h->rp_timing.setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h->pre_t0).count(); };
-  if (!any_list) {
+  if (!cns_preempt::any_may_preempt(pre, J)) {
     setup_done();
-    int rc = cns_run_resident(h, now);
-    if (rc) return rc;
-    if (int rc3 = cns_download(h, out)) return rc3;
-    for (u64 j = 0; j <= J; ++j) pout->offsets[j] = 0;
-    pout->num_cancelled = 0;
-    pout->num_preempting = 0;
-    std::set<u32> keep(set_in.begin(), set_in.end());
-    for (u32 id : keep) {
-      if (pout->num_preempting >= pout->preempting_capacity) return fail(h, CNS_ERR_INVALID_ARG, who + ": preempting_capacity too small");
-      pout->preempting_job_ids[pout->num_preempting++] = id;
-    }
-    return CNS_OK;
+    if (int rc = cns_run_resident(h, now)) return rc;
+    if (int rc = cns_download(h, out)) return rc;
+    const auto v = cns_preempt::plain_ending(who, J, set_in, pout);
+    return v ? fail(h, v.code, v.msg) : CNS_OK;
   }
   // qos preempt lists, pending-job fields (by queue index)
-  std::vector<u32> qp_off(pre->num_qos + 1, 0), qp;
-  for (u32 q = 0; q < pre->num_qos; ++q) {
-    for (u32 i = pre->qos_preempt_offsets[q]; i < pre->qos_preempt_offsets[q + 1]; ++i) qp.push_back(pre->qos_preempt[i]);
-    qp_off[q + 1] = (u32)qp.size();
-  }
-  if (qp.empty()) qp.push_back(0);
-  std::vector<u32> pj_qos(std::max<u64>(J, 1), 0), pj_qprio(std::max<u64>(J, 1), 0);
-  std::vector<double> pj_prio(std::max<u64>(J, 1), 0.0);
-  for (u64 j = 0; j < J; ++j) { pj_qos[j] = pre->pd_qos[j]; pj_qprio[j] = pre->pd_qos_priority[j]; pj_prio[j] = pre->pd_priority[j]; }
-  const u64 places = std::max<u64>(h->q.places, 1);
-  // work buffers per partition (documented in include/crane_gpu/preempt.h): candidate / chosen lists sized for every running
-  // job plus every pending job of the cycle (at most all of them hold resources on one job's nodes), bounded by 64 Mi entries
-  // over all partitions; segment-tree pools of 65 536 nodes.  Exceeding either is CNS_ERR_UNSUPPORTED, not a device fault.
-  const u32 pool_nodes = kPrePoolNodes;
-  const u32 cand_cap = (u32)std::max<u64>(4096, std::min<u64>((u64)R + J + 1, (64ull << 20) / std::max<u32>(h->rlay.P, 1)));
-  const u32 out_cap = (u32)std::min<u64>(4 * (J + R) + 64, 1u << 28);
+  const cns_preempt::QosLists ql = cns_preempt::qos_lists(pre);
+  cns_preempt::PlanIn in;
+  in.J = J; in.places = h->q.places; in.R = R; in.A = A; in.P = h->rlay.P; in.S = h->rlay.S; in.pool_nodes = kPrePoolNodes; in.node_bytes = sizeof(PreNode);
+  const cns_preempt::Plan L = h->pre_plan = cns_preempt::plan_buffers(in);
   DevBuf* B = h->d_pre;
-  if (int rc = upload(h, B[B_QPOFF], qp_off)) return rc;
-  if (int rc = upload(h, B[B_QP], qp)) return rc;
+  if (int rc = upload(h, B[B_QPOFF], ql.off)) return rc;
+  if (int rc = upload(h, B[B_QP], ql.flat)) return rc;
+  const std::vector<u32> pj_qos = cns_preempt::padded<u32>(pre->pd_qos, J), pj_qprio = cns_preempt::padded<u32>(pre->pd_qos_priority, J);
+  const std::vector<double> pj_prio = cns_preempt::padded<double>(pre->pd_priority, J);
   if (int rc = upload(h, B[B_PJQOS], pj_qos)) return rc;
   if (int rc = upload(h, B[B_PJQP], pj_qprio)) return rc;
   if (int rc = upload(h, B[B_PJPRIO], pj_prio)) return rc;
-  HIPCHK(h, B[B_PJREC0].ensure(std::max<u64>(J, 1) * 4)); HIPCHK(h, B[B_PJK].ensure(std::max<u64>(J, 1) * 4)); HIPCHK(h, B[B_PJEND].ensure(std::max<u64>(J, 1) * 8));
-  HIPCHK(h, B[B_ENTGONE].ensure(std::max<u32>(A, 1)));   // (zeroed at the start of every pass: run_resident_once)
-  HIPCHK(h, B[B_HEAD].ensure((size_t)std::max<u32>(h->rlay.S, 1) * 4));
-  HIPCHK(h, B[B_RECNEXT].ensure(places * 4)); HIPCHK(h, B[B_RECORIG].ensure(places * 4)); HIPCHK(h, B[B_RECSLOT].ensure(places * 4));
-  HIPCHK(h, B[B_RECGONE].ensure(places));
-  // one block for: segment-tree pools | candidate lists | chosen lists | output counter | output pairs
-  const size_t pool_b = (size_t)h->rlay.P * pool_nodes * sizeof(PreNode), cand_b = (size_t)h->rlay.P * cand_cap * 4;
-  const size_t off_cand = align16(pool_b), off_chosen = off_cand + align16(cand_b), off_cnt = off_chosen + align16(cand_b), off_out = off_cnt + 16;
-  HIPCHK(h, B[B_MISC].ensure(off_out + (size_t)out_cap * 8));
+  HIPCHK(h, B[B_PJREC0].ensure(L.pj4)); HIPCHK(h, B[B_PJK].ensure(L.pj4)); HIPCHK(h, B[B_PJEND].ensure(L.pj8));
+  HIPCHK(h, B[B_ENTGONE].ensure(L.ent_gone));   // (zeroed at the start of every pass: run_resident_once)
+  HIPCHK(h, B[B_HEAD].ensure(L.slot_head));
+  HIPCHK(h, B[B_RECNEXT].ensure(L.rec4)); HIPCHK(h, B[B_RECORIG].ensure(L.rec4)); HIPCHK(h, B[B_RECSLOT].ensure(L.rec4));
+  HIPCHK(h, B[B_RECGONE].ensure(L.rec_gone));
+  HIPCHK(h, B[B_MISC].ensure(L.misc));   // segment-tree pools | candidate lists | chosen lists | output counter | output pairs
   char* misc = B[B_MISC].as<char>();
   PreParams& Q = h->pre_params;
   Q = PreParams{};
@@ -1072,64 +1047,30 @@ static int pre_cycle(cns_handle* h, int64_t now, const cns_job_soa* jobs, const 
   if (int rc = bind_running(Q)) return rc;   // the running side: entry -> job and slot, per job its fields, end, mark and entries
   Q.slot_head = B[B_HEAD].as<u32>(); Q.rec_next = B[B_RECNEXT].as<u32>(); Q.rec_orig = B[B_RECORIG].as<u32>();
   Q.rec_slot = B[B_RECSLOT].as<u32>(); Q.rec_gone = B[B_RECGONE].as<uint8_t>();
-  Q.pool = misc; Q.pool_nodes = pool_nodes; Q.cand_cap = cand_cap;
-  Q.cand = (u32*)(misc + off_cand); Q.chosen = (u32*)(misc + off_chosen);
-  Q.out_cnt = (u32*)(misc + off_cnt); Q.out = (u32*)(misc + off_out); Q.out_cap = out_cap;
+  Q.pool = misc; Q.pool_nodes = L.pool_nodes; Q.cand_cap = L.cand_cap;
+  Q.cand = (u32*)(misc + L.off_cand); Q.chosen = (u32*)(misc + L.off_chosen);
+  Q.out_cnt = (u32*)(misc + L.off_cnt); Q.out = (u32*)(misc + L.off_out); Q.out_cap = L.out_cap;
   // CNS_PREEMPT_TREE=literal: TryPreempt_ on the node-for-node trees only (else: the fall-back of a call that runs out of compressed records)
   { const char* tr = getenv("CNS_PREEMPT_TREE"); Q.literal_tree = (tr && !strcmp(tr, "literal")) ? 1u : ((tr && !strcmp(tr, "tiny")) ? 2u : 0u); }   // tiny: a handful of compressed records per call, the rest falls back
-  // the partitions that have a pending job whose qos may preempt: only they run on k_select's general path (run_resident_once)
-  h->pre_part.assign(h->rlay.P, 0);
-  for (u64 j = 0; j < J; ++j) {
-    const u32 q = pre->pd_qos[j];
-    if (j < h->q.job_part.size() && h->q.job_part[(size_t)j] != kNone && q < pre->num_qos && pre->qos_preempt_offsets[q + 1] > pre->qos_preempt_offsets[q])
-      h->pre_part[h->q.job_part[(size_t)j]] = 1;
-  }
+  h->pre_part = cns_preempt::parts_that_may_preempt(pre, J, h->q.job_part, h->rlay.P);   // only they run on k_select's general path (run_resident_once)
   h->pre_active = true;
   setup_done();
   int rc = cns_run_resident(h, now);
   h->pre_active = false;
   if (rc) return rc;
   if (int rc3 = cns_download(h, out)) return rc3;
-  // ---- the preempted lists: (pending job, reference) pairs in push_back order per job -> CSR by job ------------------
+  // ---- the preempted lists: one copy of the count, one of that many (pending job, reference) pairs; the fold is preempt_host.inc's ----
   u32 cnt = 0;
-  HIPCHK(h, hipMemcpy(&cnt, misc + off_cnt, 4, hipMemcpyDeviceToHost));
-  if (cnt > out_cap) return fail(h, CNS_ERR_UNSUPPORTED, who + ": more preemptions than the result buffer holds");
-  std::vector<u32> pairs((size_t)cnt * 2 + 2);
-  if (cnt) HIPCHK(h, hipMemcpy(pairs.data(), misc + off_out, (size_t)cnt * 8, hipMemcpyDeviceToHost));
-  if (cnt > pout->capacity) return fail(h, CNS_ERR_INVALID_ARG, who + ": cns_preempt_out::capacity too small");
-  for (u64 j = 0; j <= J; ++j) pout->offsets[j] = 0;
-  for (u32 i = 0; i < cnt; ++i) pout->offsets[pairs[2 * i] + 1]++;
-  for (u64 j = 0; j < J; ++j) pout->offsets[j + 1] += pout->offsets[j];
-  {
-    std::vector<u64> cur(pout->offsets, pout->offsets + J);
-    for (u32 i = 0; i < cnt; ++i) pout->preempted[cur[pairs[2 * i]]++] = pairs[2 * i + 1];   // append order = push_back order within a job
-  }
-  // m_preempting_set_ / EnqueuePreemptCancel (:6786-6793), in queue order
-  std::set<u32> pset(set_in.begin(), set_in.end());
-  pout->num_cancelled = 0;
-  std::vector<u32> picked_ids;   // with row_ids: the ids of the running references, in the order the loop below meets them
-  if (row_ids) {
-    std::vector<u32> rows;
-    for (u64 x = 0; x < pout->offsets[J]; ++x)
-      if (!(pout->preempted[x] & CNS_PREEMPT_REF_PENDING)) rows.push_back(pout->preempted[x]);
-    if (int rc4 = (*row_ids)(rows, picked_ids)) return rc4;
-  }
-  size_t met = 0;
-  for (u64 j = 0; j < J; ++j)
-    for (u64 x = pout->offsets[j]; x < pout->offsets[j + 1]; ++x) {
-      const u32 ref = pout->preempted[x];
-      if (ref & CNS_PREEMPT_REF_PENDING) continue;
-      const u32 id = row_ids ? picked_ids[met++] : pre->rn_job_id[ref];
-      if (!pset.insert(id).second) continue;
-      if (pout->num_cancelled >= pout->cancel_capacity) return fail(h, CNS_ERR_INVALID_ARG, who + ": cancel_capacity too small");
-      pout->cancelled_job_ids[pout->num_cancelled++] = id;
-    }
-  pout->num_preempting = 0;
-  for (u32 id : pset) {
-    if (pout->num_preempting >= pout->preempting_capacity) return fail(h, CNS_ERR_INVALID_ARG, who + ": preempting_capacity too small");
-    pout->preempting_job_ids[pout->num_preempting++] = id;
-  }
-  return CNS_OK;
+  HIPCHK(h, hipMemcpy(&cnt, misc + L.off_cnt, 4, hipMemcpyDeviceToHost));
+  const u32 held = cnt > L.out_cap ? 0u : cnt;   // (a count past the buffer: the fold refuses before it reads a pair)
+  std::vector<u32> pairs((size_t)held * 2 + 2);
+  if (held) HIPCHK(h, hipMemcpy(pairs.data(), misc + L.off_out, (size_t)held * 8, hipMemcpyDeviceToHost));
+  const cns_preempt::RowIds ids_of = [&](const std::vector<u32>& rows, std::vector<u32>& ids) {
+    const int rc4 = (*row_ids)(rows, ids);
+    return rc4 ? cns_preempt::refuse(rc4, h->err) : cns_preempt::Verdict{};
+  };
+  const auto v = cns_preempt::fold(who, cnt, L.out_cap, pairs.data(), J, pre, set_in, row_ids ? &ids_of : nullptr, pout);
+  return v ? fail(h, v.code, v.msg) : CNS_OK;
 }
 
 // include/crane_gpu/preempt.h.  TryPreempt_ (JobScheduler.cpp:6378-6505) releases resources inside a cycle, which the
@@ -1143,59 +1084,19 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
   if (!h) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: null handle");
   if (!pre || !pre->enabled) {
     if (int rc = cns_select(h, now, jobs, out)) return rc;
-    if (pout) {
-      if (pout->offsets && jobs) for (uint64_t j = 0; j <= jobs->num_jobs; ++j) pout->offsets[j] = 0;
-      pout->num_cancelled = 0;
-      const uint32_t n = pre ? std::min(pre->num_preempting, pout->preempting_capacity) : 0u;   // the set passes through
-      for (uint32_t i = 0; i < n; ++i) pout->preempting_job_ids[i] = pre->preempting_job_ids[i];
-      pout->num_preempting = n;
-    }
+    cns_preempt::pass_through(jobs, pre, pout);   // the set passes through
     return CNS_OK;
   }
-  if (!jobs || !out || !pout) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: null argument");
-  if (!h->have_nodes) return fail(h, CNS_ERR_STATE, "cns_select_preempt before cns_set_nodes");
-  if (h->rl_dev) return fail(h, CNS_ERR_STATE, "cns_select_preempt: the running tables were built on the device (cns_running_seed / cns_running_advance); hand the running set in with cns_set_running first");
+  if (const auto v = cns_preempt::check_select_preempt(h->have_nodes, h->rl_dev, jobs, pre, out, pout)) return fail(h, v.code, v.msg);
   struct PreCall { cns_engine* h; ~PreCall() { h->pre_call = false; } } pre_call{h};   // (run_resident_once notes it: cns_probe refuses such a state)
   h->pre_call = true;
   h->pre_t0 = std::chrono::steady_clock::now();
   h->rp_timing = cns_running_preempt_timing{};
-  const u64 J = jobs->num_jobs;
   const u32 R = h->run.R;
-  if (J && (!pre->pd_qos || !pre->pd_qos_priority || !pre->pd_priority)) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: missing pending-job array");
-  if (R && (!pre->rn_job_id || !pre->rn_qos || !pre->rn_qos_priority || !pre->rn_start_sec)) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: missing running-job array");
-  if (!pout->offsets || !pout->preempted || !pout->cancelled_job_ids || !pout->preempting_job_ids) return fail(h, CNS_ERR_INVALID_ARG, "cns_select_preempt: missing output array");
+  if (const auto v = cns_preempt::check_select_preempt_arrays(jobs->num_jobs, R, pre, pout)) return fail(h, v.code, v.msg);
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = cns_upload_jobs(h, jobs)) return rc;
-  const u32 A = (u32)h->run.ent_job.size();
-  // m_preempting_set_: ids that no longer run are dropped, the others end at now + 1 (JobScheduler.cpp:6545-6559)
-  std::map<u32, u32> id_to_rn;
-  for (u32 r = 0; r < R; ++r) id_to_rn.emplace(pre->rn_job_id[r], r);
-  std::vector<uint8_t> rj_pre(std::max<u32>(R, 1), 0);
-  std::vector<u32> set_in;
-  for (u32 i = 0; i < pre->num_preempting; ++i) {
-    auto it = id_to_rn.find(pre->preempting_job_ids[i]);
-    if (it == id_to_rn.end()) continue;
-    rj_pre[it->second] = 1;
-    set_in.push_back(pre->preempting_job_ids[i]);
-  }
-  std::vector<i64> ent_end = h->run.rn_end, rj_end(std::max<u32>(R, 1), 0), rj_start(std::max<u32>(R, 1), 0);
-  std::vector<u32> rj_qos(std::max<u32>(R, 1), 0), rj_qprio(std::max<u32>(R, 1), 0), rj_off(R + 1, 0), rj_ent(std::max<u32>(A, 1), 0);
-  for (u32 d = 0; d < A; ++d) rj_off[h->run.ent_job[d] + 1]++;
-  for (u32 r = 0; r < R; ++r) rj_off[r + 1] += rj_off[r];
-  {
-    std::vector<u32> cur(rj_off.begin(), rj_off.end() - 1);
-    for (u32 d = 0; d < A; ++d) rj_ent[cur[h->run.ent_job[d]]++] = d;
-  }
-  for (u32 r = 0; r < R; ++r) { rj_qos[r] = pre->rn_qos[r]; rj_qprio[r] = pre->rn_qos_priority[r]; rj_start[r] = pre->rn_start_sec[r]; }
-  std::vector<char> have_end(std::max<u32>(R, 1), 0);
-  for (u32 d = 0; d < A; ++d) {
-    const u32 r = h->run.ent_job[d];
-    if (rj_pre[r]) ent_end[d] = now + 1;
-    rj_end[r] = std::max<i64>(ent_end[d], now + 1);   // :6513-6514
-    have_end[r] = 1;
-  }
-  bool patched = false;
-  for (u32 r = 0; r < R; ++r) patched = patched || rj_pre[r];
+  const cns_preempt::RunSide rs = cns_preempt::running_side(h->run.ent_job, h->run.rn_end, R, pre, now);
   // The device's running table carries the patched end times for THIS call only: whatever way the call ends, the resident
   // table goes back to the caller's end times (later cns_select / cns_run_resident calls reuse it).
   struct RestoreEnd {
@@ -1207,18 +1108,18 @@ int cns_select_preempt(cns_handle* h, int64_t now, const cns_job_soa* jobs, cons
       h->err = keep;
     }
   } restore_end{h, false};
-  if (patched) { restore_end.armed = true; if (int rc = upload(h, h->d_rn_end, ent_end)) return rc; }
-  return pre_cycle(h, now, jobs, pre, out, pout, R, A, set_in, "cns_select_preempt", [&](PreParams& Q) -> int {
+  if (rs.patched) { restore_end.armed = true; if (int rc = upload(h, h->d_rn_end, rs.ent_end)) return rc; }
+  return pre_cycle(h, now, jobs, pre, out, pout, R, (u32)h->run.ent_job.size(), rs.set_in, "cns_select_preempt", [&](PreParams& Q) -> int {
     DevBuf* B = h->d_pre;
     if (int rc = upload_some(h, B[B_RNJOB], h->run.ent_job)) return rc;
     if (int rc = upload_some(h, B[B_ENTSLOT], h->run.ent_slot)) return rc;
-    if (int rc = upload(h, B[B_RJQOS], rj_qos)) return rc;
-    if (int rc = upload(h, B[B_RJQP], rj_qprio)) return rc;
-    if (int rc = upload(h, B[B_RJSTART], rj_start)) return rc;
-    if (int rc = upload(h, B[B_RJEND], rj_end)) return rc;
-    if (int rc = upload(h, B[B_RJPRE], rj_pre)) return rc;
-    if (int rc = upload(h, B[B_RJOFF], rj_off)) return rc;
-    if (int rc = upload(h, B[B_RJENT], rj_ent)) return rc;
+    if (int rc = upload(h, B[B_RJQOS], rs.rj_qos)) return rc;
+    if (int rc = upload(h, B[B_RJQP], rs.rj_qprio)) return rc;
+    if (int rc = upload(h, B[B_RJSTART], rs.rj_start)) return rc;
+    if (int rc = upload(h, B[B_RJEND], rs.rj_end)) return rc;
+    if (int rc = upload(h, B[B_RJPRE], rs.rj_preempting)) return rc;
+    if (int rc = upload(h, B[B_RJOFF], rs.rj_off)) return rc;
+    if (int rc = upload(h, B[B_RJENT], rs.rj_ent)) return rc;
     Q.rn_job = B[B_RNJOB].as<u32>(); Q.ent_slot = B[B_ENTSLOT].as<u32>();
     Q.rj_qos = B[B_RJQOS].as<u32>(); Q.rj_qprio = B[B_RJQP].as<u32>(); Q.rj_start = B[B_RJSTART].as<i64>(); Q.rj_end = B[B_RJEND].as<i64>();
     Q.rj_preempting = B[B_RJPRE].as<uint8_t>(); Q.rj_off = B[B_RJOFF].as<u32>(); Q.rj_ent = B[B_RJENT].as<u32>();

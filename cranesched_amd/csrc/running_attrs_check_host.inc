@@ -90,8 +90,8 @@ inline Verdict refuse_sum_row(uint32_t row, int kind) {
 // cns_running_select_preempt_attrs with preemption enabled (preempt != nullptr, preempt->enabled != 0: the caller has looked)
 inline Verdict check_select_preempt_attrs(const PreemptFacts& F, bool have_columns, const cns_job_soa* jobs, const cns_preempt_soa* pre, const cns_placement_soa* out,
                                           const cns_preempt_out* pout) {
-  if (!jobs || !pre || !out || !pout) return refuse(CNS_ERR_INVALID_ARG, "cns_running_select_preempt_attrs: null argument");
-  if (!F.have_nodes) return refuse(CNS_ERR_STATE, "cns_running_select_preempt_attrs before cns_set_nodes");
+  const char* who = "cns_running_select_preempt_attrs";
+  if (const Verdict v = cns_preempt::check_order(who, F.have_nodes, jobs, pre, out, pout)) return v;
   if (!F.have_ledger) return refuse(CNS_ERR_STATE, "cns_running_select_preempt_attrs before cns_running_seed_attrs (cns_set_running and a changed num_nodes drop the ledger)");
   if (!have_columns) return refuse(CNS_ERR_STATE, std::string("cns_running_select_preempt_attrs: ") + no_columns_hint());
   if (!F.tables_are_ledgers)
@@ -101,11 +101,10 @@ inline Verdict check_select_preempt_attrs(const PreemptFacts& F, bool have_colum
   if (R >= kMaxPreemptRefs) return refuse(CNS_ERR_UNSUPPORTED, "cns_running_select_preempt_attrs: 2^31 ledger rows or more (bit 31 of a reference marks a pending job)");
   if (pre->rn_job_id || pre->rn_qos || pre->rn_qos_priority || pre->rn_start_sec)
     return refuse(CNS_ERR_INVALID_ARG, "cns_running_select_preempt_attrs: rn_job_id, rn_qos, rn_qos_priority and rn_start_sec must be NULL: the call reads the ledger's columns, not the caller's arrays");
-  if (J && (!pre->pd_qos || !pre->pd_qos_priority || !pre->pd_priority)) return refuse(CNS_ERR_INVALID_ARG, "cns_running_select_preempt_attrs: missing pending-job array");
+  if (const Verdict v = cns_preempt::check_pending(who, J, pre)) return v;
   if (!pre->qos_preempt_offsets || (!pre->qos_preempt && pre->qos_preempt_offsets[pre->num_qos])) return refuse(CNS_ERR_INVALID_ARG, "cns_running_select_preempt_attrs: missing array: the QoS preempt lists");
   if (pre->num_preempting && !pre->preempting_job_ids) return refuse(CNS_ERR_INVALID_ARG, "cns_running_select_preempt_attrs: missing array: preempting_job_ids");
-  if (!pout->offsets || !pout->preempted || !pout->cancelled_job_ids || !pout->preempting_job_ids) return refuse(CNS_ERR_INVALID_ARG, "cns_running_select_preempt_attrs: missing output array");
-  return {};
+  return cns_preempt::check_output(who, pout);
 }
 
 }  // namespace cns_running

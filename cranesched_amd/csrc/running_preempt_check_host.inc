@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/crane_gpu_running/running_preempt.h"
+#include "preempt_host.inc"   // the rules this call shares with cns_select_preempt, formed under this call's name
 #include "running_check_host.inc"
 
 namespace cns_running {
@@ -28,21 +29,19 @@ struct PreemptFacts {
 // cns_running_select_preempt with preemption enabled (preempt != nullptr, preempt->enabled != 0: the caller has looked)
 inline Verdict check_select_preempt(const PreemptFacts& F, const cns_job_soa* jobs, const cns_preempt_soa* pre, const cns_placement_soa* out,
                                     const cns_preempt_out* pout) {
-  if (!jobs || !pre || !out || !pout) return refuse(CNS_ERR_INVALID_ARG, "cns_running_select_preempt: null argument");
-  if (!F.have_nodes) return refuse(CNS_ERR_STATE, "cns_running_select_preempt before cns_set_nodes");
+  const char* who = "cns_running_select_preempt";
+  if (const Verdict v = cns_preempt::check_order(who, F.have_nodes, jobs, pre, out, pout)) return v;
   if (!F.have_ledger) return refuse(CNS_ERR_STATE, "cns_running_select_preempt before cns_running_seed (cns_set_running and a changed num_nodes drop the ledger)");
   if (!F.tables_are_ledgers)
     return refuse(CNS_ERR_STATE, "cns_running_select_preempt: the per-slot running tables are not the ledger's (cns_set_nodes / cns_set_reservations emptied them: call cns_running_advance first)");
   const uint64_t J = jobs->num_jobs, R = F.ledger_jobs;
   if (J >= kMaxPreemptRefs) return refuse(CNS_ERR_UNSUPPORTED, "cns_running_select_preempt: 2^31 pending jobs or more (bit 31 of a reference marks a pending job)");
   if (R >= kMaxPreemptRefs) return refuse(CNS_ERR_UNSUPPORTED, "cns_running_select_preempt: 2^31 ledger rows or more (bit 31 of a reference marks a pending job)");
-  if (J && (!pre->pd_qos || !pre->pd_qos_priority || !pre->pd_priority)) return refuse(CNS_ERR_INVALID_ARG, "cns_running_select_preempt: missing pending-job array");
-  if (R && (!pre->rn_job_id || !pre->rn_qos || !pre->rn_qos_priority || !pre->rn_start_sec))
-    return refuse(CNS_ERR_INVALID_ARG, "cns_running_select_preempt: missing running-job array");
+  if (const Verdict v = cns_preempt::check_pending(who, J, pre)) return v;
+  if (const Verdict v = cns_preempt::check_running(who, R, pre)) return v;
   if (!pre->qos_preempt_offsets || (!pre->qos_preempt && pre->qos_preempt_offsets[pre->num_qos])) return refuse(CNS_ERR_INVALID_ARG, "cns_running_select_preempt: missing array: the QoS preempt lists");
   if (pre->num_preempting && !pre->preempting_job_ids) return refuse(CNS_ERR_INVALID_ARG, "cns_running_select_preempt: missing array: preempting_job_ids");
-  if (!pout->offsets || !pout->preempted || !pout->cancelled_job_ids || !pout->preempting_job_ids) return refuse(CNS_ERR_INVALID_ARG, "cns_running_select_preempt: missing output array");
-  return {};
+  return cns_preempt::check_output(who, pout);
 }
 
 // m_preempting_set_ as the device bisects it: ascending, each id once

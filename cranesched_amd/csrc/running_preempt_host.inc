@@ -1,6 +1,6 @@
 // Host side of include/crane_gpu_running/running_preempt.h.  Included by engine.hip inside extern "C", behind running_host.inc.
 // Host work: the input rules (running_preempt_check_host.inc), the sort of the few preempting ids, the buffers, the launches, and the
-// cycle itself (engine.hip: pre_cycle, shared with cns_select_preempt).  Which running job owns an entry, the entries of every job, the
+// cycle itself (engine.hip: pre_cycle, shared with cns_select_preempt; its host side: preempt_host.inc).  Which running job owns an entry, the entries of every job, the
 // marks, the ends: all on the device (running_preempt_kernels.inc), from the ledger (cns_engine::d_rl) and the sorted pairs of the
 // rebuild the per-slot tables came from (d_rp[RP_KEYS] / [RP_VALS]: run_commit keeps them).  No pass over the running jobs or the
 // entries runs on a host thread.  Synchronisations in front of the cycle: one, for the flag word of the id check and the found bytes

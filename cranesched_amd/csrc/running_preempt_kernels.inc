@@ -1,6 +1,6 @@
 // Kernels of include/crane_gpu_running/running_preempt.h: the index a cycle with preemption needs of the running set, built from the
 // ledger and the sorted (slot, ledger allocation) pairs of the last rebuild (running_kernels.inc) instead of by the host passes of
-// cns_select_preempt (engine.hip: pre_index_host).  Included by engine.hip; host side: running_preempt_host.inc.
+// cns_select_preempt (preempt_host.inc: running_side).  Included by engine.hip; host side: running_preempt_host.inc.
 //
 // Once per rebuild (the first cns_running_select_preempt behind a cns_running_seed / cns_running_advance):
 //   k_rp_entries   one thread per sorted pair d, which IS entry d of the per-slot tables: ent_slot[d] = the key, ent_job[d] = the ledger

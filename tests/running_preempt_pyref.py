@@ -1,8 +1,8 @@
 """The index of a cycle with preemption over the running ledger (include/crane_gpu_running/running_preempt.h) in plain Python and numpy:
 the per-slot entry order as cns_set_running derives it from the ledger (snapshot_host.inc: build_running), then ent_job / ent_slot,
 the job -> entries CSR, the preempting marks, the patched ends, rj_end and set_in, written as the host loops of cns_select_preempt read
-(engine.hip).  Inputs: a ledger (tests/running_pyref.py), the layout's node -> slots map, the reservations' slot ranges, `now` and the
-preempting set.  layout_of() states the slot layout of a snapshot whose partitions are all served (snapshot_host.inc: build_layout,
+(preempt_host.inc: running_side).  Inputs: a ledger (tests/running_pyref.py), the layout's node -> slots map, the reservations' slot
+ranges, `now` and the preempting set.  layout_of() states the slot layout of a snapshot whose partitions are all served (snapshot_host.inc: build_layout,
 build_resv).  This is the truth cns_debug_get_preempt_index is held to — never the code under test."""
 from __future__ import annotations
 
