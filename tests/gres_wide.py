@@ -4,7 +4,15 @@ to 4 names, up to 64 distinct res_total records per snapshot) and the checks tha
 The hot path keeps GRES counts in compressed forms with saturating rules (4-bit class counts that stop at 15, a request total capped
 at 15, the predicted front after a selection that keeps a saturated count).  `tests.helpers.random_case` never has a class of more
 than 8 slots, so none of those rules ever saturates there; the cases here hold classes of 16 to 64 slots, bit 63, names 2 and 3, and
-requests around 15 / 16 / the class width / 64 / 127 / 128 / 255."""
+requests around 15 / 16 / the class width / 64 / 127 / 128 / 255.
+
+Calls held to their truth on these layouts: the selection kernels, reservations, preemption, the run limits, the step scheduler and
+the group (tests/test_gpu_gres_wide.py); cns_probe (probe_case, probe_dip_kat), cns_validate_jobs (gres_wide_case's queue and the
+hand tables of tests/valid_case.hand_wide), cns_check_submissions (submit_case, tests/submit_case.hand_table_wide), and the device
+ledger — cns_running_seed / _advance, their _attrs forms and cns_running_select_preempt (tests/running_case.scenario through
+wide_case_of, preempt_case) — in tests/test_gpu_gres_wide_calls.py.  Not covered on purpose: cns_usage_apply (its device code takes the
+4 + 8 GRES components as plain numbers and its own tests fill all twelve), cns_commit_check, cns_gate_pending and cns_resvq_run (they
+read no GRES)."""
 from __future__ import annotations
 
 import numpy as np
@@ -373,6 +381,125 @@ def step_case(seed: int, layout: str | int = "uneven", J: int = 300):
                 gt[s, b] = rng.integers(0, 4)
     steps.node_gres_total, steps.node_gres_spec = gt, gs
     return lay, jobs, steps
+
+
+def probe_case(seed: int, layout: str | int, Q: int = 32):
+    """(cluster, jobs, probes, now, running) for cns_probe: gres_wide_case(seed)'s cycle, and as probes the first Q jobs of the queue of
+    gres_wide_case(1000 + seed) on the same layout (the queue depends on the layout, N and P only, so the probes fit the cluster)."""
+    from tests import probe_case as pc
+    c, j, now, run = gres_wide_case(seed, N=96, J=700, P=2, running=60, layout=layout)
+    p = gres_wide_case(1000 + seed, N=96, J=700, P=2, running=0, layout=layout)[1]
+    return c, j, pc.take(p, np.arange(Q)), now, run
+
+
+def probe_dip_kat(kind: str):
+    """Hand-made, on one64: probes whose window reaches a slot's dip (KParams::dip_*: the packed bounds of a FUTURE time-map entry below
+    the front, 4 bits per class) where the dip's class count saturates.
+    -> (cluster, jobs, reservations, probes, now, the free slots of node 0 over time, [(start, node) per probe])
+
+    Node 0 has 64 slots, node 1 the low 20.  Job 0 takes 30 slots of node 0 for 600 s.  Job 1 (32 of 64 cores, 6 000 s) goes to the
+    then cheaper node 1 and makes it the dearer one.  From now + 600 to now + 1 200 node 0 has 24 free slots — below the front's 34,
+    above the 15 a nibble can say — and the engine holds that entry as the slot's dip:
+      "reservation": a reservation of the low 40 slots over that time (the dip the snapshot's initialisation records; job 0 holds the
+                     low 30 slots and is gone by then, so slots 40..63 are free throughout);
+      "backfill":    job 2 asks for 40 slots, which only node 0 has, and is backfilled behind job 0; job 3 asks for 30 slots for
+                     3 600 s: the front admits it, the entry at now + 600 does not (the dip the cycle records where its prediction
+                     fails), and it starts at now + 1 200.
+    Probes of 3 600 s: 17 slots typed and 17 untyped start now on node 0, the cheaper node (17 <= 24 at the dip); a filter that read
+    the saturated 15 as exact would send them to node 1 (20 free).  25 slots for 300 s end before the dip and start now on node 0."""
+    from tests import kat
+    lay = make_layout("one64")
+    now = synth.NOW
+    c = kat.cluster([64, 64], mem_gib=[256, 256], gres=[M64, (1 << 20) - 1], layout=lay)
+    specs = [dict(L=600, gspec=[30]), dict(cpu=32, L=6000)]
+    rv = None
+    if kind == "reservation":
+        rv = abi.Reservations([now + 600], [now + 1200], [0, 1], [0], [256], [GIB], [1 << 63], [0], [(1 << 40) - 1])
+        free = [(now, 34), (now + 600, 24), (now + 1200, 64)]
+    else:
+        specs += [dict(L=600, gspec=[40]), dict(L=3600, gspec=[30])]
+        free = [(now, 34), (now + 600, 24), (now + 1200, 34), (now + 4800, 64)]
+    probes = kat.jobs([dict(L=3600, gspec=[17]), dict(L=3600, gtot=[17]), dict(L=300, gspec=[25])])
+    return c, kat.jobs(specs), rv, probes, now, free, [(now, 0), (now, 0), (now, 0)]
+
+
+DIP_KATS = ("reservation", "backfill")
+SUBMIT_COUNT_CAP = 12  # the count bytes of submit_case's jobs: uncapped (127, 255, x node_num) nearly every job fails :111-114
+
+
+def submit_case(seed: int, layout: str | int, J: int = 600):
+    """(SubmitTables, jobs, SubmitKeys) for cns_check_submissions over a wide layout: 40 users, 12 accounts in two trees of depth <= 4,
+    4 QoS with deny_on_limit alternating, 3 partitions, 4 partition limits.  Every TRES limit is drawn as
+    tests.test_run_limits.random_limit_case.rtres draws it, over every name and class of the layout (a name present with probability
+    0.6, a class with 0.5), so that limits lack names and classes the jobs ask for: CheckGres_'s early `return true` (:1034, :1044) at
+    the first entry a limit lacks makes the walk order (ascending name, its total, its classes ascending) decide codes.  The usage of
+    the (user, qos) and (account, qos) records has counts on every class.  node_num, ntasks and the GRES bytes of the jobs are those of
+    gres_wide_case's queue, the bytes capped at SUBMIT_COUNT_CAP."""
+    from cranesched_amd import limits as lm, submit as sb
+    rng = np.random.default_rng(52_000 + seed)
+    lay = make_layout(layout)
+    nc, names = len(lay.class_name), sorted(set(lay.class_name))
+    U, A, Q, Pn = 40, 12, 4, 3
+    NONE = sb.LIM_NONE
+    # two trees: 0 <- 1 <- 2 <- 3 (depth 4), 0 <- 4, 1 <- 5; 6 <- 7 <- 8, 6 <- 9, 7 <- 10, 6 <- 11
+    parent = np.array([NONE, 0, 1, 2, 0, 1, NONE, 6, 7, 6, 7, 6], np.uint32)
+
+    def rtres(scale):
+        if rng.random() < 0.2:
+            return lm.unlimited_tres()
+        nm = {int(n): int(rng.integers(1, 6 * scale + 1)) for n in names if rng.random() < 0.6}
+        cl = {int(g): int(rng.integers(1, 4 * scale + 1)) for g in range(nc) if rng.random() < 0.5}
+        return lm.tres(cpu=int(rng.integers(64, 512)) if rng.random() < 0.3 else None, names=nm, classes=cl)
+
+    qos = [sb.submit_qos(deny_on_limit=bool(q % 2), max_submit_jobs_per_user=int(rng.integers(20, 60)) if q == 1 else lm.UNLIMITED_JOBS,
+                         max_tres=rtres(40), max_tres_per_user=rtres(12), max_tres_per_account=rtres(8)) for q in range(Q)]
+    pl = [sb.submit_part_limit(max_tres_per_job=rtres(8)) for _ in range(4)]
+    upl = np.where(rng.random(U * Pn) < 0.4, rng.integers(0, len(pl), U * Pn), NONE).astype(np.uint32)
+    apl = np.where(rng.random(A * Pn) < 0.3, rng.integers(0, len(pl), A * Pn), NONE).astype(np.uint32)
+
+    def rusage(n, hi):
+        u = np.zeros(n, lm.USAGE_DT)
+        u["cpu_raw"] = rng.integers(0, 16, n) * 256
+        for g in range(nc):
+            c = rng.integers(0, hi, n)
+            u["class_count"][:, g] = c
+            u["name_total"][:, lay.class_name[g]] += c.astype(np.uint64)
+        for a in names:                                           # ... and an untyped part on top of some totals
+            u["name_total"][:, a] += np.where(rng.random(n) < 0.3, rng.integers(0, 4, n), 0).astype(np.uint64)
+        return u
+
+    t = sb.SubmitTables(layout=lay, num_users=U, num_user_accts=U, num_partitions=Pn, qos=np.array(qos), acct_parent=parent,
+                        part_limits=np.array(pl), user_part_limit=upl, acct_part_limit=apl, user_qos=rusage(U * Q, 5), acct_qos=rusage(A * Q, 13),
+                        qos_usage=rusage(Q, 13), user_qos_submit=rng.integers(0, 3, U * Q), user_part_submit=rng.integers(0, 3, U * Pn),
+                        acct_qos_submit=rng.integers(0, 5, A * Q), acct_part_submit=rng.integers(0, 5, A * Pn), qos_submit=rng.integers(0, 9, Q),
+                        user_exists=rng.random(U) < 0.7, acct_exists=rng.random(A) < 0.7, qos_exists=rng.random(Q) < 0.75)
+    q = gres_wide_case(seed, N=96, J=J, P=2, running=0, layout=layout)[1]
+    jobs = abi.Jobs(partition=rng.integers(0, Pn, J).astype(np.uint32), time_limit_sec=q.time_limit_sec, node_mem=q.node_mem,
+                    task_cpu_raw=q.task_cpu_raw, task_mem=q.task_mem, node_num=q.node_num, ntasks=q.ntasks,
+                    ntasks_per_node_min=q.ntasks_per_node_min, ntasks_per_node_max=q.ntasks_per_node_max,
+                    gres_total=np.minimum(q.gres_total, SUBMIT_COUNT_CAP).astype(np.uint8),
+                    gres_spec=np.minimum(q.gres_spec, SUBMIT_COUNT_CAP).astype(np.uint8))
+    user = rng.integers(0, U, J).astype(np.uint32)
+    ua_acct = rng.integers(0, A, U).astype(np.uint32)              # user_acct i = (user i, account ua_acct[i])
+    count = np.where(rng.random(J) < 0.05, rng.integers(2, 4, J), 1).astype(np.uint32)
+    keys = sb.SubmitKeys(user, user.copy(), ua_acct[user], rng.integers(0, Q, J), count, (rng.random(J) < 0.02).astype(np.uint8))
+    return t, jobs, keys
+
+
+def with_sorted_class_names(t):
+    """The same SubmitTables over the layout whose class_name is sorted: there class-index order IS name order, so the jobs whose code
+    changes are jobs on which the two walk orders part."""
+    import dataclasses
+    lay = t.layout
+    return dataclasses.replace(t, layout=abi.GresLayout(class_name=sorted(lay.class_name), class_shift=list(lay.class_shift),
+                                                        class_width=list(lay.class_width)))
+
+
+def wide_case_of(layout: str | int):
+    """gres_wide_case over `layout` with tests.helpers.random_case's signature (tests.running_case.scenario's `case`)."""
+    def case(seed, N=96, J=600, P=2, running=40):
+        return gres_wide_case(seed, N=N, J=J, P=P, running=running, layout=layout)
+    return case
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -35,15 +35,17 @@ class Cycle:
     after: rp.Ledger
 
 
-def scenario(seed: int, cycles: int = CYCLES):
-    """-> (cluster, first ledger, [Cycle])."""
-    cluster, jobs0, now0, run0 = helpers.random_case(seed, N=N, J=J, P=P, running=RUNNING)
+def scenario(seed: int, cycles: int = CYCLES, case=None):
+    """-> (cluster, first ledger, [Cycle]).  case: a generator with tests.helpers.random_case's signature (default: that one), e.g.
+    tests.gres_wide.wide_case_of(layout): its queues must fit the cluster of every seed."""
+    case = case or helpers.random_case
+    cluster, jobs0, now0, run0 = case(seed, N=N, J=J, P=P, running=RUNNING)
     led = rp.Ledger.from_running(run0, 1000 + np.arange(len(run0.end_sec)))
     first = led.copy()
     out = []
     for c in range(cycles):
         now = now0 + STEP * c
-        jobs = jobs0 if c == 0 else helpers.random_case(seed * 16 + c, N=N, J=J, P=P, running=0)[1]
+        jobs = jobs0 if c == 0 else case(seed * 16 + c, N=N, J=J, P=P, running=0)[1]
         before = led.copy()
         run, _ = before.arrays()
         ora = pyoracle.select(cluster, jobs, now, running=run)

@@ -136,6 +136,76 @@ def expected_state(t, admitted, created):
     return s
 
 
+def hand_table_wide():
+    """CheckGres_'s walk (:1030-1050) on tests.gres_wide's eight_by_8_four_names, where class index and name disagree:
+    class_name = [3, 0, 2, 1, 0, 3, 1, 2], i.e. name 0 = classes 1, 4; name 1 = 3, 6; name 2 = 2, 7; name 3 = 0, 5.  The walk is
+    ascending name, its total, then its classes ascending, and it returns TRUE at the first requested entry the limit lacks (:1034 a
+    name, :1044 a class).  -> (tables, jobs, keys, expected codes); every job: one node, one task, count 1, a user of its own (user j
+    serves job j), account 0, partition 0.  Jobs 0-7 run under QoS 0 (nothing limited) against a partition limit of their own
+    (user_part_limit), jobs 8-10 under a DenyOnLimit QoS against the usage of their (user, qos) / (account, qos) record."""
+    from tests import gres_wide as gw
+    lay = gw.make_layout("eight_by_8_four_names")
+    C = abi
+    PB, OK = C.SUBMIT_PARTITION_TRES_PER_JOB_BEYOND, C.SUBMIT_OK
+    rows = [
+        # (qos, gres_total {name: n}, gres_spec {class: n}, the limit, expected code)
+        # 0: names 0 and 2 asked; the limit lacks name 0: :1034 returns true before name 2 (9 > 4) is looked at
+        (0, {0: 1, 2: 9}, {}, lm.tres(names={2: 4}), OK),
+        # 1: the same limit with name 0: 1 <= 1, then name 2: 9 > 4 (:1039)
+        (0, {0: 1, 2: 9}, {}, lm.tres(names={0: 1, 2: 4}), PB),
+        # 2: name 2 = classes 2, 7; the limit has the name (6 <= 10) but lacks class 2: :1044 returns true before class 7 (5 > 2)
+        (0, {2: 6}, {2: 1, 7: 5}, lm.tres(names={2: 10}, classes={7: 2}), OK),
+        # 3: ... with class 2: 1 <= 1, then class 7: 5 > 2 (:1045)
+        (0, {2: 6}, {2: 1, 7: 5}, lm.tres(names={2: 10}, classes={2: 1, 7: 2}), PB),
+        # 4: class 0 (name 3) and class 1 (name 0).  Name order reaches class 1 first (name 0: total 1 <= 10, class 1: the limit lacks
+        #    it): true.  Class-index order would reach class 0 first: 5 > 2, false.
+        (0, {0: 1, 3: 5}, {0: 5, 1: 1}, lm.tres(names={0: 10, 3: 10}, classes={0: 2}), OK),
+        # 5: the other way round.  Name order: name 0, class 1: 5 > 2, false.  Class-index order would reach class 0 first, which the
+        #    limit lacks: true.
+        (0, {0: 5, 3: 1}, {0: 1, 1: 5}, lm.tres(names={0: 10, 3: 10}, classes={1: 2}), PB),
+        # 6: names 1 and 3 asked, the limit holds name 3 only: :1034 at name 1
+        (0, {1: 1, 3: 12}, {}, lm.tres(names={3: 4}), OK),
+        # 7: name 3 alone against that limit: 12 > 4
+        (0, {3: 12}, {}, lm.tres(names={3: 4}), PB),
+        # 8: QoS 1, max_tres_per_user = name 2: 10, classes 2: 3 and 7: 3; the record holds name 2: 4 with class 7: 2.  :111 the job alone
+        #    2 <= 10, class 7: 2 <= 3.  :403 job + usage: name 2: 6 <= 10, class 7: 4 > 3
+        (1, {2: 2}, {7: 2}, None, C.SUBMIT_MAX_TRES_PER_USER_BEYOND),
+        # 9: QoS 2, max_tres_per_user = name 2: 10, class 7: 3 (no class 2); the record holds name 2: 4, class 2: 1, class 7: 2.  Job +
+        #    usage has class 2 (1, from the usage alone), which the limit lacks: :1044 returns true before class 7 (4 > 3)
+        (2, {2: 2}, {7: 2}, None, OK),
+        # 10: QoS 3, max_tres_per_account = name 0: 8, class 4: 2; account 0's record holds name 0: 1, class 4: 1.  :112 the job alone
+        #    2 <= 2.  :406 job + usage: class 4: 3 > 2
+        (3, {0: 2}, {4: 2}, None, C.SUBMIT_MAX_TRES_PER_ACCOUNT_BEYOND),
+    ]
+    J = U = len(rows)
+    Q, Pn, A = 4, 1, 1
+    q = [sb.submit_qos(),
+         sb.submit_qos(deny_on_limit=True, max_tres_per_user=lm.tres(names={2: 10}, classes={2: 3, 7: 3})),
+         sb.submit_qos(deny_on_limit=True, max_tres_per_user=lm.tres(names={2: 10}, classes={7: 3})),
+         sb.submit_qos(deny_on_limit=True, max_tres_per_account=lm.tres(names={0: 8}, classes={4: 2}))]
+    pl, upl = [], np.full(U * Pn, NONE, np.uint32)
+    for j, r in enumerate(rows):
+        if r[3] is not None:
+            upl[j * Pn] = len(pl)
+            pl.append(sb.submit_part_limit(max_tres_per_job=r[3]))
+    uq_use, aq_use = np.zeros(U * Q, lm.USAGE_DT), np.zeros(A * Q, lm.USAGE_DT)
+    uq_use[8 * Q + 1]["name_total"][2], uq_use[8 * Q + 1]["class_count"][7] = 4, 2
+    uq_use[9 * Q + 2]["name_total"][2], uq_use[9 * Q + 2]["class_count"][2], uq_use[9 * Q + 2]["class_count"][7] = 4, 1, 2
+    aq_use[0 * Q + 3]["name_total"][0], aq_use[0 * Q + 3]["class_count"][4] = 1, 1
+    t = sb.SubmitTables(layout=lay, num_users=U, num_user_accts=U, num_partitions=Pn, qos=np.array(q), acct_parent=np.array([NONE], np.uint32),
+                        part_limits=np.array(pl), user_part_limit=upl, user_qos=uq_use, acct_qos=aq_use, user_exists=np.ones(U, np.uint8),
+                        acct_exists=np.ones(A, np.uint8), qos_exists=np.ones(Q, np.uint8))
+    gt, gs = np.zeros((J, 4), np.uint8), np.zeros((J, 8), np.uint8)
+    for j, r in enumerate(rows):
+        for a, v in r[1].items():
+            gt[j, a] = v
+        for c, v in r[2].items():
+            gs[j, c] = v
+    i = np.arange(J, dtype=np.uint32)
+    keys = sb.SubmitKeys(i, i, np.zeros(J, np.uint32), [r[0] for r in rows])
+    return t, make_jobs(J, gres_total=gt, gres_spec=gs), keys, np.array([r[4] for r in rows], np.uint8)
+
+
 def random_case(seed, J, U=200, A=64, Q=4, Pn=8, array_frac=0.10):
     """About U users, A accounts in a tree, Q QoS, Pn partitions, mixed limits, DenyOnLimit / max_jobs == 0 QoS, a mix of exists bits,
     array_frac of the jobs with counts 2..199."""

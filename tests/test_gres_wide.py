@@ -2,6 +2,8 @@
 placements), both oracle algebras agree on them (selection, preemption, steps), and the reference's own code agrees with the oracle
 at these layouts (feasible on random requests, whole cycles) — so that the GPU tests of tests/test_gpu_gres_wide.py compare the
 engine with a pinned oracle."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -226,3 +228,122 @@ def test_exactly_64_types_against_the_reference_code():
     from tests.test_ref_pin import both
     c, j, now, run = gw.gres_wide_case(80, N=80, J=300, P=2, running=30, layout="uneven", types=64)
     both("64 types", c, j, now, running=run)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the calls of tests/test_gpu_gres_wide_calls.py: conditions on the inputs, asserted on the references' answers, so that a case which
+# stops reaching its edge fails here and not silently on the device
+# ---------------------------------------------------------------------------------------------------------------------------------
+WIDE_CALL_LAYOUTS = gw.NAMED + [3, 5]
+SUBMIT_LAYOUTS = ["eight_by_8_four_names", "uneven", 3, 5]
+
+
+@functools.lru_cache(maxsize=None)
+def _probe_answers(lay):
+    from tests import probe_case as pc
+    c, j, p, now, run = gw.probe_case(1, lay)
+    return c, j, p, now, run, pc.expected(c, j, p, now, running=run)
+
+
+@pytest.mark.parametrize("lay", gw.NAMED)
+def test_probes_ask_every_kind_of_question(built, lay):
+    from tests import probe_case as pc
+    c, j, p, now, run, exp = _probe_answers(lay)
+    m = pc.outcome_mix(exp, p, now)
+    assert p.num_jobs == 32 and m["now"] >= 3 and m["later"] >= 3 and m["resource_no_start"] >= 1 and m["multi_node"] >= 1, m
+
+
+def test_probes_reach_the_saturated_counts(built):
+    """Over the named layouts: a probe is placed on 16 or more slots of one class (64 on one64, 21 on uneven: behind a cycle that filled
+    the cluster such a probe starts later, the largest class share of a probe that starts now is 10), a probe's placement holds bit 63,
+    and the cycle whose front summaries the probes read started placements of 16 or more slots of one class now (55 on one64, 21 on
+    uneven): the 4-bit class counts of the summaries and dips saturate."""
+    placed, bit63, cycle_now = {}, False, {}
+    for lay in gw.NAMED:
+        c, j, p, now, run, exp = _probe_answers(lay)
+        cm = gw.class_masks(c.gres)
+        placed[lay] = 0
+        for i in range(p.num_jobs):
+            if exp.start_sec[i] == 0:
+                continue
+            for x in range(int(exp.place_offsets[i]), int(exp.place_offsets[i + 1])):
+                g = int(exp.gres[x])
+                bit63 |= bool(g >> 63)
+                placed[lay] = max([placed[lay]] + [bin(g & m).count("1") for m in cm])
+        cycle_now[lay] = gw.coverage(c, j, pyoracle.select(c, j, now, running=run).placements)["max_class_now"]
+    assert max(placed.values()) >= 16 and placed["one64"] >= 16 and placed["uneven"] >= 16, placed
+    assert bit63
+    assert cycle_now["one64"] >= 16 and cycle_now["uneven"] >= 16, cycle_now
+
+
+@pytest.mark.parametrize("kind", gw.DIP_KATS)
+def test_probe_dip_scenario_is_decided_by_a_saturated_dip(built, kind):
+    """gw.probe_dip_kat by hand and on the oracle: the first two probes start now on the node whose time map holds, inside their window,
+    an entry with fewer free slots than the front and more than the 15 a nibble can say, and they ask for more than 15."""
+    from tests import probe_case as pc
+    c, j, rv, p, now, free, want = gw.probe_dip_kat(kind)
+    tl = pyoracle.select(c, j, now, reservations=rv).timeline(0)
+    got_free = [(int(t), bin(int(g)).count("1")) for t, g in zip(tl["t"], tl["gres"])]
+    assert got_free[:len(free)] == free and free[1] == (now + 600, 24)
+    exp = pc.expected(c, j, p, now, reservations=rv)
+    got = [(int(exp.start_sec[i]), int(exp.node_idx[int(exp.place_offsets[i])])) for i in range(3)]
+    assert got == want and list(exp.reason[:3]) == [abi.REASON_NONE] * 3
+    need = [max(int(p.gres_spec[i, 0]), int(p.gres_total[i, 0])) for i in range(3)]
+    assert 15 < need[0] <= 24 and 15 < need[1] <= 24 < need[2] <= 34 and int(p.time_limit_sec[0]) > 600 >= int(p.time_limit_sec[2])
+    assert bin(int(c.gres_slots[1])).count("1") >= need[0], "the other node could take them: a wrong filter changes the answer"
+
+
+@pytest.mark.parametrize("lay", WIDE_CALL_LAYOUTS)
+def test_validity_codes_of_the_wide_queues(lay):
+    from tests import valid_pyref
+    c, j, now, run = gw.gres_wide_case(1, N=96, J=700, P=2, running=60, layout=lay)
+    code, elig = valid_pyref.check(c, j, None)
+    n = np.bincount(code, minlength=11)
+    assert n[abi.VALID_OK] >= 300 and n[abi.VALID_NOT_ENOUGH_NODES] >= 30, n
+    if lay == "one64":                      # 48 nodes of 64 slots cover a request of 255: nothing fails :7283 on its GRES
+        assert n[abi.VALID_NO_RESOURCE] == 0
+    else:
+        assert n[abi.VALID_NO_RESOURCE] >= 5, n
+
+
+@functools.lru_cache(maxsize=None)
+def _submit_answers(lay):
+    from tests import submit_pyref as sp
+    t, jobs, keys = gw.submit_case(11, lay)
+    return t, jobs, keys, sp.run(t, jobs, keys)
+
+
+@pytest.mark.parametrize("lay", SUBMIT_LAYOUTS)
+def test_submit_codes_depend_on_the_walk_order(lay):
+    from tests import submit_pyref as sp
+    t, jobs, keys, (code, tlo, adm, state) = _submit_answers(lay)
+    assert jobs.num_jobs == 600 and 0 < adm < 600
+    assert int(jobs.gres_total.max()) <= gw.SUBMIT_COUNT_CAP and int(jobs.gres_spec.max()) <= gw.SUBMIT_COUNT_CAP
+    assert t.layout.class_name != sorted(t.layout.class_name), "class-index order and name order must differ on this layout"
+    other = sp.run(gw.with_sorted_class_names(t), jobs, keys)[0]
+    assert int((other != code).sum()) >= 10, int((other != code).sum())
+
+
+def test_submit_cases_reach_every_tres_check():
+    n = np.zeros(17, np.int64)
+    for lay in SUBMIT_LAYOUTS:
+        n += np.bincount(_submit_answers(lay)[3][0], minlength=17)
+    for c in (abi.SUBMIT_TRES_PER_JOB_BEYOND, abi.SUBMIT_PARTITION_TRES_PER_JOB_BEYOND, abi.SUBMIT_MAX_TRES_PER_USER_BEYOND,
+              abi.SUBMIT_MAX_TRES_PER_ACCOUNT_BEYOND):
+        assert n[c] >= 3, (abi.SUBMIT_STR[c], n)
+
+
+@pytest.mark.parametrize("lay", gw.NAMED)
+def test_ledger_scenario_carries_wide_masks(built, lay):
+    """tests/running_case.scenario over a wide layout: what the four boundaries admit holds masks above bit 31 and bit 63, on rows of
+    several nodes; a 32-bit truncation of the gres plane or of a ledger word changes the ledger."""
+    from tests import running_case as rc
+    cluster, first, cycles = rc.scenario(3, case=gw.wide_case_of(lay))
+    assert len(cycles) == 4 and cluster.gres.class_name == gw.make_layout(lay).class_name
+    assert sum(c.num_admitted for c in cycles) >= 100 and sum(c.num_retired for c in cycles) >= 20
+    assert all(c.num_admitted >= 10 and c.num_retired >= 1 for c in cycles)
+    seeded = set(first.ids())
+    rows = {r.job_id: r for c in cycles for r in c.after.rows if r.job_id not in seeded}
+    assert sum(len(r.allocs) > 1 for r in rows.values()) >= 20
+    assert any(a[1]["gres"] >> 32 for r in rows.values() for a in r.allocs)
+    assert any(a[1]["gres"] >> 63 for r in rows.values() for a in r.allocs)

@@ -42,6 +42,20 @@ def test_hand_table_state_after_the_batch(hand):
     assert t.user_exists[17] == 0 and t.qos_exists[3] == 0      # the tables themselves are inputs and stay
 
 
+def test_hand_table_on_a_wide_layout():
+    """CheckGres_'s walk order where class index and name disagree (tests/gres_wide.py, eight_by_8_four_names)."""
+    t, jobs, keys, codes = sc.hand_table_wide()
+    got_code, got_tlo, got_adm, _ = sp.run(t, jobs, keys)
+    for j in range(jobs.num_jobs):
+        assert got_code[j] == codes[j], f"job {j}: {abi.SUBMIT_STR[int(got_code[j])]}, by hand {abi.SUBMIT_STR[int(codes[j])]}"
+    assert jobs.num_jobs >= 8 and got_adm == int((codes == 0).sum()) == 5 and np.array_equal(got_tlo, jobs.time_limit_sec)
+    # rows 4 and 5 are the ones a walk in class-index order gets wrong: on the layout with class_name sorted (where the two orders
+    # coincide, and classes 0, 1 share a name) the restatement itself answers the other way
+    from tests import gres_wide as gw
+    other = sp.run(gw.with_sorted_class_names(t), jobs, keys)[0]
+    assert other[4] != codes[4] and other[5] != codes[5]
+
+
 def test_carry_equals_one_batch(hand):
     t, jobs, keys = hand[0], hand[1], hand[2]
     from cranesched_amd import submit as sb

@@ -17,6 +17,21 @@ def test_hand_cases():
     assert set(int(c) for c in want_code) == set(range(11)), "the table has a case of every code"
 
 
+@pytest.mark.parametrize("table", ["one64", "eight_by_8_four_names", "mem_2pow63"])
+def test_hand_cases_on_wide_layouts(table):
+    """The rows decided by the clamp of a request byte, by a byte's neighbour, by 257-node sums and by the saturated memory sum."""
+    cl, jobs, want_code, want_elig, rows = vc.hand_wide()[table]
+    code, elig = ref.check(cl, jobs, None)
+    for i, r in enumerate(rows):
+        assert (int(code[i]), int(elig[i])) == (r[2], r[3]), f"{table} row {i} ({r[0]}): got {abi.VALID_STR[int(code[i])]} / {int(elig[i])}"
+    assert {abi.VALID_OK, abi.VALID_NOT_ENOUGH_NODES} <= set(int(c) for c in want_code)
+    if table == "one64":
+        assert abi.VALID_NO_RESOURCE in want_code and int(cl.gres_slots[0]) >> 63 == 1 and cl.num_nodes == 263
+        assert {63, 64, 65, 127, 255} <= set(jobs.gres_total[:, 0].tolist()) and {63, 64, 65, 127, 255} <= set(jobs.gres_spec[:, 0].tolist())
+    if table == "eight_by_8_four_names":
+        assert jobs.gres_spec.any(axis=0).all() and jobs.gres_total.any(axis=0).all(), "every class index and every name is asked for"
+
+
 def test_hand_cases_without_reservations():
     """cns_set_reservations is optional: without it every reservation index is unknown."""
     cl, _, jobs, want_code, _ = vc.hand()

@@ -131,6 +131,114 @@ def hand():
             np.asarray([h[3] for h in HAND], np.uint32))
 
 
+# ---- the hand-derived table on wide GRES layouts (tests/gres_wide.py) --------------------------------------------------------------------
+# The walk compares all classes (and all names) with one subtract-and-mask on packed bytes: a node byte is at most 64, a request byte is
+# clamped to 65 (csrc/valid_kernels.inc, vd_fits).  These rows are decided by the clamp, by a byte's neighbour, by bit 63, by names 2 and
+# 3 and class indices up to 7, and by partition sums that take more than one wave.  Every job: one core and 1 GiB per task, ntasks =
+# node_num, on nodes of 8 cores and 16 GiB, so that only the GRES counts (and, in WIDE_MEM, the memory) decide.
+M64 = 2 ** 64 - 1
+
+
+def _w(p, k=1, gt=None, gs=None, **kw):
+    return dict(p=p, tcpu=CORE, tmem=G, k=k, nt=k, gt=gt or {}, gs=gs or {}, **kw)
+
+
+# one64: class 0 = name 0 = all 64 bits.
+# p0 = {n0..n4: 64 slots, n5: 63 slots (bit 63 missing)}: 6 nodes, name 0 / class 0 total 5 * 64 + 63 = 383
+# p1 = {n6..n262: 64 slots}: 257 nodes — one more than k_valid_totals's 256-thread stride —, total 257 * 64 = 16 448
+WIDE_ONE64_NODES = [(8, 16 * G, M64, 1, 0)] * 5 + [(8, 16 * G, M64 >> 1, 1, 0)] + [(8, 16 * G, M64, 1, 0)] * 257
+WIDE_ONE64_PARTS = [list(range(6)), list(range(6, 263))]
+WIDE_ONE64 = [
+    # untyped, one node: :7283 asks count * 1 <= 383, the walk asks count <= the node's 64 (63 on n5)
+    ("untyped 63: every node", _w(0, gt={0: 63}), C.VALID_OK, 6),
+    ("untyped 64: all but n5", _w(0, gt={0: 64}), C.VALID_OK, 5),
+    ("untyped 65 <= 383 passes :7283; no node has 65", _w(0, gt={0: 65}), C.VALID_NOT_ENOUGH_NODES, 0),
+    ("untyped 127 <= 383; decided by the clamp to 65", _w(0, gt={0: 127}), C.VALID_NOT_ENOUGH_NODES, 0),
+    ("untyped 255 <= 383; decided by the clamp to 65", _w(0, gt={0: 255}), C.VALID_NOT_ENOUGH_NODES, 0),
+    # typed (a total of 0 and class 0 specified): :7283 asks 0 <= 383 and count <= 383, the walk count <= the node's class 0
+    ("typed 63", _w(0, gs={0: 63}), C.VALID_OK, 6),
+    ("typed 64", _w(0, gs={0: 64}), C.VALID_OK, 5),
+    ("typed 65", _w(0, gs={0: 65}), C.VALID_NOT_ENOUGH_NODES, 0),
+    ("typed 127", _w(0, gs={0: 127}), C.VALID_NOT_ENOUGH_NODES, 0),
+    ("typed 255", _w(0, gs={0: 255}), C.VALID_NOT_ENOUGH_NODES, 0),
+    ("typed 64 under a total of 64", _w(0, gt={0: 64}, gs={0: 64}), C.VALID_OK, 5),
+    ("typed 63 under a total of 64: the total decides n5", _w(0, gt={0: 64}, gs={0: 63}), C.VALID_OK, 5),
+    # the same requests times a node_num that :7283 refuses (it comes before :7299's node_num > 6)
+    ("63 * 6 = 378 <= 383: six nodes, six eligible", _w(0, k=6, gt={0: 63}), C.VALID_OK, 6),
+    ("63 * 7 = 441 > 383", _w(0, k=7, gt={0: 63}), C.VALID_NO_RESOURCE, 0),
+    ("64 * 5 = 320 <= 383: five nodes, five eligible", _w(0, k=5, gt={0: 64}), C.VALID_OK, 5),
+    ("64 * 6 = 384 > 383: one slot short", _w(0, k=6, gt={0: 64}), C.VALID_NO_RESOURCE, 0),
+    ("typed 64 * 6 = 384 > 383", _w(0, k=6, gs={0: 64}), C.VALID_NO_RESOURCE, 0),
+    ("65 * 5 = 325 <= 383", _w(0, k=5, gt={0: 65}), C.VALID_NOT_ENOUGH_NODES, 0),
+    ("65 * 6 = 390 > 383", _w(0, k=6, gt={0: 65}), C.VALID_NO_RESOURCE, 0),
+    ("127 * 3 = 381 <= 383", _w(0, k=3, gs={0: 127}), C.VALID_NOT_ENOUGH_NODES, 0),
+    ("127 * 4 = 508 > 383", _w(0, k=4, gs={0: 127}), C.VALID_NO_RESOURCE, 0),
+    ("255 * 2 = 510 > 383", _w(0, k=2, gt={0: 255}), C.VALID_NO_RESOURCE, 0),
+    # 257 nodes: the sums of k_valid_totals cross its stride, its waves and its LDS stage
+    ("64 * 257 = 16 448 = the total: every node", _w(1, k=257, gt={0: 64}), C.VALID_OK, 257),
+    ("typed 64 * 257 = 16 448", _w(1, k=257, gs={0: 64}), C.VALID_OK, 257),
+    ("255 * 64 = 16 320 <= 16 448 passes :7283; no node has 255", _w(1, k=64, gt={0: 255}), C.VALID_NOT_ENOUGH_NODES, 0),
+    ("255 * 65 = 16 575 > 16 448", _w(1, k=65, gt={0: 255}), C.VALID_NO_RESOURCE, 0),
+    ("typed 255 * 64 = 16 320", _w(1, k=64, gs={0: 255}), C.VALID_NOT_ENOUGH_NODES, 0),
+    ("typed 255 * 65 = 16 575", _w(1, k=65, gs={0: 255}), C.VALID_NO_RESOURCE, 0),
+    ("65 * 253 = 16 445 <= 16 448", _w(1, k=253, gt={0: 65}), C.VALID_NOT_ENOUGH_NODES, 0),
+    ("65 * 254 = 16 510 > 16 448", _w(1, k=254, gt={0: 65}), C.VALID_NO_RESOURCE, 0),
+]
+
+
+def _wide_eight():
+    """eight_by_8_four_names: class_name [3, 0, 2, 1, 0, 3, 1, 2], 8 slots each; name 0 = classes 1, 4; name 1 = 3, 6; name 2 = 2, 7;
+    name 3 = 0, 5.  n0, n1: every class full (8; every name 16).  n(2 + c): class c at 7 (its lowest slot missing), the others full, so
+    the name of class c at 15.  One partition of the 10 nodes: every class sums to 9 * 8 + 7 = 79, every name to 158, far above any
+    request here (:7283 passes everywhere)."""
+    from tests import gres_wide as gw
+    lay = gw.make_layout("eight_by_8_four_names")
+    nodes = [(8, 16 * G, M64, 1, 0)] * 2 + [(8, 16 * G, M64 & ~(1 << lay.class_shift[c]), 1, 0) for c in range(8)]
+    rows = []
+    for c in range(8):
+        nb = c + 1 if c < 7 else 6          # the class in the neighbouring byte of the packed word
+        # 8 of class c: every node but n(2 + c)
+        rows.append((f"class {c}: 8", _w(0, gs={c: 8}), C.VALID_OK, 9))
+        # ... and 8 of the neighbour: every node but n(2 + c) and n(2 + nb)
+        rows.append((f"class {c}: 8, and 8 of class {nb}", _w(0, gs={c: 8, nb: 8}), C.VALID_OK, 8))
+        # 9 of class c: no node (the byte's own borrow), whatever the neighbour's byte says
+        rows.append((f"class {c}: 9, and 8 of class {nb}", _w(0, gs={c: 9, nb: 8}), C.VALID_NOT_ENOUGH_NODES, 0))
+    for a in range(4):
+        nb = a + 1 if a < 3 else 2
+        # 16 of name a: every node but the two with one of its classes at 7
+        rows.append((f"name {a}: 16", _w(0, gt={a: 16}), C.VALID_OK, 8))
+        # ... and 16 of the neighbour: but those four
+        rows.append((f"name {a}: 16, and 16 of name {nb}", _w(0, gt={a: 16, nb: 16}), C.VALID_OK, 6))
+        rows.append((f"name {a}: 17, and 16 of name {nb}", _w(0, gt={a: 17, nb: 16}), C.VALID_NOT_ENOUGH_NODES, 0))
+        # 15 of name a, 8 of its first class: the node with that class at 7 has 15 of the name, but not the 8
+        first = lay.class_name.index(a)
+        rows.append((f"name {a}: 15 with 8 of its class {first}", _w(0, gt={a: 15}, gs={first: 8}), C.VALID_OK, 9))
+    return lay, nodes, [list(range(10))], rows
+
+
+# Three nodes of 2^63 bytes in one partition: 3 * 2^63 leaves 64 bits, the partition's sum saturates at UINT64_MAX (validity.h).
+# 2^64 - 1 = 3 * 0x5555555555555555: three tasks of that much are a total of UINT64_MAX exactly and pass :7283 only against the saturated
+# sum (a wrapped sum would be 2^63); each node holds one task (0x5555... <= 2^63).
+WIDE_MEM_NODES = [(8, 1 << 63, 0, 1, 0)] * 3
+WIDE_MEM = [
+    ("total memory 2^64 - 1 against the saturated sum", dict(p=0, tcpu=CORE, tmem=0x5555555555555555, k=3, nt=3), C.VALID_OK, 3),
+    ("one task of 2^63 on each node: 3 * 2^63 is not a 64-bit total", dict(p=0, tcpu=CORE, tmem=1 << 63, k=3, nt=3), C.VALID_BAD_REQUEST, 0),
+    ("one task of 2^63: exactly a node's", dict(p=0, tcpu=CORE, tmem=1 << 63), C.VALID_OK, 3),
+    ("one byte more than a node's, below the partition's", dict(p=0, tcpu=CORE, tmem=(1 << 63) + 1), C.VALID_NOT_ENOUGH_NODES, 0),
+]
+
+
+def hand_wide():
+    """-> {table name: (cluster, jobs, expected code, expected eligible, rows)}"""
+    from tests import gres_wide as gw
+    lay8, nodes8, parts8, rows8 = _wide_eight()
+    tables = {"one64": (make_cluster(WIDE_ONE64_NODES, WIDE_ONE64_PARTS, gw.make_layout("one64")), WIDE_ONE64),
+              "eight_by_8_four_names": (make_cluster(nodes8, parts8, lay8), rows8),
+              "mem_2pow63": (make_cluster(WIDE_MEM_NODES, [[0, 1, 2]]), WIDE_MEM)}
+    return {name: (cl, make_jobs([r[1] for r in rows]), np.asarray([r[2] for r in rows], np.uint8), np.asarray([r[3] for r in rows], np.uint32), rows)
+            for name, (cl, rows) in tables.items()}
+
+
 # ---- the generator ---------------------------------------------------------------------------------------------------------------------
 GPU_SEEDS = tuple(range(20))
 
