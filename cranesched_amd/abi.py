@@ -513,6 +513,25 @@ ResvqShape = namedtuple("ResvqShape", ("pick_block", "pick_grid", "sort_tile", "
 PreemptShape = namedtuple("PreemptShape", ("sort_lanes", "rank_sort_max", "compact_records", "cache_nodes", "pool_nodes"))
 
 
+# cns_select_shape (include/crane_gpu/node_select.h): the constants at which the selection kernels change path
+SHAPE_MAX_WIDTHS = 8
+
+
+class CnsTileShape(C.Structure):
+    _fields_ = [("lanes", C.c_uint32), ("num_widths", C.c_uint32), ("widths", C.c_uint32 * SHAPE_MAX_WIDTHS)]
+
+
+class CnsSelectShapeInfo(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("tl_chunk", "tl_cap", "multi_k", "pipe_max_k", "max_upd", "lds_heap", "alloc_cache", "pipe_ring",
+                                          "wide_task_ring", "pipe_xring", "wide_window", "sel_dip_max_npl")] + \
+               [("select", CnsTileShape), ("pipe", CnsTileShape), ("wide", CnsTileShape * 4), ("wide_waves", C.c_uint32 * 4)]
+
+
+TileShape = namedtuple("TileShape", ("lanes", "widths"))          # widths: ascending tuple of rows per lane
+# the scalar fields in the header's order, then select / pipe (TileShape) and wide: a tuple of (scanner waves, TileShape), widest build first
+SelectShape = namedtuple("SelectShape", tuple(f for f, t in CnsSelectShapeInfo._fields_ if t is C.c_uint32) + ("select", "pipe", "wide"))
+
+
 class CnsResvqSoa(C.Structure):
     _fields_ = [("num_queries", C.c_uint64), ("start_sec", _P), ("duration_sec", _P), ("node_num", _P), ("cand_offsets", _P),
                 ("cand_nodes", _P), ("find_earliest", _P)]

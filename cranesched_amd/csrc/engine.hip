@@ -1136,6 +1136,28 @@ int cns_preempt_shape(uint32_t* sort_lanes, uint32_t* rank_sort_max, uint32_t* c
   return CNS_OK;
 }
 
+int cns_select_shape(cns_select_shape_info* out) {
+  if (!out) return CNS_ERR_INVALID_ARG;
+  static_assert(w64::kWTRing == w32::kWTRing && w64::kWTRing == w16::kWTRing && w64::kWTRing == w8::kWTRing, "cns_select_shape: one task ring size for every build of k_wide");
+  const cns_plan::Facts& F = plan_facts();   // the tiles as the launch plan has them
+  cns_select_shape_info s{};
+  s.tl_chunk = kTlChunk; s.tl_cap = kTlCap;
+  s.multi_k = (u32)kMultiK; s.pipe_max_k = (u32)kPMaxK; s.max_upd = (u32)kMaxUpd; s.lds_heap = (u32)kLdsHeap; s.alloc_cache = (u32)kAllocCache;
+  s.pipe_ring = kPRing; s.wide_task_ring = w64::kWTRing; s.pipe_xring = kPXRing; s.wide_window = w64::kWJ;
+  s.sel_dip_max_npl = (u32)kSelDipMaxNpl;
+  auto tiles = [](const cns_plan::Tiles& t, cns_tile_shape& o) {
+    if (t.widths.size() > CNS_SHAPE_MAX_WIDTHS) return false;
+    o.lanes = t.lanes; o.num_widths = (u32)t.widths.size();
+    std::copy(t.widths.begin(), t.widths.end(), o.widths);
+    return true;
+  };
+  bool ok = tiles(F.select, s.select) && tiles(F.pipe, s.pipe);
+  for (u32 b = 0; b < 4; ++b) { ok = ok && tiles(F.wide[b].tiles, s.wide[b]); s.wide_waves[b] = F.wide[b].waves; }
+  if (!ok) return CNS_ERR_UNSUPPORTED;   // (an experiment build with more tile widths than the record holds)
+  *out = s;
+  return CNS_OK;
+}
+
 int cns_get_partition_status(const cns_handle* h, uint8_t* status, uint32_t capacity) {
   if (!h || !status) return fail(const_cast<cns_handle*>(h), CNS_ERR_INVALID_ARG, "cns_get_partition_status: null argument");
   if (!h->have_nodes) return fail(const_cast<cns_handle*>(h), CNS_ERR_STATE, "cns_get_partition_status before cns_set_nodes");

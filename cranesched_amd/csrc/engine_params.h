@@ -42,6 +42,7 @@ constexpr unsigned kScan = kScanWaves * 64;  // scanner lanes = nodes per tile r
 #endif
 constexpr int kWaves = kBlock / 64;
 constexpr u32 kTlCap = 1008;         // >= kAlgoMaxJobNumPerNode - 1 + 2 entries per node
+constexpr u32 kTlChunk = 64;         // a time map of up to this many entries is worked on in registers, one entry per lane of the wave; longer ones 64 entries per step
 constexpr int kMaxUpd = 32;          // per-job owner updates broadcast through LDS
 constexpr int kMultiK = kWaves < 8 ? kWaves : 8;      // node_num handled by the parallel multi-node protocol (one helper wave per node, the worker included)
 constexpr int kLdsHeap = 33;         // heap / pick entries kept in LDS when node_num < this

@@ -171,7 +171,7 @@ __device__ __forceinline__ void pipe_commit_node(const KParams& P, const KParams
                                                  u32 orig, u64 rec, u32 lane) {
   const i64 end = start + L;   // job->end_time = start_time + time_limit, JobScheduler.cpp:6772
   Res f = rl_res(e.r, 0);      // entry 0 = the entry at `now`
-  if (h.len <= 64) tl_commit_regs(P, hd, tl_of<kW>(P, hd), e, h.len, start, end, alloc, lane, orig);
+  if (h.len <= kTlChunk) tl_commit_regs(P, hd, tl_of<kW>(P, hd), e, h.len, start, end, alloc, lane, orig);
   else tl_commit(Pmem, hd, start, end, alloc, lane, orig);
   const double ratio = ((double)alloc.cpu / 256.0) / ((double)h.total.cpu / 256.0);
   const double ncost = __longlong_as_double((long long)cost0) + (double)(end - start) * ratio;

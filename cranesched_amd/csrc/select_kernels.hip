@@ -955,7 +955,7 @@ template <bool kW> __device__ __forceinline__ Res narrow(Res r) { if (!kW) { r.c
 // The window minimum of a loaded node block (:6278-6283), wave-uniform.
 template <bool kW = true>
 __device__ __forceinline__ Res block_window_min(const KParams& P, NodeHdr* hd, const NodeHdr& h, const TlEntry& e, i64 E, u32 lane) {
-  return uni_res(narrow<kW>(h.len <= 64 ? window_min_regs(e, lane < h.len, h.avail0, E)
+  return uni_res(narrow<kW>(h.len <= kTlChunk ? window_min_regs(e, lane < h.len, h.avail0, E)
                                         : window_min(tl_of<kW>(P, hd), h.len, h.avail0, E, lane)));
 }
 
@@ -976,7 +976,7 @@ __device__ __forceinline__ bool fits_now(const Req& mv, const Res& m, const Res&
 template <bool kW = true>
 __device__ __forceinline__ i64 block_next_fit(const KParams& P, NodeHdr* hd, const NodeHdr& h, const TlEntry& e, const Res& alloc,
                                               i64 L, i64 t0, u32 lane) {
-  return h.len <= 64 ? next_fit_regs(e, h.len, uni_res(narrow<kW>(alloc)), L, t0, lane) : next_fit_wave(tl_of<kW>(P, hd), h.len, &alloc, L, t0);
+  return h.len <= kTlChunk ? next_fit_regs(e, h.len, uni_res(narrow<kW>(alloc)), L, t0, lane) : next_fit_wave(tl_of<kW>(P, hd), h.len, &alloc, L, t0);
 }
 
 // EarliestStartSubsetSelector::CalcEarliestStartTime over k nodes as the fixed point t <- max_i next_fit(i, t), from t = now;
@@ -1291,7 +1291,7 @@ __device__ __forceinline__ u32 pack_dip(u32 dt, u32 dcm) {
   return (t16 << 16) | ((c > 255u ? 255u : c) << 8) | (m > 255u ? 255u : m);
 }
 __device__ __forceinline__ bool post_dip(const KParams& P, const GresDev& G, int* fl, u32 code, const TlEntry& e, u32 len, const Req& mv, i64 E, u32 lane, const Res& m) {
-  if (len > 64) { if (lane == 0) fl[4] = (int)kNone; return false; }
+  if (len > kTlChunk) { if (lane == 0) fl[4] = (int)kNone; return false; }
   const bool inw = lane == 0 || (lane < len && e.t < E);
   const bool cand = inw && lane >= 1 && !feasible_counts(mv, e.r.cpu, e.r.mem, 0u, class_counts(e.r.gres, G), G);
   const u64 b = __ballot(cand);
@@ -1380,7 +1380,7 @@ __device__ __noinline__ int worker_job_slow(const KParams& Pm, const WorkerShare
       }
     }
     if constexpr (kSelect) {   // (k_select's scanners alone read the dip words: post_dip)
-      if (!ok && !excl_job && len <= 64) {
+      if (!ok && !excl_job && len <= kTlChunk) {
         TlEntry e;
         e.t = kInf;
         if (lane < len) e = T[lane];
@@ -1572,7 +1572,7 @@ __device__ __forceinline__ void load_block(const KParams& P, u32 q, u32 lane, No
 // where the misprediction is found — nothing on the path of a prediction that holds.  Register maps (<= 64 entries) only.
 // (G: the GRES layout — P.gres, or the caller's own copy of it when P is a scalar copy of the block: kparams_scalar)
 __device__ __forceinline__ void record_dip(const KParams& P, const GresDev& G, u32 q, const TlEntry& e, u32 len, const Req& mv, i64 E, u32 lane) {
-  if (len > 64) return;
+  if (len > kTlChunk) return;
   const bool cand = lane >= 1 && lane < len && e.t < E && e.t - P.now < 0xFFFFFFFFll &&
                     !feasible_counts(mv, e.r.cpu, e.r.mem, 0u, class_counts(e.r.gres, G), G);
   const u64 b = __ballot(cand);
@@ -1595,7 +1595,7 @@ __device__ __forceinline__ void commit_pick(const KParams& P, const JobCtx& J, c
   const i64 end = start + J.L;
   const Res e0 = rl_res(e.r, 0);  // entry at `now`
   u32 newlen;
-  if (h.len <= 64) newlen = tl_commit_regs(P, hd, tl_of(P, hd), e, h.len, start, end, x.res, lane, orig);
+  if (h.len <= kTlChunk) newlen = tl_commit_regs(P, hd, tl_of(P, hd), e, h.len, start, end, x.res, lane, orig);
   else newlen = tl_commit(P, hd, start, end, x.res, lane, orig);
   const double ratio = ((double)x.res.cpu / 256.0) / ((double)h.total.cpu / 256.0);
   const double ncost = x.cost + (double)(end - start) * ratio;
@@ -1686,7 +1686,7 @@ __device__ __noinline__ int worker_job_multi(const KParams& P, const WorkerShare
         code = 2;
       }
     }
-    if (!ok && h.len <= 64) {
+    if (!ok && h.len <= kTlChunk) {
       if (feasible(J.min_view, h.avail0, f, P.gres)) post_dip(P, P.gres, sh.flag, wcode, e, h.len, J.min_view, J.E, lane, m);
       else post_dip(P, P.gres, sh.flag, wcode, e, 1u, J.min_view, J.E, lane, h.avail0);
     } else if (lane == 0) {
@@ -1778,7 +1778,7 @@ __device__ __forceinline__ void helper_commit_regs(const KParams& P, const GresD
   const i64 end = start + J.L;
   const Res e0 = rl_res(e.r, 0);  // entry at `now`
   u32 newlen;
-  if (h.len <= 64) newlen = tl_commit_regs(P, hd, tl_of(P, hd), e, h.len, start, end, res, lane, J.orig);
+  if (h.len <= kTlChunk) newlen = tl_commit_regs(P, hd, tl_of(P, hd), e, h.len, start, end, res, lane, J.orig);
   else newlen = tl_commit(P, hd, start, end, res, lane, J.orig);
   // MinCpuTimeRatioFirst::UpdateCost, JobScheduler.h:47-53 — ratio first, then x seconds, then +=
   const double ratio = ((double)res.cpu / 256.0) / ((double)h.total.cpu / 256.0);
@@ -2123,7 +2123,7 @@ __global__ __launch_bounds__(kBlock) void k_select(const KParams P, const KParam
           // one coalesced read: header (broadcast) + entry `lane` of the time map
           NodeHdr* hd; NodeHdr h; TlEntry e;
           load_block(P, q, lane, hd, h, e);
-          if (h.len > 64) { divert = true; break; }  // long time map: the general routines take over from here
+          if (h.len > kTlChunk) { divert = true; break; }  // long time map: the general routines take over from here
           PROF_T(a1);
           PROF_ADD(1, a0, a1);  // node block load
           Res f;
@@ -2187,7 +2187,7 @@ __global__ __launch_bounds__(kBlock) void k_select(const KParams P, const KParam
           if (tcode != kNone) {
             if (!resv_part) first_resv = P.first_resv[qbeg + slot_of_code(tcode)];  // in flight with the block
             load_block(P, qbeg + slot_of_code(tcode), lane, hd, h, e);
-            if (h.len > 64) divert = true;
+            if (h.len > kTlChunk) divert = true;
           }
           PROF_T(b0l);
           PROF_ADD(8, b0, b0l);  // phase B: node block load

@@ -470,7 +470,7 @@ __device__ __noinline__ void wide_test_task(const KParams* Pg, const WideHome sh
     // for its commit (retirement is in id order) and none contradicted its prediction — no verdict through the slot, no claim by another
     // wave, no second load of the node block (nobody else may touch the node: a younger task on it waits for this one).  (Waiting a few
     // hundred cycles for the predecessors' claims so that more tasks take this path was measured and does not pay: profiles/r05_ab_fuse_spin.txt)
-    if (ok && P.wide_tester_opt != 0u && h.len <= 64 && vld(&sh.w->retired) + 1u == my && vld(&T->gid) <= vld(&sh.w->allow) && vld(&sh.w->flush_job) > ji) {
+    if (ok && P.wide_tester_opt != 0u && h.len <= kTlChunk && vld(&sh.w->retired) + 1u == my && vld(&T->gid) <= vld(&sh.w->allow) && vld(&sh.w->flush_job) > ji) {
       u32 won = 0;
       if (lane == 0) won = atomicCAS(&sh.w->retired, my - 1u, my) == my - 1u ? 1u : 0u;
       if (uni32(won)) {

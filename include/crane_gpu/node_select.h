@@ -363,6 +363,35 @@ const char* cns_debug_last_kernel(const cns_handle* h);
 int cns_debug_get_prof(cns_handle* h, uint64_t* out, uint32_t capacity);
 uint32_t cns_debug_engine_partitions(const cns_handle* h);   /* schedulers of the snapshot as the engine runs them: groups of partitions that share nodes + one per reservation (the rows of cns_debug_get_prof) */
 
+/* The constants at which the selection kernels (k_select, k_pipe, k_wide) change path, as this build has them: read from the
+ * kernels' own constants and from the figures the launch plan works on.  Not a limit of the interface — every value below is
+ * served — but the places where a test has to stand (tests/select_seams.py puts a case on each).  Needs no handle and no
+ * device. */
+#define CNS_SHAPE_MAX_WIDTHS 8u
+typedef struct cns_tile_shape {       /* a kernel's register tile: `lanes` nodes per row, instantiated for these rows per lane */
+  uint32_t lanes;
+  uint32_t num_widths;
+  uint32_t widths[CNS_SHAPE_MAX_WIDTHS];   /* ascending; a partition of n slots runs on the narrowest w with n <= lanes * w */
+} cns_tile_shape;
+typedef struct cns_select_shape_info {
+  uint32_t tl_chunk;          /* entries of a node's time map held one per lane: longer maps take the chunked routines (64) */
+  uint32_t tl_cap;            /* entries a node's time map may hold (kTlCap)                                                */
+  uint32_t multi_k;           /* k_select: node_num served by the parallel multi-node protocol (kMultiK)                    */
+  uint32_t pipe_max_k;        /* k_pipe / k_wide: node_num served by the pipeline (kPMaxK)                                  */
+  uint32_t max_upd;           /* owner updates of one job broadcast through workgroup memory (kMaxUpd)                      */
+  uint32_t lds_heap;          /* the heap of a job's nodes stays in workgroup memory below this node_num (kLdsHeap)         */
+  uint32_t alloc_cache;       /* k_select: entries of the backfill path's allocation cache (kAllocCache)                    */
+  uint32_t pipe_ring;         /* k_pipe: task slots (kPRing)                                                                */
+  uint32_t wide_task_ring;    /* k_wide: task slots of a home workgroup (kWTRing)                                           */
+  uint32_t pipe_xring;        /* k_pipe: exchanges the supervisor may lag behind the scanners (kPXRing)                     */
+  uint32_t wide_window;       /* k_wide, 64-wave build: jobs decided per window at most (kWJ; 0: built without windows)     */
+  uint32_t sel_dip_max_npl;   /* k_select: tiles of up to this many rows keep a dip per node (kSelDipMaxNpl)                */
+  cns_tile_shape select, pipe;
+  cns_tile_shape wide[4];     /* k_wide's builds, widest first ...                                                          */
+  uint32_t wide_waves[4];     /* ... and their scanner waves per partition (64, 32, 16, 8)                                  */
+} cns_select_shape_info;
+int cns_select_shape(cns_select_shape_info* out);
+
 #ifdef __cplusplus
 }
 #endif
