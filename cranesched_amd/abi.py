@@ -532,6 +532,15 @@ TileShape = namedtuple("TileShape", ("lanes", "widths"))          # widths: asce
 SelectShape = namedtuple("SelectShape", tuple(f for f, t in CnsSelectShapeInfo._fields_ if t is C.c_uint32) + ("select", "pipe", "wide"))
 
 
+# cns_probe_shape (include/crane_gpu_probe/probe.h): the constants at which k_probe changes path
+class CnsProbeShapeInfo(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("block", "dip_cpu_sat", "dip_mem_sat", "dip_gres_sat", "gres_classes", "gres_names", "max_types",
+                                          "heap_ent_bytes", "loff_clamp", "pad")] + [("scratch_cap", C.c_uint64)]
+
+
+ProbeShape = namedtuple("ProbeShape", tuple(f for f, _ in CnsProbeShapeInfo._fields_ if f != "pad"))
+
+
 class CnsResvqSoa(C.Structure):
     _fields_ = [("num_queries", C.c_uint64), ("start_sec", _P), ("duration_sec", _P), ("node_num", _P), ("cand_offsets", _P),
                 ("cand_nodes", _P), ("find_earliest", _P)]

@@ -66,6 +66,7 @@
 #include "preempt_host.inc"    // the host side of a cycle with preemption: who may preempt, the buffer plan, the running side, the fold of the results (no HIP in there either)
 #include "running_preempt_check_host.inc" // the input rules of cns_running_select_preempt (no HIP in there either)
 #include "running_attrs_check_host.inc" // the input rules of the calls of running_attrs.h (no HIP in there either)
+#include "probe_plan_host.inc" // the launch plan of k_probe: workgroups, heap stride, scratch bytes under the cap (no HIP in there either)
 #include "sort_host.inc"       // the arithmetic of the pair sort: passes, tiles, histogram bytes (no HIP in there either)
 #include "resvq_passes.inc"    // the radix passes over the segment numbers of cns_resvq_run's sort (no HIP in there either)
 #include "buf_slots.h"         // the slots of cns_engine's per-feature buffer sets
@@ -178,6 +179,7 @@ struct cns_engine {
   DevBuf d_pb[PB_COUNT];
   u32 pkmax = 1;                                // the widest node_num of the probes that reach a walk
   bool have_probes = false, probes_answered = false;
+  u64 probe_grid = 0; u32 probe_stride = 0;     // what the last cns_probe_run_resident launched (cns_debug_get_probe_plan)
   bool pre_call = false;                        // inside cns_select_preempt with preemption enabled
   bool run_preempt = false;                     // the last successful cycle was such a call (probes are not served behind it)
   double probe_ms = 0.0;

@@ -64,17 +64,17 @@ int cns_probe_run_resident(cns_handle* h, double* kernel_ms) {
   HIPCHK(h, hipMemsetAsync(B[PB_FAULT].p, 0, 16, h->stream));
   K.fault = B[PB_FAULT].as<u32>();
   float ms = 0;
+  u64 grid = 0;
+  u32 stride = 0;
   if (h->pt.Jg) {
     // Persistent one-wave workgroups, as many as the device holds at once (the runtime's occupancy figure for this kernel x its compute
-    // units), never more than there are probes; the heap scratch is per RESIDENT workgroup: min(widest partition, widest node_num) + 1.
+    // units), never more than there are probes; the heap scratch is per RESIDENT workgroup and capped: probe_plan_host.inc.
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_probe, kProbeBlock, 0) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
-    const u64 resident = (u64)std::max(per_cu, 1) * std::max<u32>(h->num_cus, 1);
-    const u32 stride = std::min<u32>(h->rlay.max_np, h->pkmax) + 1u;
-    u64 grid = std::min<u64>(h->pt.Jg, resident);
-    const u64 scratch_cap = 1ull << 30;       // ... and at most 1 GiB of it (a probe over thousands of nodes of a giant partition)
-    grid = std::max<u64>(1, std::min<u64>(grid, scratch_cap / ((u64)stride * sizeof(HeapEnt))));
-    HIPCHK(h, B[PB_HEAP].ensure((size_t)grid * stride * sizeof(HeapEnt)));
+    const cns_probe_plan::Plan L = cns_probe_plan::plan(cns_probe_plan::resident(per_cu, h->num_cus), h->pt.Jg, h->rlay.max_np, h->pkmax, (uint32_t)sizeof(HeapEnt),
+                                                        cns_probe_plan::scratch_cap());
+    grid = L.grid; stride = L.stride;
+    HIPCHK(h, B[PB_HEAP].ensure((size_t)L.bytes));
     K.heap = B[PB_HEAP].as<HeapEnt>();
     HIPCHK(h, B[PB_CTR].ensure(16));
     HIPCHK(h, hipMemsetAsync(B[PB_CTR].p, 0, 16, h->stream));
@@ -99,6 +99,7 @@ int cns_probe_run_resident(cns_handle* h, double* kernel_ms) {
     return fail(h, CNS_ERR_DEVICE_FAULT, "device invariant violated: code " + std::to_string(fault[0]) + " probe " + std::to_string(fault[1]) +
                                              " aux " + std::to_string(fault[2]) + "," + std::to_string(fault[3]) + " (k_probe)");
   h->probe_ms = ms;
+  h->probe_grid = grid; h->probe_stride = stride;
   h->probes_answered = true;
   if (kernel_ms) *kernel_ms = ms;
   return CNS_OK;
@@ -125,4 +126,43 @@ int cns_probe(cns_handle* h, const cns_job_soa* probes, cns_placement_soa* out, 
   if (int rc = cns_probe_upload(h, probes)) return rc;
   if (int rc = cns_probe_run_resident(h, kernel_ms)) return rc;
   return cns_probe_download(h, out);
+}
+
+int cns_probe_shape(cns_probe_shape_info* out) {
+  if (!out) return CNS_ERR_INVALID_ARG;
+  cns_probe_shape_info s{};
+  s.block = (u32)kProbeBlock;
+  s.dip_cpu_sat = kDipCpuSat; s.dip_mem_sat = kDipMemSat; s.dip_gres_sat = kDipGresSat;
+  s.gres_classes = (u32)kMaxClasses; s.gres_names = (u32)kMaxNames;
+  s.max_types = CNS_MAX_NODE_TYPES;
+  s.heap_ent_bytes = (u32)sizeof(HeapEnt);
+  s.loff_clamp = kProbeLoffClamp;
+  s.scratch_cap = cns_probe_plan::kScratchCap;
+  *out = s;
+  return CNS_OK;
+}
+
+int cns_debug_get_probe_plan(cns_handle* h, uint64_t* grid, uint32_t* stride) {
+  if (!h || !grid || !stride) return fail(h, CNS_ERR_INVALID_ARG, "cns_debug_get_probe_plan: null argument");
+  if (!h->have_probes || !h->probes_answered) return fail(h, CNS_ERR_STATE, "cns_debug_get_probe_plan before cns_probe_run_resident");
+  *grid = h->probe_grid; *stride = h->probe_stride;
+  return CNS_OK;
+}
+
+int cns_debug_get_dips(cns_handle* h, uint32_t* dip_t, uint32_t* dip_cm, uint32_t* dip_g) {
+  if (!h || !dip_t || !dip_cm || !dip_g) return fail(h, CNS_ERR_INVALID_ARG, "cns_debug_get_dips: null argument");
+  if (!h->have_run) return fail(h, CNS_ERR_STATE, "cns_debug_get_dips before a successful run");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t S = h->rlay.S;
+  std::vector<u32> t(std::max<size_t>(S, 1)), cm(t.size()), g(t.size());
+  HIPCHK(h, hipMemcpy(t.data(), h->d_dipt.p, S * sizeof(u32), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(cm.data(), h->d_dipcm.p, S * sizeof(u32), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(g.data(), h->d_dipg.p, S * sizeof(u32), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < h->lay.orig_pos_slot.size(); ++i) {   // slot order as cns_debug_get_costs; a slot the engine does not keep: no dip
+    const u32 q = h->lay.orig_pos_slot[i];
+    dip_t[i] = q == kNone ? 0xFFFFFFFFu : t[q];
+    dip_cm[i] = q == kNone ? 0u : cm[q];
+    dip_g[i] = q == kNone ? 0u : g[q];
+  }
+  return CNS_OK;
 }

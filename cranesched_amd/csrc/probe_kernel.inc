@@ -33,20 +33,22 @@ struct ProbeParams {
   u32 pad;
 };
 
+constexpr u32 kProbeLoffClamp = 0xFFFFFFFFu;   // KParams::dip_t is 32 bits of seconds after `now`: a longer time limit reaches every dip
 constexpr int kProbeBlock = 64;   // one wave: the routines of the exact test are wave-wide, and the parallelism is over probes
 
 // May the time-map entry behind a slot's dip (KParams::dip_*: packed upper bounds of one FUTURE entry below the front) host the
 // minimum view?  Every saturated field counts as "fits": only a necessary condition may filter.
 __device__ __forceinline__ bool probe_fits_dip(const Req& mv, u32 flags, u32 dcm, u32 dg, const GresDev& G) {
   const u32 dc = dcm >> 16, dm = dcm & 0xFFFFu;
+  static_assert(kDipCpuSat == 0xFFFFu && kDipMemSat == 0xFFFFu && kDipGresSat == 15u, "the packing of KParams::dip_cm / dip_g");
   const i64 rcpus = mv.cpu >> 8;          // whole cpus of the request, rounded down (the dip's are rounded up)
   const u64 rgib = mv.mem >> 30;          // GiB, rounded down
-  if (dc != 0xFFFFu && rcpus > (i64)dc) return false;
-  if (dm != 0xFFFFu && rgib > (u64)dm) return false;
+  if (dc != kDipCpuSat && rcpus > (i64)dc) return false;
+  if (dm != kDipMemSat && rgib > (u64)dm) return false;
   if (flags & kJfGres) {
     for (int g = 0; g < kMaxClasses; ++g) {
       const u32 need = (u32)((mv.gspec >> (8 * g)) & 0xFFull), have = (dg >> (4 * g)) & 15u;
-      if (have != 15u && need > have) return false;
+      if (have != kDipGresSat && need > have) return false;
     }
     for (int a = 0; a < kMaxNames; ++a) {
       const u32 tot = (mv.gtot >> (8 * a)) & 0xFFu;
@@ -54,7 +56,7 @@ __device__ __forceinline__ bool probe_fits_dip(const Req& mv, u32 flags, u32 dcm
       u32 have = 0;
       bool sat = false;
       for (int g = 0; g < kMaxClasses; ++g)
-        if ((G.name_bytes[a] >> (8 * g)) & 0xFFull) { const u32 h = (dg >> (4 * g)) & 15u; have += h; sat = sat || h == 15u; }
+        if ((G.name_bytes[a] >> (8 * g)) & 0xFFull) { const u32 h = (dg >> (4 * g)) & 15u; have += h; sat = sat || h == kDipGresSat; }
       if (!sat && have < tot) return false;
     }
   }
@@ -68,7 +70,7 @@ __device__ __forceinline__ void probe_next(const KParams& P, const KParams& Pm, 
                                            u64 lc, u32 ln, u32 lane, u64& oc, u32& op) {
   u64 bc = ~0ull;
   u32 bp = kNone;
-  const u32 loff = J.L >= 0xFFFFFFFFll ? 0xFFFFFFFFu : (u32)J.L;   // an entry t seconds after now lies in the window iff t < L (:6279)
+  const u32 loff = J.L >= (i64)kProbeLoffClamp ? kProbeLoffClamp : (u32)J.L;   // an entry t seconds after now lies in the window iff t < L (:6279)
   for (u32 o = lane; o < rn; o += (u32)kProbeBlock) {
     const u32 p = rb + o, q = qbeg + p;
     const u64 ck = cost_key(P.cost[q]);

@@ -297,9 +297,13 @@ __device__ __forceinline__ u32 nibbles_of(u64 cnt);
 __device__ __forceinline__ u32 mem_gib16(u32 mib);
 // KParams::dip_*: the packed upper bounds of one time-map entry, and "is it below the front somewhere" (on the summaries:
 // what the scanners' filters can tell apart)
+// (the values at which a field of a dip saturates: a saturated field says "at least this much" and may refuse nothing; cns_probe_shape names them)
+constexpr u32 kDipCpuSat = 0xFFFFu;    // whole cpus
+constexpr u32 kDipMemSat = 0xFFFFu;    // GiB
+constexpr u32 kDipGresSat = 15u;       // slots of one GRES class (a nibble)
 __device__ __forceinline__ u32 dip_cm_of(const Res& r) {
   const i64 c = r.cpu <= 0 ? 0 : ((r.cpu + 255) >> 8);
-  return ((u32)(c > 0xFFFF ? 0xFFFF : c) << 16) | mem_gib16(mem_mib_ceil(r.mem));
+  return ((u32)(c > (i64)kDipCpuSat ? (i64)kDipCpuSat : c) << 16) | mem_gib16(mem_mib_ceil(r.mem));
 }
 __device__ __forceinline__ u64 class_counts(u64 gres, const GresDev& L);
 __device__ __forceinline__ bool dip_below(const Res& e, const Res& front, const GresDev& L) {
@@ -1930,11 +1934,12 @@ __device__ __noinline__ i64 multi_backfill_par(const KParams& P, const GresDev* 
 //   gn = front GRES popcount per class, 4 bits each, saturating at 15
 // The front values only feed a NECESSARY condition (the worker's exact test decides), so rounding the
 // node side up and the request side down keeps the filter conservative.
-__device__ __forceinline__ u32 mem_gib16(u32 mib) { u32 g = (mib + 1023u) >> 10; return g > 0xFFFFu ? 0xFFFFu : g; }
+__device__ __forceinline__ u32 mem_gib16(u32 mib) { u32 g = (mib + 1023u) >> 10; return g > kDipMemSat ? kDipMemSat : g; }
 __device__ __forceinline__ u32 nibbles_of(u64 cnt) {  // byte g -> nibble g, saturating at 15
   const u64 hi = (cnt >> 4) & 0x0F0F0F0F0F0F0F0Full;
   const u64 nz = ((hi + 0x0F0F0F0F0F0F0F0Full) >> 4) & 0x0101010101010101ull;  // 1 where the byte is >= 16
-  u64 x = (cnt & 0x0F0F0F0F0F0F0F0Full) | (nz * 15ull);
+  static_assert(kDipGresSat == 15u, "a nibble per class");
+  u64 x = (cnt & 0x0F0F0F0F0F0F0F0Full) | (nz * (u64)kDipGresSat);
   x = (x | (x >> 4)) & 0x00FF00FF00FF00FFull;
   x = (x | (x >> 8)) & 0x0000FFFF0000FFFFull;
   x = (x | (x >> 16)) & 0x00000000FFFFFFFFull;

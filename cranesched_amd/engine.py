@@ -42,7 +42,8 @@ STEPS_ABI_SYMBOLS = ("cns_schedule_steps",)
 # ... and include/crane_gpu/preempt.h
 PREEMPT_ABI_SYMBOLS = ("cns_select_preempt", "cns_preempt_shape")
 # ... and include/crane_gpu_probe/probe.h
-PROBE_ABI_SYMBOLS = ("cns_probe", "cns_probe_upload", "cns_probe_run_resident", "cns_probe_download")
+PROBE_ABI_SYMBOLS = ("cns_probe", "cns_probe_upload", "cns_probe_run_resident", "cns_probe_download", "cns_probe_shape")
+PROBE_DEBUG_ABI_SYMBOLS = ("cns_debug_get_probe_plan", "cns_debug_get_dips")
 # ... and include/crane_gpu_resv/resv_probe.h
 RESVQ_ABI_SYMBOLS = ("cns_resvq_set_state", "cns_resvq_run", "cns_resvq_shape")
 # ... and include/crane_gpu_valid/validity.h
@@ -131,6 +132,15 @@ def select_shape() -> "abi.SelectShape":
     tile = lambda t: abi.TileShape(int(t.lanes), tuple(int(w) for w in t.widths[:t.num_widths]))
     scalars = [int(getattr(s, f)) for f in abi.SelectShape._fields[:-3]]
     return abi.SelectShape(*scalars, tile(s.select), tile(s.pipe), tuple((int(s.wide_waves[b]), tile(s.wide[b])) for b in range(4)))
+
+
+def probe_shape() -> "abi.ProbeShape":
+    """cns_probe_shape: the constants at which k_probe changes path, as this build has them.  Needs no handle and no GPU."""
+    s = abi.CnsProbeShapeInfo()
+    status = lib().cns_probe_shape(C.byref(s))
+    if status != 0:
+        raise EngineError(status, "cns_probe_shape")
+    return abi.ProbeShape(*[int(getattr(s, f)) for f in abi.ProbeShape._fields])
 
 
 class GpuNodeSelector:
@@ -414,6 +424,20 @@ class GpuNodeSelector:
     def probe_timing(self) -> dict:
         """HIP-event time of the last k_probe launch of this object."""
         return {"kernel_ms": getattr(self, "_probe_ms", 0.0)}
+
+    def probe_plan(self) -> tuple:
+        """cns_debug_get_probe_plan: (workgroups, heap entries per workgroup) of the last probe_run_resident / probe."""
+        g, st = C.c_uint64(0), C.c_uint32(0)
+        self._check(self._L.cns_debug_get_probe_plan(self._h, C.byref(g), C.byref(st)))
+        return int(g.value), int(st.value)
+
+    def dips(self) -> dict:
+        """cns_debug_get_dips: the dip the last cycle left at every (partition, node) slot, in the order of costs()."""
+        n = len(self._cluster.part_nodes)
+        t, cm, g = (np.zeros(n, np.uint32) for _ in range(3))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self._L.cns_debug_get_dips(self._h, p(t), p(cm), p(g)))
+        return {"t": t, "cpus": cm >> 16, "gib": cm & 0xFFFF, "gres": g}
 
     # -- reservation what-ifs (include/crane_gpu_resv/resv_probe.h) --------------------------------------------------------
     def set_resv_query_state(self, running: "abi.Running | None", reservations: "abi.Reservations | None"):

@@ -27,7 +27,13 @@
  *   - every job shape the cycle serves: node_num >= 1, ntasks > node_num, exclusive, include / exclude lists, fractional
  *     cpus, GRES typed / untyped, core ids up to 255, partitions that share nodes (a probe sees the slots of its own
  *     partition, the node's one time map, its own partition's cost), partitions of every width the engine serves — the state
- *     has the same layout whichever selection kernel produced it.
+ *     has the same layout whichever selection kernel produced it;
+ *   - a cycle over an EMPTY queue is a cycle: probes behind it are answered against the snapshot (running jobs, reservations) as
+ *     cns_set_nodes / cns_set_running left it; a probe into a partition the last cycle had no job for sees that partition's
+ *     snapshot, never what an earlier cycle on the handle left there;
+ *   - the table is validated like a queue (cns_upload_jobs): a request for a GRES class the layout does not define refuses the
+ *     whole call with CNS_ERR_INVALID_ARG ("probe job requests an undefined GRES class") and writes nothing — the reference
+ *     would ignore such a request.
  *
  * State.  CNS_ERR_STATE before a successful run and after anything that invalidates it (cns_set_nodes,
  * cns_set_reservations, cns_set_running, cns_upload_jobs without a run).  After a cycle that ran cns_select_preempt with
@@ -61,6 +67,34 @@ int cns_probe(cns_handle* h, const cns_job_soa* probes, cns_placement_soa* out, 
 int cns_probe_upload(cns_handle* h, const cns_job_soa* probes);       /* validates like cns_upload_jobs, packs the records on the device */
 int cns_probe_run_resident(cns_handle* h, double* kernel_ms);          /* may be repeated: every run answers the uploaded probes anew */
 int cns_probe_download(cns_handle* h, cns_placement_soa* out);
+
+/* The constants at which k_probe changes path, as this build has them (tests/probe_seams.py puts a case on each).  Needs no handle
+ * and no GPU; out == NULL -> CNS_ERR_INVALID_ARG. */
+typedef struct cns_probe_shape_info {
+  uint32_t block;          /* lanes of a probe's workgroup: the candidate walk strides over a partition's slots, the emit loop over
+                              node_num, in steps of this */
+  uint32_t dip_cpu_sat;    /* a dip's whole cpus (rounded up) saturate here: a saturated field refuses nothing */
+  uint32_t dip_mem_sat;    /* ... its GiB (rounded up) */
+  uint32_t dip_gres_sat;   /* ... its slots of one GRES class */
+  uint32_t gres_classes;   /* classes / names a dip and a request are compared over */
+  uint32_t gres_names;
+  uint32_t max_types;      /* distinct res_total records of a snapshot (CNS_MAX_NODE_TYPES): one lane per type */
+  uint32_t heap_ent_bytes; /* one entry of a workgroup's heap scratch */
+  uint32_t loff_clamp;     /* a time limit of this many seconds or more reaches every dip (dips are 32 bits of seconds after now) */
+  uint32_t pad;
+  uint64_t scratch_cap;    /* bytes of heap scratch a call may take: min(widest partition, widest node_num) + 1 entries per resident
+                              workgroup, fewer workgroups where that would exceed it, never fewer than one.  The environment variable
+                              CNS_PROBE_SCRATCH_CAP (bytes) lowers it, never raises it; a value that does not begin with a digit is
+                              ignored. */
+} cns_probe_shape_info;
+int cns_probe_shape(cns_probe_shape_info* out);
+
+/* Test hooks, beside cns_debug_get_costs.  cns_debug_get_probe_plan: the workgroups and the heap entries per workgroup of the last
+ * cns_probe_run_resident (0, 0 where no probe reached a walk).  cns_debug_get_dips: per (partition, node) slot, [len(part_nodes)] in
+ * the order of cns_debug_get_costs, the dip the last cycle left: seconds after now (0xFFFFFFFF: none) | whole cpus << 16 | GiB |
+ * a nibble per GRES class. */
+int cns_debug_get_probe_plan(cns_handle* h, uint64_t* grid, uint32_t* stride);
+int cns_debug_get_dips(cns_handle* h, uint32_t* dip_t, uint32_t* dip_cm, uint32_t* dip_g);
 
 #ifdef __cplusplus
 }

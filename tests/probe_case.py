@@ -6,6 +6,8 @@ last job.  backend "oracle" is the restated oracle, "ref" the reference's own co
 never comes from the engine."""
 from __future__ import annotations
 
+import dataclasses
+
 import numpy as np
 
 from cranesched_amd import abi
@@ -79,8 +81,28 @@ def ordered(jobs: abi.Jobs, batch: int = 0) -> abi.Jobs:
     return take(jobs, np.arange(batch))
 
 
-def expected(cluster, jobs, probes, now, running=None, reservations=None, batch=0, backend="oracle", **cfg) -> abi.Placements:
-    """Per probe i: one cycle over `ordered jobs + [probe i]` with batch size 0; what it wrote for the last job.  -> the probes' Placements."""
+def jobs_key(jobs: abi.Jobs):
+    """The content of a job table, hashable: two tables with the same arrays are the same queue."""
+    return tuple(None if getattr(jobs, f.name) is None else (str(getattr(jobs, f.name).dtype), getattr(jobs, f.name).tobytes()) for f in dataclasses.fields(jobs))
+
+
+class CycleMemo:
+    """pyoracle.select on one snapshot, every distinct queue run once and kept: the replays of one select case ask for the same prefixes
+    again and again (the cycle of split n + 1 is the queue + [probe] of split n).  select(jobs, backend) -> OracleRun; the runs stay open."""
+
+    def __init__(self, cluster, now, running=None, reservations=None, **cfg):
+        self.args, self.kw, self.runs = (cluster, now), dict(running=running, reservations=reservations, **cfg), {}
+
+    def select(self, jobs, backend="oracle"):
+        key = (backend, jobs_key(jobs))
+        if key not in self.runs:
+            self.runs[key] = pyoracle.select(self.args[0], jobs, self.args[1], backend=backend, **self.kw)
+        return self.runs[key]
+
+
+def expected(cluster, jobs, probes, now, running=None, reservations=None, batch=0, backend="oracle", memo: "CycleMemo | None" = None, **cfg) -> abi.Placements:
+    """Per probe i: one cycle over `ordered jobs + [probe i]` with batch size 0; what it wrote for the last job.  -> the probes' Placements.
+    memo: a CycleMemo of this snapshot and configuration — the cycles are taken from it, and kept in it."""
     base = ordered(jobs, batch)
     Q = probes.num_jobs
     out = abi.Placements(Q, probes.total_places())
@@ -88,7 +110,10 @@ def expected(cluster, jobs, probes, now, running=None, reservations=None, batch=
     out.place_offsets[:Q + 1] = off
     for i in range(Q):
         q = concat(base, take(probes, [i]))
-        run = pyoracle.select(cluster, q, now, running=running, reservations=reservations, scheduled_batch_size=0, backend=backend, **cfg)
+        if memo is not None:
+            run = memo.select(q, backend)
+        else:
+            run = pyoracle.select(cluster, q, now, running=running, reservations=reservations, scheduled_batch_size=0, backend=backend, **cfg)
         pl = run.placements
         last = q.num_jobs - 1
         out.start_sec[i] = pl.start_sec[last]
@@ -97,7 +122,8 @@ def expected(cluster, jobs, probes, now, running=None, reservations=None, batch=
         o = int(off[i])
         for f in ("node_idx", "ntasks", "cpu_raw", "mem", "core_lo", "core_hi", "gres", "core_w2", "core_w3"):
             getattr(out, f)[o:o + (b - a)] = getattr(pl, f)[a:b]
-        run.close()
+        if memo is None:
+            run.close()
     return out
 
 

@@ -56,9 +56,57 @@ def test_probe_calls_reject_null_arguments_without_a_gpu(built):
     assert out.start_sec[0] == 0 and out.node_idx[0] == abi.NODE_NONE, "a refused call writes nothing"
 
 
+def test_probe_shape_needs_no_handle_and_refuses_a_null_record(built):
+    from cranesched_amd import abi, engine
+    L = engine.lib()
+    assert "cns_probe_shape" in engine.PROBE_ABI_SYMBOLS
+    assert L.cns_probe_shape(None) == -1   # CNS_ERR_INVALID_ARG
+    rec = abi.CnsProbeShapeInfo()
+    C.memset(C.byref(rec), 0xEE, C.sizeof(rec))
+    assert L.cns_probe_shape(C.byref(rec)) == 0
+    assert rec.pad == 0 and C.sizeof(rec) == 10 * 4 + 8
+    s = engine.probe_shape()
+    assert s == engine.probe_shape() and isinstance(s, abi.ProbeShape)
+    for n in engine.PROBE_DEBUG_ABI_SYMBOLS:
+        assert hasattr(L, n), n
+    assert L.cns_debug_get_probe_plan(None, None, None) == -1 and L.cns_debug_get_dips(None, None, None, None) == -1
+
+
+def test_probe_shape_record_mirrors_the_header():
+    """abi.CnsProbeShapeInfo field for field against the struct in the header."""
+    from cranesched_amd import abi
+    src = open(HEADER).read()
+    body = re.search(r"typedef struct cns_probe_shape_info \{(.*?)\} cns_probe_shape_info;", src, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    decls = re.findall(r"(uint32_t|uint64_t)\s+([a-z_0-9]+);", body)
+    want = [(f, {C.c_uint32: "uint32_t", C.c_uint64: "uint64_t"}[t]) for f, t in abi.CnsProbeShapeInfo._fields_]
+    assert [(n, t) for t, n in decls] == want, decls
+    assert abi.ProbeShape._fields == tuple(f for f, _ in want if f != "pad")
+
+
+def test_the_shipped_probe_figures(built):
+    """The constants of the shipped build (csrc/probe_kernel.inc, select_kernels.hip, probe_plan_host.inc, node_select.h), and that the
+    record is filled from them: the source names each constant where the record takes it."""
+    from cranesched_amd import abi, engine
+    from tests import probe_seams as ps
+    s = engine.probe_shape()
+    assert s == (64, 0xFFFF, 0xFFFF, 15, abi.MAX_GRES_CLASSES, abi.MAX_GRES_NAMES, 64, s.heap_ent_bytes, 0xFFFFFFFF, 1 << 30)
+    assert s.heap_ent_bytes % 8 == 0 and 48 <= s.heap_ent_bytes <= 128, "node, slot, ntasks, the cost and one Res"
+    assert s == ps.SHIPPED
+    csrc = os.path.join(ROOT, "cranesched_amd", "csrc")
+    host = open(os.path.join(csrc, "probe_host.inc")).read()
+    for line in ("s.block = (u32)kProbeBlock;", "s.dip_cpu_sat = kDipCpuSat; s.dip_mem_sat = kDipMemSat; s.dip_gres_sat = kDipGresSat;",
+                 "s.gres_classes = (u32)kMaxClasses; s.gres_names = (u32)kMaxNames;", "s.max_types = CNS_MAX_NODE_TYPES;", "s.loff_clamp = kProbeLoffClamp;"):
+        assert line in host, line
+    kern = open(os.path.join(csrc, "probe_kernel.inc")).read()
+    fits = kern[kern.index("bool probe_fits_dip("):kern.index("void probe_next(")]
+    assert "dc != kDipCpuSat" in fits and "dm != kDipMemSat" in fits and fits.count("have != kDipGresSat") == 1 and fits.count("h == kDipGresSat") == 1
+    assert "J.L >= (i64)kProbeLoffClamp ? kProbeLoffClamp : (u32)J.L" in kern and "o += (u32)kProbeBlock" in kern and kern.count("i += (u32)kProbeBlock") == 3
+
+
 def test_python_surface(built):
     from cranesched_amd.engine import GpuNodeSelector
-    for m in ("probe", "probe_upload", "probe_run_resident", "probe_download", "probe_timing"):
+    for m in ("probe", "probe_upload", "probe_run_resident", "probe_download", "probe_timing", "probe_plan", "dips"):
         assert callable(getattr(GpuNodeSelector, m))
 
 
