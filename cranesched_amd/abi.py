@@ -532,6 +532,15 @@ TileShape = namedtuple("TileShape", ("lanes", "widths"))          # widths: asce
 SelectShape = namedtuple("SelectShape", tuple(f for f, t in CnsSelectShapeInfo._fields_ if t is C.c_uint32) + ("select", "pipe", "wide"))
 
 
+# cns_serial_shape (include/crane_gpu/node_select.h): the loop shapes of the serial protocol (k_mem, k_giant)
+class CnsSerialShapeInfo(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("scan_lanes", "scan_trip_rows", "mem_words", "giant_mem_words", "mem_slots", "giant_mem_slots", "helper_lanes",
+                                          "helper_trip_slots", "helpers_max", "helper_budget", "helpers_min", "select_tile_slots")]
+
+
+SerialShape = namedtuple("SerialShape", tuple(f for f, _ in CnsSerialShapeInfo._fields_))
+
+
 # cns_probe_shape (include/crane_gpu_probe/probe.h): the constants at which k_probe changes path
 class CnsProbeShapeInfo(C.Structure):
     _fields_ = [(f, C.c_uint32) for f in ("block", "dip_cpu_sat", "dip_mem_sat", "dip_gres_sat", "gres_classes", "gres_names", "max_types",

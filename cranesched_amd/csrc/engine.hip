@@ -1160,6 +1160,21 @@ int cns_select_shape(cns_select_shape_info* out) {
   return CNS_OK;
 }
 
+int cns_serial_shape(cns_serial_shape_info* out) {
+  if (!out) return CNS_ERR_INVALID_ARG;
+  using W = w8::WideInfo;               // k_mem / k_giant are the 8-wave build's k_wide<1> in serial-only mode
+  const cns_plan::Facts& F = plan_facts();
+  static_assert(W::mem_slots == W::mem_lanes * 64u * W::mem_words && W::giant_mem_slots == W::mem_lanes * 64u * W::giant_mem_words, "cns_serial_shape: one bit per row of a scanner lane");
+  cns_serial_shape_info s{};
+  s.scan_lanes = W::mem_lanes; s.scan_trip_rows = W::mem_trip;
+  s.mem_words = W::mem_words; s.giant_mem_words = W::giant_mem_words; s.mem_slots = F.mem_slots; s.giant_mem_slots = F.giant_mem_slots;
+  s.helper_lanes = W::block; s.helper_trip_slots = W::giant_trip;
+  s.helpers_max = F.giant_helpers_max; s.helper_budget = F.giant_helper_budget; s.helpers_min = cns_plan::kGiantMinHelpers;
+  s.select_tile_slots = F.select.slots();
+  *out = s;
+  return CNS_OK;
+}
+
 int cns_get_partition_status(const cns_handle* h, uint8_t* status, uint32_t capacity) {
   if (!h || !status) return fail(const_cast<cns_handle*>(h), CNS_ERR_INVALID_ARG, "cns_get_partition_status: null argument");
   if (!h->have_nodes) return fail(const_cast<cns_handle*>(h), CNS_ERR_STATE, "cns_get_partition_status before cns_set_nodes");

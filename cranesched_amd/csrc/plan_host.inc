@@ -32,6 +32,7 @@ inline Switch parse_kernel_switch(const char* e) {
   return Switch::Other;
 }
 constexpr u32 kPinAuto = 0, kPinSelect = 1;   // cns_kernel_pin (engine.hip asserts the values)
+constexpr u32 kGiantMinHelpers = 4;           // k_giant with fewer helper workgroups per partition is not worth its hand-off: k_mem (plan_serial_launch)
 
 // ---- what the build says ------------------------------------------------------------------------------------------------------
 struct Tiles {                        // a kernel's register tile: `lanes` nodes per row, instantiated for these rows per lane (ascending)
@@ -162,7 +163,7 @@ inline void plan_serial_launch(const Facts& F, const Inputs& in, bool giant_shap
   if (L.max_np > F.giant_mem_slots) return;   // (cns_set_nodes refuses such groups: never reached)
   // 64 helper workgroups per launch at most (8 per XCD): C4's k_wide launch beside it keeps its 8 x 17 workgroups
   const u32 nh = std::min(F.giant_helpers_max, F.giant_helper_budget / std::max(nparts, 1u));
-  if ((giant_shape || in.sw == Switch::Giant) && in.sw != Switch::Mem && !in.protocol_off && !in.helpers_unproven && in.num_cus != 0 && nh >= 4) {
+  if ((giant_shape || in.sw == Switch::Giant) && in.sw != Switch::Mem && !in.protocol_off && !in.helpers_unproven && in.num_cus != 0 && nh >= kGiantMinHelpers) {
     Candidate c;
     c.family = Family::Giant; c.build = 3; c.waves = W.waves; c.width = 1; c.giant_masks = true; c.extra = nh; c.block = W.tiles.block; c.waits = true;
     c.grid = c.holds = nparts * (1u + nh);   // the home of partition i is block i

@@ -133,6 +133,7 @@ static_assert(kWJ + 8u < kWRing, "the decisions of a window must fit the decisio
 constexpr u32 kWTRing = 64;                    // task slots of the home workgroup (power of two, <= 64: one lane per slot in drain)
 constexpr u32 kWNonePay = 0x3FFFFFFFu;         // payload "no node": code 0xFFFFFF, type 63
 constexpr u32 kWMs = (u32)kWTesters * 64u;     // memory-scanner lanes of a serial job
+constexpr u32 kWMsTrip = 4;                    // ... rows of one lane per trip of its scan (every load of a trip in flight before any is looked at; 64 % kWMsTrip == 0)
 constexpr u32 kWMemWords = 5;                  // ... each with up to 64 x kWMemWords rows: 448 x 320 = 143 360 slots (an ALL partition over 65 536 nodes
                                                // next to partitions that cover them once more = 131 072)
 constexpr u32 kWMemWordsGiant = 19;            // the giant instantiation of the serial-only mode (k_wide<1, false, kWMemWordsGiant>): 448 x 1 216 = 544 768
@@ -556,6 +557,7 @@ __device__ __noinline__ void wide_test_task(const KParams* Pg, const WideHome sh
 // (the host proves it with the occupancy figure, else k_mem runs); a home that waits for an answer longer than kGiantAnsSpin polls
 // raises device fault 43 and scans the job itself (exact; the host re-runs the cycle on k_mem).
 constexpr u32 kGiantHelpersMax = 64;           // helper workgroups per partition at most (one answer per lane of the home's tester wave 1)
+constexpr u32 kGiantTrip = 4;                  // slots of one helper lane per trip of giant_scan
 constexpr u32 kGiantExit = 0xFFFFFFFFu;        // GiantCtl::job >> 32: the home is done
 constexpr u32 kGiantAnsSpin = 1u << 22;        // home: polls for the helpers' answers to one job (> 1 s)
 constexpr u32 kGiantHelperSpin = 1u << 24;     // helper: polls for the next job (the home may scan a job with node lists alone meanwhile)
@@ -586,18 +588,18 @@ __device__ __forceinline__ u64 giant_eval(const KParams& P, const FastJob& F, u6
 __device__ __forceinline__ void giant_scan(const KParams& P, const FastJob& F, u64 tyok, u32 qbeg, u32 rb, u32 rn, bool own_range, u32 jt,
                                            u32 first, u32 stride, u64& ac, u32& ap, u64& tc, u32& tp) {
   ac = ~0ull; tc = ~0ull; ap = kNone; tp = kNone;
-  for (u32 o = first; o < rn; o += 4u * stride) {
-    bool a[4], b[4];
-    u64 ck[4];
+  for (u32 o = first; o < rn; o += kGiantTrip * stride) {
+    bool a[kGiantTrip], b[kGiantTrip];
+    u64 ck[kGiantTrip];
 #pragma unroll
-    for (u32 u = 0; u < 4u; ++u) {
+    for (u32 u = 0; u < kGiantTrip; ++u) {
       const u32 off = o + u * stride;
       const bool in = off < rn;
       ck[u] = giant_eval(P, F, tyok, qbeg, rb + (in ? off : 0u), own_range, jt, a[u], b[u]);
       a[u] = a[u] && in; b[u] = b[u] && in;
     }
 #pragma unroll
-    for (u32 u = 0; u < 4u; ++u) {   // (slots ascend and `<` is strict: the smallest slot among equal keys)
+    for (u32 u = 0; u < kGiantTrip; ++u) {   // (slots ascend and `<` is strict: the smallest slot among equal keys)
       if (a[u] && ck[u] < ac) { ac = ck[u]; ap = rb + o + u * stride; }
       if (b[u] && ck[u] < tc) { tc = ck[u]; tp = rb + o + u * stride; }
     }
@@ -1414,18 +1416,18 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
       u64 ac = ~0ull, tcs = ~0ull;
       u32 ap = kNone, tp = kNone;
       // The bits of the mask word under way collect in registers and go to the scratch masks once per word (a trip's four rows never
-      // straddle a word: 64 % 4 == 0): a read-modify-write of scratch per row and mask kept every trip waiting on the last one.
+      // straddle a word: 64 % kWMsTrip == 0): a read-modify-write of scratch per row and mask kept every trip waiting on the last one.
       const bool hjob = gnh != 0u && !(F.flags & (kJfIncl | kJfExcl));   // k_giant: round 0 comes from the helpers
       bool built = !hjob;                                                // the row masks of this job exist
       auto scan_rows = [&]() {
       u64 wb = 0, wa = 0;
-      for (u32 r0 = 0; r0 < jrows; r0 += 4u) {
-        u32 vlen[4], vty[4], vtg[4], vfmem[4];
-        int vfcpu[4];
-        u64 vfcnt[4], vck[4];
-        bool in[4];
+      for (u32 r0 = 0; r0 < jrows; r0 += kWMsTrip) {
+        u32 vlen[kWMsTrip], vty[kWMsTrip], vtg[kWMsTrip], vfmem[kWMsTrip];
+        int vfcpu[kWMsTrip];
+        u64 vfcnt[kWMsTrip], vck[kWMsTrip];
+        bool in[kWMsTrip];
 #pragma unroll
-        for (u32 u = 0; u < 4u; ++u) {
+        for (u32 u = 0; u < kWMsTrip; ++u) {
           const u32 pr = rb + (r0 + u) * kWMs + ml;
           in[u] = r0 + u < jrows && pr < rb + rn;
           const u32 q = qbeg + (in[u] ? pr : rb);
@@ -1436,7 +1438,7 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
           vtg[u] = (P.slot_tag && !own_range) ? (u32)P.slot_tag[q] : jt;
         }
 #pragma unroll
-        for (u32 u = 0; u < 4u; ++u) {
+        for (u32 u = 0; u < kWMsTrip; ++u) {
           if (!in[u]) continue;
           const u32 r = r0 + u;
           const u32 pr = rb + r * kWMs + ml;
@@ -1455,7 +1457,7 @@ __global__ __launch_bounds__(kWBlock) void k_wide(const KParams P, const KParams
           if (a && vck[u] < ac) { ac = vck[u]; ap = pr; }
           if (b && vck[u] < tcs) { tcs = vck[u]; tp = pr; }
         }
-        if (((r0 + 4u) & 63u) == 0u || r0 + 4u >= jrows) { bmask.w[r0 >> 6] = wb; amask.w[r0 >> 6] = wa; wb = 0; wa = 0; }
+        if (((r0 + kWMsTrip) & 63u) == 0u || r0 + kWMsTrip >= jrows) { bmask.w[r0 >> 6] = wb; amask.w[r0 >> 6] = wa; wb = 0; wa = 0; }
       }
       };
       if (!hjob) scan_rows();
@@ -2843,6 +2845,9 @@ struct WideInfo {
   static constexpr size_t ctl_bytes = sizeof(WideCtl);
   static constexpr u32 mem_slots = kWMs * 64u * kWMemWords;   // widest group the serial-only mode (KParams::serial_only) scans
   static constexpr u32 giant_mem_slots = kWMs * 64u * kWMemWordsGiant;   // ... and its giant instantiation (the 8-wave build only)
+  // the serial-only mode's loop shapes (cns_serial_shape): scanner lanes and their rows per trip, mask words, a helper lane's slots per trip
+  static constexpr u32 mem_lanes = kWMs, mem_trip = kWMsTrip, mem_words = kWMemWords, giant_mem_words = kWMemWordsGiant, giant_trip = kGiantTrip;
+  static_assert(64u % kWMsTrip == 0u, "a trip's rows never straddle a mask word");
   // the tile widths (rows per lane) of this build, ascending, and how many of the first ones also have a windows build
 #define CNS_WIDE_WIDTH(w) (u32)(w),
   static constexpr u32 widths[] = {CNS_WNPL_LIST(CNS_WIDE_WIDTH)};

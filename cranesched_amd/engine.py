@@ -27,7 +27,7 @@ _LIB = None
 ABI_SYMBOLS = ("cns_abi_version", "cns_last_error", "cns_create", "cns_destroy", "cns_set_nodes",
                "cns_set_reservations", "cns_set_running", "cns_set_host_threads", "cns_select", "cns_upload_jobs", "cns_run_resident", "cns_download",
                "cns_device_results", "cns_host_alloc", "cns_host_free", "cns_get_timing", "cns_debug_get_costs", "cns_debug_get_timeline", "cns_debug_get_timeline_cores",
-               "cns_debug_last_kernel", "cns_debug_get_prof", "cns_debug_engine_partitions", "cns_select_shape",
+               "cns_debug_last_kernel", "cns_debug_get_prof", "cns_debug_engine_partitions", "cns_select_shape", "cns_serial_shape",
                # several devices (csrc/group_host.inc)
                "cns_get_partition_status",
                "cns_results_layout", "cns_comm_unique_id", "cns_comm_init_rank", "cns_comm_destroy", "cns_allgather_results",
@@ -132,6 +132,15 @@ def select_shape() -> "abi.SelectShape":
     tile = lambda t: abi.TileShape(int(t.lanes), tuple(int(w) for w in t.widths[:t.num_widths]))
     scalars = [int(getattr(s, f)) for f in abi.SelectShape._fields[:-3]]
     return abi.SelectShape(*scalars, tile(s.select), tile(s.pipe), tuple((int(s.wide_waves[b]), tile(s.wide[b])) for b in range(4)))
+
+
+def serial_shape() -> "abi.SerialShape":
+    """cns_serial_shape: the loop shapes of the serial protocol (k_mem, k_giant), as this build has them.  Needs no handle and no GPU."""
+    s = abi.CnsSerialShapeInfo()
+    status = lib().cns_serial_shape(C.byref(s))
+    if status != 0:
+        raise EngineError(status, "cns_serial_shape")
+    return abi.SerialShape(*[int(getattr(s, f)) for f in abi.SerialShape._fields])
 
 
 def probe_shape() -> "abi.ProbeShape":

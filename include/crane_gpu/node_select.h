@@ -392,6 +392,28 @@ typedef struct cns_select_shape_info {
 } cns_select_shape_info;
 int cns_select_shape(cns_select_shape_info* out);
 
+/* The loop shapes of the serial protocol: k_wide<1>'s home workgroup alone over the HBM arrays (k_mem) or with helper workgroups
+ * (k_giant).  It serves a group of partitions that share nodes and is wider than k_select's widest tile, and a partition wider
+ * than k_wide's.  Read from the kernels' and the launch plan's own constants; tests/serial_seams.py puts a case on each.
+ * Row r of scanner lane l of a job is slot rb + r * scan_lanes + l of the job's range [rb, rb + rn); helper h of nh, lane t,
+ * takes the slots rb + h * helper_lanes + t + i * nh * helper_lanes.  nh = min(helpers_max, helper_budget / busy partitions of
+ * the launch); below helpers_min the launch is k_mem.  Needs no handle and no device. */
+typedef struct cns_serial_shape_info {
+  uint32_t scan_lanes;         /* memory-scanner lanes of the home workgroup (kWMs)                                          */
+  uint32_t scan_trip_rows;     /* rows of a lane per trip of its scan; a mask word (64 rows) is flushed on a trip's end      */
+  uint32_t mem_words;          /* 64-row mask words per lane: the ordinary instantiation (kWMemWords) ...                    */
+  uint32_t giant_mem_words;    /* ... and the giant one (kWMemWordsGiant): every k_giant launch, k_mem above mem_slots       */
+  uint32_t mem_slots;          /* slots the ordinary masks hold: scan_lanes * 64 * mem_words                                 */
+  uint32_t giant_mem_slots;    /* slots the giant masks hold: the widest group cns_set_nodes takes                           */
+  uint32_t helper_lanes;       /* lanes of a helper workgroup (kWBlock)                                                      */
+  uint32_t helper_trip_slots;  /* slots of a helper lane per trip of its scan                                                */
+  uint32_t helpers_max;        /* helper workgroups per partition at most (kGiantHelpersMax)                                 */
+  uint32_t helper_budget;      /* helper workgroups per launch at most (kGiantHelperBudget)                                  */
+  uint32_t helpers_min;        /* the least helper count per partition that still launches k_giant                           */
+  uint32_t select_tile_slots;  /* k_select's widest tile: a shared group of more slots goes to the serial protocol           */
+} cns_serial_shape_info;
+int cns_serial_shape(cns_serial_shape_info* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,8 +45,25 @@ static bool has(const CyclePlan& P, Family f) {
   return false;
 }
 
-int main() {
+// `plan_host_test serial <n>`: what CNS_SELECT_KERNEL=giant launches for 1 .. n busy partitions of 64 slots, one line each:
+// "<busy> <first candidate's kernel> <its helper workgroups per partition>" (tests/test_serial_seams.py reads the rule from here).
+static int serial_table(const Facts& F, u32 n) {
+  printf("helpers_min %u\n", kGiantMinHelpers);
+  for (u32 busy = 1; busy <= n; ++busy) {
+    Inputs in = cluster(busy, 64);
+    in.sw = Switch::Giant;
+    const CyclePlan P = plan_cycle(F, in);
+    if (!P.a.parts.empty() || !P.b.parts.empty() || P.c.cands.empty()) return 1;
+    const Candidate& c = P.c.cands[0];
+    printf("%u %s %u %d\n", busy, kernel_of(c).c_str(), c.family == Family::Giant ? c.extra : 0u, (int)c.giant_masks);
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
   const Facts F = shipped();
+  if (argc == 3 && std::string(argv[1]) == "serial") return serial_table(F, (u32)std::stoul(argv[2]));
+  CHECK(kGiantMinHelpers == 4);
   CHECK(F.wide[0].tiles.slots() == 65536 && F.wide[1].tiles.slots() == 16384 && F.wide[2].tiles.slots() == 8192 && F.wide[3].tiles.slots() == 4096);
   CHECK(F.select.slots() == 37 * 448 && F.pipe.slots() == 8192);
 
