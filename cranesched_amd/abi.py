@@ -883,6 +883,19 @@ class CnsRunningTiming(C.Structure):
                 ("pairs", C.c_uint64)]
 
 
+# include/crane_gpu_amend/running_amend.h
+class CnsRunningAmend(C.Structure):
+    _fields_ = [("num_amend", C.c_uint64), ("job_ids", _P), ("end_sec", _P)]
+
+
+class CnsRunningAmendOut(C.Structure):
+    _fields_ = [("found", _P), ("num_amended", _P)]
+
+
+class CnsRunningAmendTiming(C.Structure):
+    _fields_ = [("h2d_ms", C.c_double), ("kernels_ms", C.c_double), ("d2h_ms", C.c_double), ("rows", C.c_uint64), ("pairs", C.c_uint64)]
+
+
 # include/crane_gpu_running/running_preempt.h
 class CnsPreemptIndexOut(C.Structure):
     _fields_ = [("capacity_entries", C.c_uint64), ("capacity_rows", C.c_uint64), ("num_entries", _P), ("num_rows", _P)] + \

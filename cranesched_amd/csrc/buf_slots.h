@@ -67,7 +67,8 @@ enum { RL_ID = 0, RL_END, RL_RESV, RL_OFF, RL_NODE, RL_RES,                     
        RL_WID, RL_WEND, RL_WRESV, RL_WOFF, RL_WNODE, RL_WRES,                                               // the call's copy of it
        RL_RET, RL_FOUND, RL_JID, RL_ADMIT, RL_JRESV,                                                        // the call's lists
        RL_WROWS0, RL_WENTS0, RL_WROWS1, RL_WENTS1, RL_TOT, RL_NSOFF, RL_NS, RL_WEXP,                        // counts, the node -> slots CSR
-       RL_K0, RL_K1, RL_V0, RL_V1, RL_HIST, RL_RNOFF, RL_RNEND, RL_RNRES, RL_FLAG, RL_COUNT };              // pairs, the per-slot tables
+       RL_K0, RL_K1, RL_V0, RL_V1, RL_HIST, RL_RNOFF, RL_RNEND, RL_RNRES, RL_FLAG,                          // pairs, the per-slot tables
+       RL_AMID, RL_AMEND, RL_COUNT };                                                                       // cns_running_amend_ends: the sorted ids, their ends
 
 // cns_engine::d_rp (running_preempt_host.inc): the sorted (slot, allocation) pairs of the last rebuild, the index built from them,
 // the call's lists and tables

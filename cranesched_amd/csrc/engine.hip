@@ -33,6 +33,7 @@
 #include "../../include/crane_gpu_running/running.h"
 #include "../../include/crane_gpu_running/running_preempt.h"
 #include "../../include/crane_gpu_running/running_attrs.h"
+#include "../../include/crane_gpu_amend/running_amend.h"
 #include "../../include/crane_gpu/run_limits.h"
 #include "../../include/crane_gpu/steps.h"
 #include <limits>
@@ -53,6 +54,7 @@
 #include "running_kernels.inc" // the running set kept on the device between two cycles: retire, admit, rebuild (include/crane_gpu_running/running.h)
 #include "running_preempt_kernels.inc" // a cycle with preemption on that set: the entry index, the job -> entries CSR, the marks and the end patch (include/crane_gpu_running/running_preempt.h)
 #include "running_attrs_kernels.inc" // the attribute columns beside that set, the per-row sums and the running side of the sorter taken from them (include/crane_gpu_running/running_attrs.h)
+#include "running_amend_kernels.inc" // a running job's end time changed on that set: the end column and the per-slot end times (include/crane_gpu_amend/running_amend.h)
 #include "jobs_host.inc"       // the host pass of cns_upload_jobs (no HIP in there: also compiled by the CPU tests)
 #include "plan_host.inc"       // the launch plan of a cycle: which kernel serves which partitions (no HIP in there either)
 #include "csr_host.inc"        // the CSR rules of the callers' lists: offsets, sorted lists without a repeat (no HIP in there either)
@@ -63,6 +65,7 @@
 #include "submit_check_host.inc" // the input rules of cns_set_submit_limits / cns_check_submissions (no HIP in there either)
 #include "usage_check_host.inc" // the input rules of cns_usage_set_tables / cns_usage_apply (no HIP in there either)
 #include "running_check_host.inc" // the input rules of cns_running_seed / cns_running_advance (no HIP in there either)
+#include "running_amend_check_host.inc" // the input rules of cns_running_amend_ends (no HIP in there either)
 #include "preempt_host.inc"    // the host side of a cycle with preemption: who may preempt, the buffer plan, the running side, the fold of the results (no HIP in there either)
 #include "running_preempt_check_host.inc" // the input rules of cns_running_select_preempt (no HIP in there either)
 #include "running_attrs_check_host.inc" // the input rules of the calls of running_attrs.h (no HIP in there either)
@@ -256,6 +259,7 @@ struct cns_engine {
   u64 lay_gen = 0, rl_lay_gen = ~0ull;          // uploads of the snapshot so far; the one RL_NSOFF / RL_NS were derived from
   u32 rl_fan = 1;                               // slots of the node in most partitions
   cns_running_timing rl_timing{};
+  cns_running_amend_timing am_timing{};         // the last cns_running_amend_ends (running_amend_host.inc)
   // a cycle with preemption on that set (running_preempt_host.inc): the sorted pairs of the rebuild the per-slot tables came from, the
   // index built from them, the call's lists and tables
   DevBuf d_rp[RP_COUNT];
@@ -1282,6 +1286,7 @@ int cns_debug_get_timeline_cores(cns_handle* h, uint32_t node, uint32_t capacity
 #include "running_host.inc"
 #include "running_preempt_host.inc"
 #include "running_attrs_host.inc"
+#include "running_amend_host.inc"
 
 }  // extern "C"
 

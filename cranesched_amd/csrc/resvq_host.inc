@@ -14,27 +14,29 @@ static u64 rq_interval_cap() {
   return std::min<u64>(kRqMaxIntervals, strtoull(e, nullptr, 10));
 }
 
-static int resvq_set_state_impl(cns_handle* h, const cns_running_soa* rn, const cns_resv_soa* rv) {
+// the running side of the per-node tables: the arrays k_rq_latest reads, on the host (uploaded into RQ_RAW_*) or on the device where they are
+struct RqRunning {
+  const i64* end = nullptr;    // [jobs]
+  const u32* off = nullptr;    // [jobs + 1]
+  const u32* node = nullptr;   // [allocs]
+  u32 jobs = 0, allocs = 0;
+  bool host = false;
+};
+
+// everything behind the running side: the reservations' per-node CSR, latest_end[N].  who: the call's name in front of its messages
+static int resvq_set_state_tables(cns_handle* h, const RqRunning& side, const cns_resv_soa* rv, const std::string& who) {
   const u32 N = h->lay.N;
-  const u32 RJ = rn ? rn->num_jobs : 0, RA = rn ? rn->num_allocs : 0;
-  if (RJ && (!rn->end_sec || !rn->alloc_offsets || (RA && !rn->alloc_node))) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: missing array (running)");
-  if (RJ) {
-    if (rn->alloc_offsets[0] != 0 || rn->alloc_offsets[RJ] != RA) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: running alloc_offsets do not span num_allocs");
-    for (u32 j = 0; j < RJ; ++j)
-      if (rn->alloc_offsets[j] > rn->alloc_offsets[j + 1]) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: running alloc_offsets decrease");
-    for (u32 a = 0; a < RA; ++a)
-      if (rn->alloc_node[a] >= N) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: running allocation on a node >= num_nodes");
-  }
+  const u32 RJ = side.jobs, RA = side.allocs;
   const u32 V = rv ? rv->num_resv : 0, VA = V ? rv->alloc_offsets ? rv->alloc_offsets[V] : 0 : 0;
-  if (V && (!rv->start_sec || !rv->end_sec || !rv->alloc_offsets || (VA && !rv->alloc_node))) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: missing array (reservations)");
+  if (V && (!rv->start_sec || !rv->end_sec || !rv->alloc_offsets || (VA && !rv->alloc_node))) return fail(h, CNS_ERR_INVALID_ARG, who + ": missing array (reservations)");
   // per node: the (start, end) of every reservation that lists it, sorted (the earliest-start walk merges them in this order)
   std::vector<u32> off((size_t)N + 1, 0);
   if (V) {
-    if (rv->alloc_offsets[0] != 0) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: reservation alloc_offsets do not start at 0");
+    if (rv->alloc_offsets[0] != 0) return fail(h, CNS_ERR_INVALID_ARG, who + ": reservation alloc_offsets do not start at 0");
     for (u32 v = 0; v < V; ++v)
-      if (rv->alloc_offsets[v] > rv->alloc_offsets[v + 1]) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: reservation alloc_offsets decrease");
+      if (rv->alloc_offsets[v] > rv->alloc_offsets[v + 1]) return fail(h, CNS_ERR_INVALID_ARG, who + ": reservation alloc_offsets decrease");
     for (u32 a = 0; a < VA; ++a) {
-      if (rv->alloc_node[a] >= N) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: reservation on a node >= num_nodes");
+      if (rv->alloc_node[a] >= N) return fail(h, CNS_ERR_INVALID_ARG, who + ": reservation on a node >= num_nodes");
       ++off[(size_t)rv->alloc_node[a] + 1];
     }
   }
@@ -61,14 +63,17 @@ static int resvq_set_state_impl(cns_handle* h, const cns_running_soa* rn, const 
   hipLaunchKernelGGL(k_fill_i64, dim3((N + 255) / 256), dim3(256), 0, h->stream, B[RQ_LATEST].as<i64>(), N, (i64)INT64_MIN);
   HIPCHK(h, hipGetLastError());
   if (RA) {
-    HIPCHK(h, B[RQ_RAW_END].ensure((size_t)RJ * 8));
-    HIPCHK(h, B[RQ_RAW_OFF].ensure(((size_t)RJ + 1) * 4));
-    HIPCHK(h, B[RQ_RAW_NODE].ensure((size_t)RA * 4));
-    HIPCHK(h, hipMemcpyAsync(B[RQ_RAW_END].p, rn->end_sec, (size_t)RJ * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(B[RQ_RAW_OFF].p, rn->alloc_offsets, ((size_t)RJ + 1) * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(B[RQ_RAW_NODE].p, rn->alloc_node, (size_t)RA * 4, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_rq_latest, dim3((RA + 255) / 256), dim3(256), 0, h->stream, (const i64*)B[RQ_RAW_END].as<i64>(),
-                       (const u32*)B[RQ_RAW_OFF].as<u32>(), (const u32*)B[RQ_RAW_NODE].as<u32>(), RJ, RA, N, B[RQ_LATEST].as<i64>());
+    const i64* d_end = side.end; const u32* d_off = side.off; const u32* d_node = side.node;
+    if (side.host) {
+      HIPCHK(h, B[RQ_RAW_END].ensure((size_t)RJ * 8));
+      HIPCHK(h, B[RQ_RAW_OFF].ensure(((size_t)RJ + 1) * 4));
+      HIPCHK(h, B[RQ_RAW_NODE].ensure((size_t)RA * 4));
+      HIPCHK(h, hipMemcpyAsync(B[RQ_RAW_END].p, side.end, (size_t)RJ * 8, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(B[RQ_RAW_OFF].p, side.off, ((size_t)RJ + 1) * 4, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(B[RQ_RAW_NODE].p, side.node, (size_t)RA * 4, hipMemcpyHostToDevice, h->stream));
+      d_end = B[RQ_RAW_END].as<i64>(); d_off = B[RQ_RAW_OFF].as<u32>(); d_node = B[RQ_RAW_NODE].as<u32>();
+    }
+    hipLaunchKernelGGL(k_rq_latest, dim3((RA + 255) / 256), dim3(256), 0, h->stream, d_end, d_off, d_node, RJ, RA, N, B[RQ_LATEST].as<i64>());
     HIPCHK(h, hipGetLastError());
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));   // (the staging vectors and the caller's arrays are free again)
@@ -76,6 +81,24 @@ static int resvq_set_state_impl(cns_handle* h, const cns_running_soa* rn, const 
   h->rq_rv_cnt = std::move(cnt);
   h->rq_have = true;
   return CNS_OK;
+}
+
+// the running side handed in: its rules, then the shared tables
+static int resvq_set_state_impl(cns_handle* h, const cns_running_soa* rn, const cns_resv_soa* rv) {
+  const u32 N = h->lay.N;
+  const u32 RJ = rn ? rn->num_jobs : 0, RA = rn ? rn->num_allocs : 0;
+  if (RJ && (!rn->end_sec || !rn->alloc_offsets || (RA && !rn->alloc_node))) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: missing array (running)");
+  if (RJ) {
+    if (rn->alloc_offsets[0] != 0 || rn->alloc_offsets[RJ] != RA) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: running alloc_offsets do not span num_allocs");
+    for (u32 j = 0; j < RJ; ++j)
+      if (rn->alloc_offsets[j] > rn->alloc_offsets[j + 1]) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: running alloc_offsets decrease");
+    for (u32 a = 0; a < RA; ++a)
+      if (rn->alloc_node[a] >= N) return fail(h, CNS_ERR_INVALID_ARG, "cns_resvq_set_state: running allocation on a node >= num_nodes");
+  }
+  RqRunning side;
+  if (rn) { side.end = rn->end_sec; side.off = rn->alloc_offsets; side.node = rn->alloc_node; }
+  side.jobs = RJ; side.allocs = RA; side.host = true;
+  return resvq_set_state_tables(h, side, rv, "cns_resvq_set_state");
 }
 
 int cns_resvq_set_state(cns_handle* h, const cns_running_soa* running, const cns_resv_soa* resv) {

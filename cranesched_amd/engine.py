@@ -63,6 +63,8 @@ RUNNING_PREEMPT_ABI_SYMBOLS = ("cns_running_select_preempt", "cns_debug_get_pree
 # ... and include/crane_gpu_running/running_attrs.h
 RUNNING_ATTRS_ABI_SYMBOLS = ("cns_running_seed_attrs", "cns_running_advance_attrs", "cns_running_get_attrs", "cns_priority_order_resident",
                              "cns_running_select_preempt_attrs")
+# ... and include/crane_gpu_amend/running_amend.h
+RUNNING_AMEND_ABI_SYMBOLS = ("cns_running_amend_ends", "cns_running_amend_get_timing", "cns_resvq_set_state_resident")
 LIMITS_ABI_SYMBOLS = ("cns_set_run_limits", "cns_apply_run_limits", "cns_upload_limit_jobs", "cns_run_limits_resident",
                       "cns_download_limits", "cns_get_limit_timing", "cns_get_usage", "cns_limits_shape")
 
@@ -456,6 +458,12 @@ class GpuNodeSelector:
         rv = reservations.to_c() if reservations is not None else None
         self._check(self._L.cns_resvq_set_state(self._h, C.byref(rn) if rn is not None else None, C.byref(rv) if rv is not None else None))
 
+    def set_resv_query_state_resident(self, reservations: "abi.Reservations | None"):
+        """set_resv_query_state with the running side taken from the device ledger where it is (running_amend.h).  The tables do not
+        follow later amends or advances: set them again."""
+        rv = reservations.to_c() if reservations is not None else None
+        self._check(self._L.cns_resvq_set_state_resident(self._h, C.byref(rv) if rv is not None else None))
+
     def query_reservations(self, now: int, queries: "abi.ResvQueries", out: "abi.ResvAnswers | None" = None) -> dict:
         """JobScheduler::CreateResv_'s node walk (JobScheduler.cpp:4383-4419) for every query at once, at its start or at the earliest
         start that fits; nothing is created.  -> {status, start_sec, num_free, code, chosen_offsets, chosen_nodes} as numpy arrays."""
@@ -699,6 +707,24 @@ class GpuNodeSelector:
             qa = attrs.to_c() if isinstance(attrs, abi.RunningAttrs) else None
             self._check(self._L.cns_running_advance_attrs(self._h, C.byref(s), C.byref(qa) if qa is not None else None, C.byref(o)))
         return found[:k], int(nret[0]), int(nadm[0])
+
+    # -- a running job's end time changed (include/crane_gpu_amend/running_amend.h) ---------------------------------------------
+    def amend_running(self, job_ids, end_sec):
+        """Every ledger row whose id is job_ids[i] gets end_sec[i] (ChangeJobTimeConstraint, ResumeSuspendedJobs); the per-slot running
+        tables follow when they are the ledger's.  -> (found per id, rows written)."""
+        ids = abi._arr(np.asarray(job_ids, np.uint32).reshape(-1), np.uint32)
+        k = len(ids)
+        ends = abi._arr(np.asarray(end_sec, np.int64).reshape(-1), np.int64, k)
+        found, n = np.zeros(max(k, 1), np.uint8), np.zeros(1, np.uint64)
+        s = abi.CnsRunningAmend(k, abi._ptr(ids) if k else None, abi._ptr(ends) if k else None)
+        o = abi.CnsRunningAmendOut(abi._ptr(found), abi._ptr(n))
+        self._check(self._L.cns_running_amend_ends(self._h, C.byref(s), C.byref(o)))
+        return found[:k], int(n[0])
+
+    def running_amend_timing(self) -> dict:
+        t = abi.CnsRunningAmendTiming()
+        self._check(self._L.cns_running_amend_get_timing(self._h, C.byref(t)))
+        return {f: getattr(t, f) for f, _ in abi.CnsRunningAmendTiming._fields_}
 
     def running_attrs(self) -> dict:
         """The attribute columns of the device ledger and the three values derived per row (node_num, alloc_cpu_raw, alloc_mem: what

@@ -27,6 +27,7 @@
 #include "../../include/crane_gpu_running/running.h"
 #include "../../include/crane_gpu_running/running_preempt.h"
 #include "../../include/crane_gpu_running/running_attrs.h"
+#include "../../include/crane_gpu_amend/running_amend.h"
 
 namespace crane {
 
@@ -1219,6 +1220,7 @@ bool GpuNodeSelectionAlgo::AdvanceRunning(const std::vector<job_id_t>& finished_
   }
   if (st != 0) return fail(st, cns_last_error(I.h));
   I.resident_stale = false;
+  I.resvq_stale = true;   // (QueryReservation's tables were taken from the ledger as it was)
   if (I.ledger_ids_valid) {   // the ledger's order on this side: a stable erase, then the admitted jobs in queue order
     std::unordered_set<job_id_t> gone;
     for (size_t i = 0; i < ret.size(); ++i) if (found[i]) gone.insert(ret[i]);
@@ -1230,6 +1232,32 @@ bool GpuNodeSelectionAlgo::AdvanceRunning(const std::vector<job_id_t>& finished_
   }
   if (num_retired) *num_retired = nret;
   if (num_admitted) *num_admitted = nadm;
+  status_ = 0; error_.clear();
+  return true;
+}
+
+// A running job's end time changed (JobScheduler::ChangeJobTimeConstraint, JobScheduler.cpp:2411-2413 — one pair per running child of an
+// array parent, :2312-2321 — and ResumeSuspendedJobs, :2833-2857): the ledger's end column and the per-slot tables follow on the device
+// (include/crane_gpu_amend/running_amend.h).  An id the ledger does not carry changes nothing (ERR_NON_EXISTENT is the caller's, :2302-2305).
+bool GpuNodeSelectionAlgo::AmendRunning(const std::vector<std::pair<job_id_t, TimeSec>>& new_ends, uint64_t* num_amended) {
+  Impl& I = *impl_;
+  auto fail = [&](int st, const std::string& msg) { status_ = st; error_ = msg; return false; };
+  if (num_amended) *num_amended = 0;
+  if (I.grp) return fail(CNS_ERR_UNSUPPORTED, "AmendRunning on an algorithm object over several devices");
+  if (!I.h) return fail(status_ ? status_ : CNS_ERR_NO_DEVICE, error_);
+  if (!I.resident_running) return fail(CNS_ERR_STATE, "AmendRunning needs UseResidentRunning(true): with the running set handed in, write end_time into the RnJobInScheduler");
+  if (!I.have_snapshot) return fail(CNS_ERR_STATE, "AmendRunning before SetClusterSnapshot");
+  std::vector<uint32_t> ids(new_ends.size() + 1);
+  std::vector<int64_t> ends(new_ends.size() + 1);
+  std::vector<uint8_t> found(new_ends.size() + 1, 0);
+  for (size_t i = 0; i < new_ends.size(); ++i) { ids[i] = new_ends[i].first; ends[i] = new_ends[i].second; }
+  uint64_t n = 0;
+  const cns_running_amend in{new_ends.size(), ids.data(), ends.data()};
+  const cns_running_amend_out out{found.data(), &n};
+  const int st = cns_running_amend_ends(I.h, &in, &out);
+  if (st != 0) return fail(st, cns_last_error(I.h));
+  I.resvq_stale = true;   // (QueryReservation's tables were taken from the ledger as it was)
+  if (num_amended) *num_amended = n;
   status_ = 0; error_.clear();
   return true;
 }
@@ -1468,7 +1496,8 @@ std::vector<GpuNodeSelectionAlgo::ResvAnswer> GpuNodeSelectionAlgo::QueryReserva
     cns_resv_soa rv{};
     rv.num_resv = (uint32_t)I.v_start.size(); rv.num_allocs = (uint32_t)I.v_node.size();
     rv.start_sec = I.v_start.data(); rv.end_sec = I.v_end.data(); rv.alloc_offsets = I.v_off.data(); rv.alloc_node = I.v_node.data();
-    st = cns_resvq_set_state(I.h, rs.num_jobs ? &rs : nullptr, rv.num_resv ? &rv : nullptr);
+    // with resident running on nothing packs the running set after SeedRunning: the running side comes from the device ledger
+    st = I.resident_running ? cns_resvq_set_state_resident(I.h, rv.num_resv ? &rv : nullptr) : cns_resvq_set_state(I.h, rs.num_jobs ? &rs : nullptr, rv.num_resv ? &rv : nullptr);
     if (st != 0) return fail(st, cns_last_error(I.h));
     I.resvq_stale = false;
   }

@@ -386,6 +386,8 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   // in one list, duration <= 0) the result is empty and Ok() / LastStatus() / LastError() say why; nothing is thrown.
   // The engine's per-node tables (cns_resvq_set_state) are rebuilt only when the running set or the snapshot was packed anew since the
   // last call.  As in a cycle, a running job whose reservation name the snapshot does not know is not part of the packed running set.
+  // With resident running on nothing packs the running set behind SeedRunning: the running side then comes from the device ledger
+  // (cns_resvq_set_state_resident) and is taken again behind SeedRunning, AdvanceRunning, AmendRunning and a new snapshot.
   struct ResvRequest {
     TimeSec start{0};
     int64_t duration{0};
@@ -644,6 +646,13 @@ class GpuNodeSelectionAlgo final : public INodeSelectionAlgo {
   bool SeedRunning(const std::vector<std::unique_ptr<RnJobInScheduler>>& running_jobs);
   bool AdvanceRunning(const std::vector<job_id_t>& finished_job_ids, const std::vector<const PdJobInScheduler*>& admitted,
                       uint64_t* num_retired = nullptr, uint64_t* num_admitted = nullptr);
+  // A running job's end time changed (include/crane_gpu_amend/running_amend.h): JobScheduler::ChangeJobTimeConstraint's SetEndTime
+  // (JobScheduler.cpp:2411-2413; an array parent: one pair per running child, :2312-2321) and ResumeSuspendedJobs (:2833-2857).  Valid
+  // with resident running on; (job id, new end_time) pairs in any order, ids distinct.  The ledger's end column and the per-slot
+  // running tables follow on the device: no re-seed.  A job the ledger does not carry changes nothing and is not counted in
+  // *num_amended.  With resident running on, QueryReservation takes its running side from the ledger (cns_resvq_set_state_resident)
+  // and refreshes it behind SeedRunning, AdvanceRunning, AmendRunning and a new snapshot.
+  bool AmendRunning(const std::vector<std::pair<job_id_t, TimeSec>>& new_ends, uint64_t* num_amended = nullptr);
 
   // ---- event-fed mirror of the running allocations -------------------------------------------------
   // Instead of re-deriving the running jobs' allocations from the vector NodeSelect is handed every cycle, the adapter
